@@ -2,13 +2,21 @@
 """Headline benchmark: images/sec of one RADet train step (forward + loss + backward + gradient
 all-reduce + grad-clip + AdamW), r50_ycbv_pbr, 640x480, batch 4 per GPU, fp32, synthetic data.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  The timed region contains only the
 product path (HIP kernels through the C ABI + RCCL); the oracle is used solely for the
-`cpu_baseline` leg (rank 0, N = 1), as the thing that is timed next to the GPU number.
+`cpu_baseline` leg (rank 0, N = 1, --full), as the thing that is timed next to the GPU number.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure
+(per-kernel HIP-event table / roofline, clock and power, the native-f32-MFMA and secondary child runs,
+the CPU baseline, the traced bucket exchange of data-parallel runs) runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (rank 0): DIR/losses.npy (the loss triple
+train_step returns), DIR/params.npy and DIR/grads.npy (the trainable parameters after the step and the
+step's gradients, float32, at DUMP_SAMPLE elements: np.random.default_rng(0).choice(n, DUMP_SAMPLE,
+replace=False), sorted, of the flat arenas of n elements).
 """
 import argparse
 import json
@@ -36,6 +44,7 @@ ISSUED_PER_MAC = 6.0 if os.environ.get("RADET_X3", "h2") in ("bf16", "b3") else 
 
 
 INFER_FLOP_PER_IMG = 120.96e9      # forward conv MACs x 2 of one 640x480 image (backbone + FPN + head)
+DUMP_SAMPLE = 1 << 21              # --dump-outputs: sampled elements of the parameter / gradient arenas (8 MB each)
 
 
 class ClockSampler:
@@ -427,7 +436,8 @@ def extras(args):
         except Exception as e:                   # the headline line must not depend on the secondary runs
             out[key] = {"error": repr(e)[:200]}
     me = os.path.abspath(__file__)
-    short = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-mfma-line", "--no-extras"]
+    short = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-mfma-line",
+             "--no-extras"]
     try:                                         # BASELINE configs[2] arithmetic on one GPU (bf16 tensors + operands)
         d = _child([me, "--math", "bf16-storage"] + short)
         out["bf16_storage"] = {
@@ -457,7 +467,7 @@ def extras(args):
         out["bs16"] = {"error": repr(e)[:200]}
     try:
         d = _child([os.path.abspath(__file__), "--weights", "synth", "--steps", str(args.steps), "--warmup", str(args.warmup),
-                    "--no-cpu-baseline", "--no-kernel-events", "--no-mfma-line", "--no-extras"])
+                    "--full", "--no-cpu-baseline", "--no-kernel-events", "--no-mfma-line", "--no-extras"])
         out["synthetic_trained_like_weights"] = {
             "value": d["value"], "unit": "images/sec", "ms_per_step": d["ms_per_step"], "clock_power": d.get("clock_power"),
             "losses_step1": d["config"]["losses_step1"],
@@ -467,6 +477,18 @@ def extras(args):
     except Exception as e:
         out["synthetic_trained_like_weights"] = {"error": repr(e)[:200]}
     return out
+
+
+def dump_outputs(path, loss, flat, device):
+    """--dump-outputs: the loss triple of the last timed step, and DUMP_SAMPLE seeded elements of the trainable parameters
+    after it and of its gradients (the arenas hold tens of millions of floats), as float32 .npy files."""
+    os.makedirs(path, exist_ok=True)
+    n = flat.n_train
+    idx = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_SAMPLE), replace=False))
+    sel = torch.from_numpy(idx).to(device)
+    np.save(os.path.join(path, "losses.npy"), loss.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "params.npy"), flat.params[sel].float().cpu().numpy())
+    np.save(os.path.join(path, "grads.npy"), flat.grads[sel].float().cpu().numpy())
 
 
 def main():
@@ -491,7 +513,15 @@ def main():
     ap.add_argument("--math", choices=("fp32", "fp32-mfma", "bf16", "bf16-storage"), default="fp32",
                     help="fp32 = the headline metric (BASELINE configs[1]); bf16 = configs[2] arithmetic: conv operands "
                          "rounded to bf16 into the matrix cores, fp32 accumulate / storage / optimizer (secondary line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline step (kernel events / roofline, clock and power, "
+                         "native-f32-MFMA and secondary child runs, CPU baseline, traced bucket exchange); the --no-* options "
+                         "switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the loss triple, and sampled parameters and gradients, of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:                         # a plain run measures the headline step only
+        args.no_cpu_baseline = args.no_kernel_events = args.no_mfma_line = args.no_clock_sampler = args.no_extras = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` started plainly: become the launcher -- N worker processes through torch.distributed.run
@@ -606,6 +636,8 @@ def main():
     t_end = t0 + dt
     dt_rank = dt
     losses = rt.engine.losses.cpu().numpy()
+    if rank == 0 and args.dump_outputs:       # before anything else runs a step
+        dump_outputs(args.dump_outputs, out_l, rt.flat, device)
     # the same K steps once more with a pair of HIP events around EVERY conv GEMM launch, on the stream it is launched on
     # (radet_amd.kernels.EVENTS): the per-kernel table behind `roofline`.  Kept out of the region above so that `value` is
     # the uninstrumented step; the instrumented step time is reported next to it.
@@ -646,7 +678,7 @@ def main():
     dt = float(t.item())
 
     comm = None
-    if rt.reducer is not None:                # data-parallel runs: a few more steps with the bucket exchange traced
+    if rt.reducer is not None and args.full:  # data-parallel runs: a few more steps with the bucket exchange traced
         rt.reducer.enable_trace(True)
         for _ in range(min(args.steps, 8)):
             rt.train_step(img, tg, next_img=nxt)
@@ -721,7 +753,8 @@ def main():
             import subprocess
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--math", "fp32-mfma", "--steps", str(args.steps),
-                                    "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-kernel-events", "--no-extras"],
+                                    "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-kernel-events",
+                                    "--no-extras"],
                                    capture_output=True, text=True, timeout=600)
                 line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
                 d2 = json.loads(line)

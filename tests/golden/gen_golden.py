@@ -539,6 +539,43 @@ def gen_recall():
     save("recall", **out)
 
 
+def ref_dist_cases():
+    """Inputs of the MBD / GDT comparison (tests/test_oracle.py::test_distance_oracle_matches_reference_build): ragged crop
+    sizes incl. crops larger than base_size^2 (integer size factor) and odd niter."""
+    from oracle import dist
+    rs = np.random.RandomState(0)
+    for (h, w, niter, base) in ((150, 200, 4, 300), (37, 53, 4, 300), (64, 41, 3, 40), (2, 2, 4, 300), (90, 90, 5, 30)):
+        img = (rs.rand(h, w, 3) * 255).astype(np.uint8)
+        img[h // 4:3 * h // 4, w // 4:3 * w // 4] //= 3
+        sx, sy = dist.border_seeds(h, w)
+        cost = rs.rand(h, w).astype(np.float32)
+        yield (h, w, niter, base), img, sx, sy, cost
+
+
+def gen_ref_ops():
+    """Outputs of the reference's own C++ ops (vote_ext.cpp, bbox2distance_ext.cpp, compiled into oracle/_ref by
+    oracle/build_ref.py) on the inputs of tests/test_oracle.py's two comparisons against them: nms.npz's boxes and
+    ref_dist_cases()."""
+    from oracle import build_ref
+    vote, b2d = build_ref.load("ref_vote_ext"), build_ref.load("ref_bbox2distance_ext")
+    assert vote is not None and b2d is not None, "oracle/_ref not built"
+    g = np.load(os.path.join(HERE, "nms.npz"))
+    out = {}
+    for tag in "abc":
+        bx = torch.from_numpy(g[tag + "_boxes"])
+        sc = torch.from_numpy(g[tag + "_cls"] * g[tag + "_ctr"])
+        lb = torch.from_numpy(g[tag + "_labels"])
+        for fn in ("vote_nms", "global_vote_nms"):
+            for iou_enable in (False, True):
+                rb, rl, rs = getattr(vote, fn)(bx, sc, sc.clone(), lb, 0.65, iou_enable, 0.025)
+                k = f"{tag}_{fn}_{int(iou_enable)}"
+                out[k + "_b"], out[k + "_l"], out[k + "_s"] = rb.numpy(), rl.numpy(), rs.numpy()
+    for i, ((h, w, niter, base), img, sx, sy, cost) in enumerate(ref_dist_cases()):
+        out[f"mbd{i}"] = b2d.MBD(torch.from_numpy(img), torch.from_numpy(sx), torch.from_numpy(sy), 0.1, niter, base).numpy()
+        out[f"gdt{i}"] = b2d.GDT(torch.from_numpy(cost), torch.from_numpy(sx), torch.from_numpy(sy)).numpy()
+    save("ref_ops", **out)
+
+
 def gen_model_grads(det, assign, out_name="model_grads"):
     """Sampled gradient ELEMENTS of every trainable parameter (model.npz holds only their norms, which a tap transposition
     or a sign error inside a tensor would preserve): same weights / batch as gen_model."""
@@ -597,6 +634,9 @@ def main():
         det = build_detector(model_cfg, train_cfg=train_cfg, test_cfg=test_cfg)
         synth.fill_state_dict(det.state_dict(), seed=0)
         gen_model_grads(det, dict(np.load(os.path.join(HERE, "assigner.npz"))))
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "ref_ops":    # only ref_ops.npz (needs oracle/_ref: oracle/build_ref.py)
+        gen_ref_ops()
         return
     torch.manual_seed(0)
     model_cfg, train_cfg, test_cfg = ref_import.load_cfg()

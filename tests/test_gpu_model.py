@@ -233,12 +233,14 @@ def test_collectives_run_on_their_own_stream(comm_stream):
     for what the handing (side) stream does after the hand-over: with the main stream parked in a long spin kernel BEFORE the hand-over and the side stream parked in one AFTER
     it, the collective still completes at once.  Run in a process of its own: in the test process dozens of streams from the
     other tests share the device's hardware queues, and a collective queued behind a parked stream's spin kernel in the same
-    hardware queue says nothing about stream dependencies."""
+    hardware queue says nothing about stream dependencies.  For the same reason the probe asks for 8 hardware queues itself
+    (radet_amd only sets its default of 8 when the environment names no count: with 4, the probe's main, side, probe, comm and
+    RCCL streams share queues)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, "-c", _OWN_STREAM_PROBE], cwd=root, capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, PROBE_COMM_STREAM=comm_stream))
+                         env=dict(os.environ, PROBE_COMM_STREAM=comm_stream, GPU_MAX_HW_QUEUES="8"))
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("PARKED")][-1]
     assert line.split()[1:] == ["True", "True"], line

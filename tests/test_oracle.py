@@ -108,21 +108,23 @@ def test_nms_ops(golden, tag):
 
 
 def test_nms_against_reference_binary(golden):
-    """oracle/_ref = the reference's own vote_ext.cpp compiled here; also covers iou_enable=True."""
+    """The reference's own vote_ext.cpp: its outputs recorded in tests/golden/ref_ops.npz (gen_golden.py ref_ops), and the
+    compiled op itself where oracle/_ref is built; also covers iou_enable=True."""
     from oracle import build_ref
     ref = build_ref.load("ref_vote_ext")
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
-    g = golden("nms")
+    g, r = golden("nms"), golden("ref_ops")
     for tag in "abc":
         bx = torch.from_numpy(g[tag + "_boxes"])
         sc = torch.from_numpy(g[tag + "_cls"] * g[tag + "_ctr"])
         lb = torch.from_numpy(g[tag + "_labels"])
-        for mine, theirs in ((onms.vote_nms_raw, ref.vote_nms), (onms.global_vote_nms_raw, ref.global_vote_nms)):
+        for mine, fn in ((onms.vote_nms_raw, "vote_nms"), (onms.global_vote_nms_raw, "global_vote_nms")):
             for iou_enable in (False, True):
-                rb, rl, rs = theirs(bx, sc, sc.clone(), lb, 0.65, iou_enable, 0.025)
+                k = f"{tag}_{fn}_{int(iou_enable)}"
                 ob, ol, os_ = mine(bx.numpy(), sc.numpy(), sc.numpy(), lb.numpy(), 0.65, iou_enable, 0.025)
-                assert np.array_equal(rb.numpy(), ob) and np.array_equal(rl.numpy(), ol) and np.array_equal(rs.numpy(), os_)
+                assert np.array_equal(r[k + "_b"], ob) and np.array_equal(r[k + "_l"], ol) and np.array_equal(r[k + "_s"], os_)
+                if ref is not None:
+                    rb, rl, rs = getattr(ref, fn)(bx, sc, sc.clone(), lb, 0.65, iou_enable, 0.025)
+                    assert np.array_equal(rb.numpy(), ob) and np.array_equal(rl.numpy(), ol) and np.array_equal(rs.numpy(), os_)
 
 
 def test_nms_empty_and_single():
@@ -288,26 +290,30 @@ def test_mask_oracle_identities():
     assert om.rescale_size((640, 480), (1333, 800)) == (1067, 800) and om.rescale_size((640, 480), 0.5) == (320, 240)
 
 
-def test_distance_oracle_matches_reference_build():
-    """oracle/dist.c (MBD / GDT raster scans) == the reference's bbox2distance_ext.cpp compiled in place (oracle/_ref),
-    bit for bit, on ragged crop sizes incl. crops larger than base_size^2 (integer size factor) and odd niter."""
+def test_distance_oracle_matches_reference_build(golden):
+    """oracle/dist.c (MBD / GDT raster scans) == the reference's bbox2distance_ext.cpp, bit for bit: its outputs recorded in
+    tests/golden/ref_ops.npz (gen_golden.py ref_ops), and the op compiled in place (oracle/_ref) where it is built, on ragged
+    crop sizes incl. crops larger than base_size^2 (integer size factor) and odd niter."""
     import torch
     from oracle import build_ref, dist
     ref = build_ref.load("ref_bbox2distance_ext")
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference)")
+    r = golden("ref_ops")
     rs = np.random.RandomState(0)
-    for (h, w, niter, base) in ((150, 200, 4, 300), (37, 53, 4, 300), (64, 41, 3, 40), (2, 2, 4, 300), (90, 90, 5, 30)):
+    for i, (h, w, niter, base) in enumerate(((150, 200, 4, 300), (37, 53, 4, 300), (64, 41, 3, 40), (2, 2, 4, 300),
+                                             (90, 90, 5, 30))):
         img = (rs.rand(h, w, 3) * 255).astype(np.uint8)
         img[h // 4:3 * h // 4, w // 4:3 * w // 4] //= 3
         sx, sy = dist.border_seeds(h, w)
         a = dist.mbd(img, sx, sy, 0.1, niter, base)
-        b = ref.MBD(torch.from_numpy(img), torch.from_numpy(sx), torch.from_numpy(sy), 0.1, niter, base).numpy()
-        assert np.array_equal(a, b), (h, w)
+        assert np.array_equal(a, r[f"mbd{i}"]), (h, w)
         cost = rs.rand(h, w).astype(np.float32)
         c = dist.gdt(cost, sx, sy)
-        d = ref.GDT(torch.from_numpy(cost), torch.from_numpy(sx), torch.from_numpy(sy)).numpy()
-        assert np.array_equal(c, d), (h, w)
+        assert np.array_equal(c, r[f"gdt{i}"]), (h, w)
+        if ref is not None:
+            b = ref.MBD(torch.from_numpy(img), torch.from_numpy(sx), torch.from_numpy(sy), 0.1, niter, base).numpy()
+            assert np.array_equal(a, b), (h, w)
+            d = ref.GDT(torch.from_numpy(cost), torch.from_numpy(sx), torch.from_numpy(sy)).numpy()
+            assert np.array_equal(c, d), (h, w)
 
 
 def test_imgproc_oracle_against_scipy():

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/${TAG}_bf16
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 SHORT="--math bf16-storage --no-cpu-baseline --no-mfma-line --no-extras --no-clock-sampler"
-python3 $R/bench.py $SHORT > $OUT/bench_bf16_storage.json 2> $OUT/bench.err
+python3 $R/bench.py --full $SHORT > $OUT/bench_bf16_storage.json 2> $OUT/bench.err
 rm -rf /tmp/prof_b16
 rocprofv3 --kernel-trace -d /tmp/prof_b16 -o p -- python3 $R/bench.py --steps 20 --warmup 3 $SHORT --no-kernel-events > $OUT/prof_run.log 2>&1
 db=$(find /tmp/prof_b16 -name "*.db" | head -1)

@@ -24,7 +24,7 @@ pmc() {    # name, counters (space separated), program args...
 }
 # 1. headline bench: the JSON line (incl. the per-kernel HIP-event table, infer / r101 / trained-like-weights lines), then
 #    kernel stats + timeline (phases, idle gaps) of the same step under rocprofv3
-python3 $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 db=$(prof bench $R/bench.py --steps 20 --warmup 3 $BENCH_SHORT)
 python3 $R/tools/trace_timeline.py $db 5 $OUT/bench_timeline.txt > /dev/null
 # 1b. the same step without plane operands for the towers (RADET_P3=0: every GEMM splits in registers), for comparison
