@@ -450,6 +450,24 @@ int radet_mask_max(const uint8_t* masks, uint32_t* maxes /* [G] */, int G, size_
 int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, int G, int Hs, int Ws, int Hr, int Wr,
                          int Hd, int Wd, int flip, int pad_val, void* stream);
 
+/* ---- BOP training-image augmentation (csrc/augment.hip): RandomBackground merge, CosyPoseAug's PillowBlur /
+ *      PillowSharpness / PillowContrast / PillowBrightness / PillowColor, RandomFlip, Normalize, Pad, batched over packed
+ *      u8 HWC BGR images (every buffer packed alike).  params (device) = nimg rows of AUG_PARAM_INTS ints:
+ *      {pixel offset, h, w, flags, background pixel offset, mask count, mask address lo, hi (u8 [G,h,w]), blur radius,
+ *       blur ww, blur fw, f32 bits of the sharpness / contrast / brightness / color factors, 0};
+ *      flags: 1 merge, 2 blur, 4 sharpness, 8 contrast, 16 brightness, 32 color, 64 horizontal flip, 128 BGR->RGB.
+ *      Four launches per batch in this order; lsum = one u64 luma sum per image (sharp -> finish); out = f32 [nimg,3,Hp,Wp]
+ *      with out = (x - m) * s per channel and zeros beyond each image.  Widths and heights up to AUG_MAX_W. */
+#define AUG_PARAM_INTS 16
+#define AUG_MAX_W 8192
+int radet_augment_merge_hblur(const uint8_t* src, const uint8_t* bg, const int* params, uint8_t* dst, int nimg, int max_h,
+                              int max_w, void* stream);
+int radet_augment_vblur(const uint8_t* src, const int* params, uint8_t* dst, int nimg, int max_h, int max_w, void* stream);
+int radet_augment_sharp(const uint8_t* src, const int* params, uint8_t* dst, unsigned long long* lsum, int nimg, int max_px,
+                        void* stream);
+int radet_augment_finish(const uint8_t* src, const unsigned long long* lsum, const int* params, float* out, int nimg, int Hp,
+                         int Wp, float m0, float m1, float m2, float s0, float s1, float s2, void* stream);
+
 /* ---- stand-alone box / loss operators behind the registered classes (used on their own; inside the detector the same
  *      arithmetic runs fused in radet_head_loss / radet_decode_candidates) ------------------------------------------ */
 /* bbox_overlaps / BboxOverlaps2D (radet/core/bbox/iou_calculators/iou2d_calculator.py:43-159): boxes [batch, M, 4] and

@@ -1,5 +1,6 @@
 from .bop import DATASETS, BOPDataset, YcbvDataset, build_dataset
+from .loader import build_dataloader
 from .pipelines import PIPELINES, GenerateDistanceMap, LabelAssignment, build_pipeline
 
 __all__ = ["PIPELINES", "LabelAssignment", "GenerateDistanceMap", "build_pipeline", "DATASETS", "BOPDataset", "YcbvDataset",
-           "build_dataset"]
+           "build_dataset", "build_dataloader"]

@@ -5,8 +5,9 @@ dictionaries, result-file formats and metric names -- a config or a tool written
 The implementation is this package's own: one pass over the annotation file builds per-image NumPy tables, and filtering,
 grouping, annotation parsing and result serialisation work on those tables.
 
-Host-only Python; image decoding / augmentation stay outside the hot-path scope, so `pipeline` is a list of callables or of
-configs of the registered stages (LabelAssignment, GenerateDistanceMap).  Evaluation runs on radet_amd.datasets.cocoeval
+`pipeline` is a list of callables or stage configs.  A pipeline that starts with LoadImageFromFile is an image pipeline
+(radet_amd.datasets.loading): host decoding and random draws per sample, one batched device pass per batch -- `dataset[idx]`
+is a batch of one, `build_dataloader` feeds whole batches.  Other pipelines run their stages one after the other.  Evaluation runs on radet_amd.datasets.cocoeval
 (a NumPy restatement of pycocotools' COCOeval, which is absent here; parity with pycocotools itself is unpinned)."""
 import json
 import logging
@@ -17,6 +18,7 @@ import numpy as np
 
 from ..utils import Registry, build_from_cfg
 from .cocoeval import COCO, COCOeval, eval_recalls
+from .loading import ImagePipeline, is_image_pipeline
 from .pipelines import PIPELINES
 
 osp = os.path
@@ -100,7 +102,7 @@ class BOPDataset:
             keep = self._filter_imgs()
             self.data_infos = [self.data_infos[i] for i in keep]
             self._set_group_flag()
-        self.pipeline = Compose(pipeline)
+        self.pipeline = ImagePipeline(pipeline) if is_image_pipeline(pipeline) else Compose(pipeline)
         if bop_submission:
             self._det2json = self._bop_det2json
 
@@ -164,12 +166,19 @@ class BOPDataset:
         results.update(img_prefix=self.img_prefix, seg_prefix=self.seg_prefix, proposal_file=self.proposal_file,
                        bbox_fields=[], mask_fields=[], seg_fields=[])
 
-    def _sample(self, idx, with_ann):
+    def _results(self, idx, with_ann):
         results = dict(img_info=self.data_infos[idx])
         if with_ann:
             results["ann_info"] = self.get_ann_info(idx)
         self.pre_pipeline(results)
-        return self.pipeline(results)
+        return results
+
+    def _sample(self, idx, with_ann):
+        return self.pipeline(self._results(idx, with_ann))
+
+    def plan_sample(self, idx, rnd, nprnd):
+        """host part of sample `idx` of an image pipeline on the given generators (thread-safe for distinct ones)"""
+        return self.pipeline.plan(self._results(idx, not self.test_mode), rnd, nprnd)
 
     def prepare_train_img(self, idx):
         return self._sample(idx, True)

@@ -1,0 +1,525 @@
+"""The image side of the reference's BOP data pipelines (radet/datasets/pipelines: loading.py, transforms.py,
+color_aug.py, formating.py, test_time_aug.py) under the reference's stage names and constructor arguments.
+
+Every stage has a host part, `plan(s, rnd, nprnd)`: file decoding (Pillow, into BGR u8 like mmcv.imfrombytes), box
+arithmetic (NumPy, mmdet 2.x Resize / RandomFlip.bbox_flip) and every random draw, in the reference's order, on the
+sample's own generators (`rnd`: a random.Random or the `random` module, `nprnd`: a RandomState or `np.random`).  Planning
+touches no device, so the loader runs it on host threads.  `ImagePipeline.run(planned)` then does the device part of a
+whole batch on the calling thread and stream: the resize of images and backgrounds (radet_resize_linear_u8), mask
+normalisation / resize / flip (radet_mask_transform), the four augmentation launches of csrc/augment.hip and the label
+assigner -- a fixed number of launches whatever the batch size.  A single sample (`BOPDataset.__getitem__`) is a batch
+of one.  Options the RADet configs do not use raise NotImplementedError."""
+import glob
+import math
+import os
+import struct
+
+import numpy as np
+import torch
+
+from .. import kernels as K
+from ..core.mask import rescale_size
+from ..utils import build_from_cfg
+from .pipelines import PIPELINES, GenerateDistanceMap, LabelAssignment
+
+osp = os.path
+DEFAULT_META_KEYS = ("filename", "ori_filename", "ori_shape", "img_shape", "pad_shape", "scale_factor", "flip",
+                     "flip_direction", "img_norm_cfg")
+# stage order of the device part (a pipeline lists a subsequence of it; MultiScaleFlipAug's transforms sit in its place)
+_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Resize", "RandomBackground", "CosyPoseAug", "RandomFlip",
+          "GenerateDistanceMap", "LabelAssignment", "Normalize", "Pad", "DefaultFormatBundle", "ImageToTensor", "Collect")
+_COSY_ORDER = ("PillowBlur", "PillowSharpness", "PillowContrast", "PillowBrightness", "PillowColor")
+# flags of a params row (include/radet_hip.h)
+F_MERGE, F_BLUR, F_SHARP, F_CONTRAST, F_BRIGHT, F_COLOR, F_FLIP, F_TO_RGB = 1, 2, 4, 8, 16, 32, 64, 128
+
+
+def _refuse(what):
+    raise NotImplementedError(f"{what} is not used by the RADet configs and is not implemented")
+
+
+def decode_bgr(path):
+    """mmcv.imfrombytes(flag='color') with Pillow: 3-channel BGR u8"""
+    from PIL import Image
+    with Image.open(path) as im:
+        rgb = np.asarray(im.convert("RGB"))
+    return np.ascontiguousarray(rgb[..., ::-1])
+
+
+def decode_unchanged(path):
+    """mmcv.imfrombytes(flag='unchanged') of an 8-bit single-channel mask PNG"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im) if im.mode in ("L", "P", "1") else np.asarray(im.convert("L"))
+
+
+def blur_params(k):
+    """PIL ImagingGaussianBlur(radius k, 3 passes) -> (box radius, ww, fw) of ImagingHorizontalBoxBlur: the box length of
+    the extended box blur in float32 (sqrt and floor in double, as the C code promotes them), then 24-bit fixed-point weights"""
+    f = np.float32
+    sigma2 = f(f(k) * f(k)) / f(3)
+    L = f(math.sqrt(12.0 * float(sigma2) + 1.0))
+    l = f(math.floor((float(L) - 1.0) / 2.0))
+    a = f(f(f(2) * l + f(1)) * f(l * f(l + f(1)) - f(3) * sigma2))
+    a = f(a / f(f(6) * f(sigma2 - f(l + f(1)) * f(l + f(1)))))
+    radius = f(l + a)
+    ww = int(f(1 << 24) / f(radius * f(2) + f(1)))
+    return int(radius), ww, ((1 << 24) - (2 * int(radius) + 1) * ww) // 2
+
+
+def _f32_bits(v):
+    return struct.unpack("<i", struct.pack("<f", float(v)))[0]
+
+
+# ---------------------------------------------------------------------------------------------------- loading
+@PIPELINES.register_module()
+class LoadImageFromFile:
+    def __init__(self, to_float32=False, color_type="color", file_client_args=None):
+        if to_float32:
+            _refuse("LoadImageFromFile(to_float32=True)")
+        if color_type != "color":
+            _refuse(f"LoadImageFromFile(color_type={color_type!r})")
+        if file_client_args not in (None, dict(backend="disk")):
+            _refuse(f"LoadImageFromFile(file_client_args={file_client_args})")
+
+    def plan(self, s, rnd, nprnd):
+        name = s["img_info"]["filename"]
+        s["filename"] = osp.join(s["img_prefix"], name) if s.get("img_prefix") is not None else name
+        s["ori_filename"] = name
+        s["img"] = decode_bgr(s["filename"])
+        s["img_shape"] = s["ori_shape"] = s["pad_shape"] = s["img"].shape
+        s["img_fields"] = ["img"]
+
+
+@PIPELINES.register_module()
+class LoadAnnotations:
+    def __init__(self, with_bbox=True, with_label=True, with_mask=False, with_seg=False, with_bop_mask=False, poly2mask=True,
+                 file_client_args=None):
+        if with_mask or with_seg:
+            _refuse("LoadAnnotations(with_mask / with_seg)")
+        self.with_bbox, self.with_label, self.with_bop_mask = with_bbox, with_label, with_bop_mask
+
+    def plan(self, s, rnd, nprnd):
+        ann = s["ann_info"]
+        if self.with_bbox:
+            s["gt_bboxes"] = np.asarray(ann["bboxes"], np.float32).reshape(-1, 4).copy()
+            if ann.get("bboxes_ignore") is not None:
+                s["gt_bboxes_ignore"] = np.asarray(ann["bboxes_ignore"], np.float32).reshape(-1, 4).copy()
+                s["bbox_fields"].append("gt_bboxes_ignore")
+            s["bbox_fields"].append("gt_bboxes")
+        if self.with_label:
+            s["gt_labels"] = np.asarray(ann["labels"], np.int64).copy()
+        if self.with_bop_mask:
+            h, w = s["img_info"]["height"], s["img_info"]["width"]
+            masks = [decode_unchanged(osp.join(s["seg_prefix"], p)) for p in ann["masks"]]
+            for m in masks:
+                if m.shape != (h, w):
+                    raise ValueError(f"mask of shape {m.shape} for an image of {h} x {w}")
+            s["gt_masks"] = np.stack(masks) if masks else np.zeros((0, h, w), np.uint8)
+            s["mask_fields"].append("gt_masks")
+
+
+# ---------------------------------------------------------------------------------------------------- geometry
+@PIPELINES.register_module()
+class Resize:
+    def __init__(self, img_scale=None, multiscale_mode="range", ratio_range=None, keep_ratio=True, bbox_clip_border=True,
+                 backend="cv2", override=False):
+        scales = None if img_scale is None else (img_scale if isinstance(img_scale, list) else [img_scale])
+        if scales is not None and len(scales) != 1:
+            _refuse("Resize with several img_scale values")
+        if ratio_range is not None or override or backend != "cv2":
+            _refuse("Resize(ratio_range / override / backend)")
+        self.img_scale = None if scales is None else tuple(scales[0])
+        self.keep_ratio, self.bbox_clip_border = keep_ratio, bbox_clip_border
+
+    def plan(self, s, rnd, nprnd):
+        if "scale" not in s:
+            if self.img_scale is None:
+                raise KeyError("Resize: no img_scale given and no 'scale' in the results")
+            s["scale"], s["scale_idx"] = self.img_scale, 0
+        h, w = s["img"].shape[:2]
+        if self.keep_ratio:
+            nw, nh = rescale_size((w, h), s["scale"])
+        else:
+            nw, nh = int(s["scale"][0]), int(s["scale"][1])
+        s["resize_hw"] = (nh, nw)
+        sf = np.array([nw / w, nh / h, nw / w, nh / h], dtype=np.float32)
+        s["img_shape"] = s["pad_shape"] = (nh, nw, 3)
+        s["scale_factor"], s["keep_ratio"] = sf, self.keep_ratio
+        for key in s.get("bbox_fields", []):
+            b = s[key] * sf
+            if self.bbox_clip_border:
+                b[:, 0::2] = np.clip(b[:, 0::2], 0, nw)
+                b[:, 1::2] = np.clip(b[:, 1::2], 0, nh)
+            s[key] = b
+
+
+@PIPELINES.register_module()
+class RandomFlip:
+    def __init__(self, flip_ratio=None, direction="horizontal"):
+        if direction != "horizontal" or isinstance(flip_ratio, list):
+            _refuse(f"RandomFlip(direction={direction!r}, list flip_ratio)")
+        if flip_ratio is not None:
+            assert 0 <= flip_ratio <= 1
+        self.flip_ratio, self.direction = flip_ratio, direction
+
+    def plan(self, s, rnd, nprnd):
+        if "flip" not in s:
+            if self.flip_ratio is None:
+                raise TypeError("RandomFlip(flip_ratio=None) needs 'flip' in the results (MultiScaleFlipAug sets it)")
+            cur = nprnd.choice([self.direction, None], p=[self.flip_ratio, 1 - self.flip_ratio])
+            s["flip"] = cur is not None
+        if "flip_direction" not in s:
+            s["flip_direction"] = cur
+        if s["flip"]:
+            w = s["img_shape"][1]
+            for key in s.get("bbox_fields", []):
+                b = s[key].copy()
+                b[..., 0::4] = w - s[key][..., 2::4]
+                b[..., 2::4] = w - s[key][..., 0::4]
+                s[key] = b
+
+
+@PIPELINES.register_module()
+class Normalize:
+    def __init__(self, mean, std, to_rgb=True):
+        self.mean, self.std, self.to_rgb = np.array(mean, np.float32), np.array(std, np.float32), to_rgb
+
+    def plan(self, s, rnd, nprnd):
+        s["img_norm_cfg"] = dict(mean=self.mean, std=self.std, to_rgb=self.to_rgb)
+
+
+@PIPELINES.register_module()
+class Pad:
+    def __init__(self, size=None, size_divisor=None, pad_val=0):
+        if size is not None or size_divisor is None or pad_val != 0:
+            _refuse("Pad(size= / pad_val != 0)")
+        self.size_divisor = int(size_divisor)
+
+    def plan(self, s, rnd, nprnd):
+        h, w = s["img_shape"][:2]
+        d = self.size_divisor
+        s["pad_shape"] = (int(math.ceil(h / d)) * d, int(math.ceil(w / d)) * d, 3)
+        s["pad_fixed_size"], s["pad_size_divisor"] = None, d
+
+
+# ---------------------------------------------------------------------------------------------------- photometric
+@PIPELINES.register_module()
+class RandomBackground:
+    def __init__(self, background_dir, prob=0.8, file_client_args=None, flag="color"):
+        if flag != "color":
+            _refuse(f"RandomBackground(flag={flag!r})")
+        # sorted: the reference's glob order depends on the file system
+        self.background_images = sorted(glob.glob(osp.join(background_dir, "*.jpg")) + glob.glob(osp.join(background_dir, "*.png")))
+        if not self.background_images:
+            raise RuntimeError(f"No background images found in {background_dir}")
+        self.background_dir, self.prob = background_dir, prob
+
+    def plan(self, s, rnd, nprnd):
+        if rnd.random() > self.prob:
+            return
+        s["background"] = decode_bgr(rnd.choice(self.background_images))
+
+
+class _PillowStage:
+    key = None
+
+    def __init__(self, p, factor_interval):
+        self.p, self.factor_interval = p, tuple(factor_interval)
+
+    def draw(self, s, rnd):
+        if rnd.random() <= self.p:
+            s[self.key] = rnd.uniform(*self.factor_interval)
+
+
+@PIPELINES.register_module()
+class PillowSharpness(_PillowStage):
+    key = "aug_sharpness"
+
+    def __init__(self, p=0.3, factor_interval=(0., 50.)):
+        super().__init__(p, factor_interval)
+
+
+@PIPELINES.register_module()
+class PillowContrast(_PillowStage):
+    key = "aug_contrast"
+
+    def __init__(self, p=0.3, factor_interval=(0.2, 50.)):
+        super().__init__(p, factor_interval)
+
+
+@PIPELINES.register_module()
+class PillowBrightness(_PillowStage):
+    key = "aug_brightness"
+
+    def __init__(self, p=0.5, factor_interval=(0.1, 6.0)):
+        super().__init__(p, factor_interval)
+
+
+@PIPELINES.register_module()
+class PillowColor(_PillowStage):
+    key = "aug_color"
+
+    def __init__(self, p=0.3, factor_interval=(0.0, 20.0)):
+        super().__init__(p, factor_interval)
+
+
+@PIPELINES.register_module()
+class PillowBlur(_PillowStage):
+    """GaussianBlur(k), k = random.randint(*factor_interval); `p` is ignored, as in the reference"""
+    key = "aug_blur"
+
+    def __init__(self, p=0.4, factor_interval=(1, 3)):
+        super().__init__(p, factor_interval)
+
+    def draw(self, s, rnd):
+        s[self.key] = rnd.randint(*self.factor_interval)
+
+
+@PIPELINES.register_module()
+class CosyPoseAug:
+    def __init__(self, p=0.8, pipelines=()):
+        self.p = p
+        self.pipelines = [build_from_cfg(c, PIPELINES) if isinstance(c, dict) else c for c in pipelines]
+        names = [type(t).__name__ for t in self.pipelines]
+        pos = [(_COSY_ORDER.index(n) if n in _COSY_ORDER else -1) for n in names]
+        if -1 in pos or pos != sorted(set(pos)):
+            _refuse(f"CosyPoseAug stages {names} (the device chain runs a subsequence of {_COSY_ORDER}, each at most once)")
+
+    def plan(self, s, rnd, nprnd):
+        if rnd.random() > self.p:
+            return
+        for t in self.pipelines:
+            t.draw(s, rnd)
+
+
+# ---------------------------------------------------------------------------------------------------- formatting
+@PIPELINES.register_module()
+class DefaultFormatBundle:
+    def plan(self, s, rnd, nprnd):
+        pass
+
+
+@PIPELINES.register_module()
+class ImageToTensor:
+    def __init__(self, keys):
+        self.keys = list(keys)
+
+    def plan(self, s, rnd, nprnd):
+        pass
+
+
+@PIPELINES.register_module()
+class Collect:
+    def __init__(self, keys, meta_keys=DEFAULT_META_KEYS):
+        self.keys, self.meta_keys = list(keys), tuple(meta_keys)
+
+    def plan(self, s, rnd, nprnd):
+        s["_collect"] = self
+
+
+@PIPELINES.register_module()
+class MultiScaleFlipAug:
+    """one view only: a single img_scale with flip=False (test-time augmentation with several views is refused, like
+    forward_test)"""
+
+    def __init__(self, transforms, img_scale=None, scale_factor=None, flip=False, flip_direction="horizontal"):
+        scales = img_scale if isinstance(img_scale, list) else [img_scale]
+        if flip or scale_factor is not None or img_scale is None or len(scales) != 1:
+            _refuse("MultiScaleFlipAug with more than one view (flip=True / several scales / scale_factor)")
+        self.img_scale = tuple(scales[0])
+        self.transforms = [build_from_cfg(t, PIPELINES) if isinstance(t, dict) else t for t in transforms]
+
+    def plan(self, s, rnd, nprnd):
+        s.update(scale=self.img_scale, flip=False, flip_direction=None, _tta=True)
+        for t in self.transforms:
+            t.plan(s, rnd, nprnd)
+
+
+# ---------------------------------------------------------------------------------------------------- the batched device part
+def is_image_pipeline(transforms):
+    return any((t.get("type") if isinstance(t, dict) else type(t).__name__) == "LoadImageFromFile" for t in transforms or ())
+
+
+class ImagePipeline:
+    """A pipeline that starts from files: host planning per sample, one batched device pass per batch."""
+
+    def __init__(self, transforms):
+        self.transforms = [build_from_cfg(t, PIPELINES) if isinstance(t, dict) else t for t in transforms]
+        flat = []
+        for t in self.transforms:
+            flat += [t] + (list(t.transforms) if isinstance(t, MultiScaleFlipAug) else [])
+        names = [type(t).__name__ for t in flat]
+        pos = [(_ORDER.index(n) if n in _ORDER else -1) for n in names]
+        if -1 in pos or pos != sorted(set(pos)):
+            _refuse(f"pipeline {names} (an image pipeline runs a subsequence of {_ORDER}, each stage once)")
+        for need in ("LoadImageFromFile", "Normalize", "Collect"):
+            if need not in names:
+                _refuse(f"an image pipeline without {need}")
+        self.assigner = next((t for t in flat if isinstance(t, LabelAssignment)), None)
+        dm = next((t for t in flat if isinstance(t, GenerateDistanceMap)), None)
+        if dm is not None and not dm.with_gt_mask:
+            _refuse("GenerateDistanceMap(with_gt_mask=False) in an image pipeline")
+        if self.assigner is not None and dm is None:
+            raise ValueError("LabelAssignment needs GenerateDistanceMap before it")
+        self.tta = any(isinstance(t, MultiScaleFlipAug) for t in self.transforms)
+
+    def plan(self, results, rnd, nprnd):
+        """host part of one sample (thread-safe for distinct generators): decoding, boxes, random draws"""
+        s = dict(results)
+        for t in self.transforms:
+            if not isinstance(t, (GenerateDistanceMap, LabelAssignment)):     # (device-only: run() does them)
+                t.plan(s, rnd, nprnd)
+        s["_nprnd"] = nprnd
+        return s
+
+    def __call__(self, results):
+        """one sample on the global generators, like the reference"""
+        import random
+        return self.run([self.plan(results, random, np.random)])[0]
+
+    # --------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _dev():
+        return torch.device("cuda", torch.cuda.current_device())
+
+    def _resize_packed(self, arrays, dst_hw, dev):
+        """u8 HWC images of any sizes -> one packed device buffer of the dst sizes (one resize launch)"""
+        src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(dev)
+        sdesc, ddesc, so, do = [], [], 0, 0
+        for a, (h, w) in zip(arrays, dst_hw):
+            sdesc.append((so, a.shape[0], a.shape[1]))
+            ddesc.append((do, h, w))
+            so += a.shape[0] * a.shape[1]
+            do += h * w
+        dst = torch.empty(do * 3, dtype=torch.uint8, device=dev)
+        desc = torch.from_numpy(np.array(sdesc + ddesc, np.int32).reshape(-1, 3)).to(dev)
+        n = len(arrays)
+        K.resize_linear_u8(src, desc[:n], dst, desc[n:], n, max(h * w for h, w in dst_hw), 3)
+        return dst, [d[0] for d in ddesc]
+
+    def run(self, planned, collate=False):
+        """device part of a batch of planned samples; returns per-sample dicts, or one collated batch dict"""
+        dev = self._dev()
+        B = len(planned)
+        hw = [tuple(s.get("resize_hw", s["img"].shape[:2])) for s in planned]
+        for h, w in hw:
+            if h > K.AUG_MAX_W or w > K.AUG_MAX_W:
+                raise ValueError(f"image of {h} x {w}: the augmentation kernels take sides up to {K.AUG_MAX_W}")
+        img, offs = self._resize_packed([s["img"] for s in planned], hw, dev)
+        with_bg = [i for i, s in enumerate(planned) if "background" in s]
+        bg, bg_offs = (self._resize_packed([planned[i]["background"] for i in with_bg], [hw[i] for i in with_bg], dev)
+                       if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
+        bg_off = dict(zip(with_bg, bg_offs))
+        masks, flipped_masks = self._masks(planned, hw, dev)
+
+        P = np.zeros((B, K.AUG_PARAM_INTS), np.int32)
+        for i, s in enumerate(planned):
+            fl = 0
+            cfg = s["img_norm_cfg"]
+            if cfg["to_rgb"]:
+                fl |= F_TO_RGB
+            if s.get("flip"):
+                fl |= F_FLIP
+            P[i, 0], (P[i, 1], P[i, 2]) = offs[i], hw[i]
+            if i in bg_off:
+                fl |= F_MERGE
+                P[i, 4] = bg_off[i]
+                m = masks[i]
+                P[i, 5] = 0 if m is None else m.shape[0]
+                if m is not None and m.shape[0]:
+                    addr = m.data_ptr()
+                    P[i, 6], P[i, 7] = np.array([addr & 0xFFFFFFFF, addr >> 32], np.uint32).view(np.int32)
+            if "aug_blur" in s:
+                fl |= F_BLUR
+                r, ww, fw = blur_params(s["aug_blur"])
+                P[i, 8], P[i, 9], P[i, 10] = r, ww, fw
+            for key, flag, col in (("aug_sharpness", F_SHARP, 11), ("aug_contrast", F_CONTRAST, 12),
+                                   ("aug_brightness", F_BRIGHT, 13), ("aug_color", F_COLOR, 14)):
+                if key in s:
+                    fl |= flag
+                    P[i, col] = _f32_bits(s[key])
+            P[i, 3] = fl
+        cfg0 = planned[0]["img_norm_cfg"]
+        for s in planned[1:]:
+            c = s["img_norm_cfg"]
+            if not (np.array_equal(c["mean"], cfg0["mean"]) and np.array_equal(c["std"], cfg0["std"])):
+                raise ValueError("one batch, one Normalize")
+        params = torch.from_numpy(P).to(dev)
+        Hp = max(s["pad_shape"][0] for s in planned)
+        Wp = max(s["pad_shape"][1] for s in planned)
+        max_h, max_w = max(h for h, _ in hw), max(w for _, w in hw)
+        if any(s["pad_shape"][0] < h or s["pad_shape"][1] < w for s, (h, w) in zip(planned, hw)):
+            raise ValueError("pad_shape smaller than the image")
+        t1, t2 = torch.empty_like(img), torch.empty_like(img)
+        lsum = torch.empty(B, dtype=torch.int64, device=dev)
+        out = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=dev)
+        mean = cfg0["mean"].astype(np.float64).astype(np.float32)
+        stdinv = (1.0 / cfg0["std"].astype(np.float64)).astype(np.float32)
+        K.augment_merge_hblur(img, bg, params, t1, B, max_h, max_w)
+        K.augment_vblur(t1, params, t2, B, max_h, max_w)
+        K.augment_sharp(t2, params, t1, lsum, B, max_h * max_w)
+        K.augment_finish(t1, lsum, params, out, B, Hp, Wp, mean, stdinv)
+
+        p2g = pw = None
+        if self.assigner is not None:
+            p2g, pw = [None] * B, [None] * B
+            for shape in sorted(set(hw)):
+                idx = [i for i in range(B) if hw[i] == shape]
+                a, b = self.assigner.assign_batch([planned[i]["gt_bboxes"] for i in idx], [flipped_masks[i] for i in idx], shape,
+                                                  rngs=[planned[i]["_nprnd"] for i in idx], device=dev)
+                for j, i in enumerate(idx):
+                    p2g[i], pw[i] = a[j], b[j]
+        return self._collect(planned, out, p2g, pw, collate)
+
+    def _masks(self, planned, hw, dev):
+        """normalised (mask / max), nearest-resized instance masks per sample (for the merge) and the same after the
+        sample's flip (for the assigner): one normalise + resize pass per group of equal sizes, one flip pass per group"""
+        masks, flipped = [None] * len(planned), [None] * len(planned)
+        groups = {}
+        for i, s in enumerate(planned):
+            if "gt_masks" in s:
+                groups.setdefault((s["gt_masks"].shape[1:], hw[i]), []).append(i)
+        for (src_hw, dst_hw), idx in groups.items():
+            counts = [planned[i]["gt_masks"].shape[0] for i in idx]
+            if not sum(counts):
+                for i in idx:
+                    masks[i] = flipped[i] = torch.zeros(0, *dst_hw, dtype=torch.uint8, device=dev)
+                continue
+            src = torch.from_numpy(np.concatenate([planned[i]["gt_masks"] for i in idx])).to(dev)
+            res = K.mask_transform(src, resized_hw=dst_hw, normalize=True)
+            fl = K.mask_transform(res, flip="horizontal") if any(planned[i].get("flip") for i in idx) else None
+            o = 0
+            for i, c in zip(idx, counts):
+                masks[i] = res[o:o + c]
+                flipped[i] = fl[o:o + c] if planned[i].get("flip") else masks[i]
+                o += c
+        return masks, flipped
+
+    def _collect(self, planned, out, p2g, pw, collate):
+        samples = []
+        for i, s in enumerate(planned):
+            col = s["_collect"]
+            h, w = s["pad_shape"][:2]
+            d = {}
+            for key in col.keys:
+                if key == "img":
+                    d["img"] = out[i, :, :h, :w]
+                elif key == "points_to_gt_index":
+                    d[key] = p2g[i]
+                elif key == "points_weight":
+                    d[key] = pw[i]
+                else:
+                    d[key] = torch.from_numpy(np.asarray(s[key]))
+            d["img_metas"] = {k: s[k] for k in col.meta_keys if k in s}
+            if s.get("_tta"):
+                d = {k: [v] for k, v in d.items()}
+            samples.append(d)
+        if not collate:
+            return samples
+        keys = planned[0]["_collect"].keys
+        if self.tta:
+            return dict(img=[out], img_metas=[[d["img_metas"][0] for d in samples]])
+        batch = {k: [d[k] for d in samples] for k in keys if k != "img"}
+        batch["img"] = out
+        batch["img_metas"] = [d["img_metas"] for d in samples]
+        return batch

@@ -1494,3 +1494,25 @@ def gaussian_blur9_u8(src, desc, dst, tmp, n, max_px):
 
 def sobel_edge(src, desc, edge, gray_ws, max_ws, n, max_px):
     _lib.call("radet_sobel_edge", _ptr(src), _ptr(desc), _ptr(edge), _ptr(gray_ws), _ptr(max_ws), n, max_px, _stream())
+
+
+# ---------------------------------------------------------------------- BOP training-image augmentation (csrc/augment.hip)
+AUG_PARAM_INTS = 16
+AUG_MAX_W = 8192
+
+
+def augment_merge_hblur(src, bg, params, dst, n, max_h, max_w):
+    _lib.call("radet_augment_merge_hblur", _ptr(src), _ptr(bg), _ptr(params), _ptr(dst), n, max_h, max_w, _stream())
+
+
+def augment_vblur(src, params, dst, n, max_h, max_w):
+    _lib.call("radet_augment_vblur", _ptr(src), _ptr(params), _ptr(dst), n, max_h, max_w, _stream())
+
+
+def augment_sharp(src, params, dst, lsum, n, max_px):
+    _lib.call("radet_augment_sharp", _ptr(src), _ptr(params), _ptr(dst), _ptr(lsum), n, max_px, _stream())
+
+
+def augment_finish(src, lsum, params, out, n, Hp, Wp, mean, stdinv):
+    _lib.call("radet_augment_finish", _ptr(src), _ptr(lsum), _ptr(params), _ptr(out), n, Hp, Wp, *[float(v) for v in mean],
+              *[float(v) for v in stdinv], _stream())
