@@ -468,6 +468,18 @@ int radet_augment_sharp(const uint8_t* src, const int* params, uint8_t* dst, uns
 int radet_augment_finish(const uint8_t* src, const unsigned long long* lsum, const int* params, float* out, int nimg, int Hp,
                          int Wp, float m0, float m1, float m2, float s0, float s1, float s2, void* stream);
 
+/* ---- the mixpbr stages RandomHSV / RandomNoise / RandomSmooth (csrc/augment.hip) on the same packed u8 HWC BGR layout,
+ *      between radet_augment_merge_hblur and radet_augment_finish.  params2 (device) = nimg rows of AUG2_PARAM_INTS ints:
+ *      {pixel offset, h, w, flags, f32 bits of the h / s / v factors, lt (bit 0 / 1 / 2: that factor is < 1, no clip),
+ *       f64 bits of the noise sigma (lo, hi), Philox key word 0 (lo, hi), key word 1 (lo, hi), box size k (1, 3, 5, 7), 0};
+ *      flags: 1 HSV, 2 noise, 4 box.  hsv_noise: cv2 BGR2HSV, scale, HSV2BGR, then + N(0, sigma) * 255 from Box-Muller on
+ *      Philox-4x64-10 (key, counter = block + 1); box: cv2.blur k x k, reflect-101.  src / dst 4-byte aligned; nbytes =
+ *      the size of box's src buffer (its loads stay inside it); max_px = the largest h * w. */
+#define AUG2_PARAM_INTS 16
+int radet_augment_hsv_noise(const uint8_t* src, const int* params2, uint8_t* dst, int nimg, int max_px, void* stream);
+int radet_augment_box(const uint8_t* src, const int* params2, uint8_t* dst, size_t nbytes, int nimg, int max_h, int max_w,
+                      void* stream);
+
 /* ---- stand-alone box / loss operators behind the registered classes (used on their own; inside the detector the same
  *      arithmetic runs fused in radet_head_loss / radet_decode_candidates) ------------------------------------------ */
 /* bbox_overlaps / BboxOverlaps2D (radet/core/bbox/iou_calculators/iou2d_calculator.py:43-159): boxes [batch, M, 4] and

@@ -25,7 +25,41 @@ osp = os.path
 DATASETS = Registry("dataset")
 
 
+def _concat_dataset(cfg, default_args=None):
+    """a dataset config whose ann_file is a list: one dataset per file (img_prefix / seg_prefix / proposal_file lists pair
+    up with it), concatenated"""
+    from .dataset_wrappers import ConcatDataset
+    datasets = []
+    for i, ann_file in enumerate(cfg["ann_file"]):
+        c = {k: v for k, v in cfg.items() if k != "separate_eval"}
+        c["ann_file"] = ann_file
+        for key in ("img_prefix", "seg_prefix", "proposal_file"):
+            if isinstance(cfg.get(key), (list, tuple)):
+                c[key] = cfg[key][i]
+        datasets.append(build_dataset(c, default_args))
+    return ConcatDataset(datasets, cfg.get("separate_eval", True))
+
+
 def build_dataset(cfg, default_args=None):
+    """the reference's builder (datasets/builder.py): a list, ConcatDataset, RepeatDataset, MixDataset (every key that
+    contains 'dataset' is a sub-dataset config; its 'ratio', default 1, is the repeat count), a list-valued ann_file, or
+    one registered dataset.  The caller's config is left as it was."""
+    from .dataset_wrappers import ConcatDataset, MixDataset, RepeatDataset
+    if isinstance(cfg, (list, tuple)):
+        return ConcatDataset([build_dataset(c, default_args) for c in cfg])
+    kind = cfg.get("type")
+    if kind == "ConcatDataset":
+        return ConcatDataset([build_dataset(c, default_args) for c in cfg["datasets"]], cfg.get("separate_eval", True))
+    if kind == "RepeatDataset":
+        return RepeatDataset(build_dataset(cfg["dataset"], default_args), cfg["times"])
+    if kind == "MixDataset":
+        subs = [{k: v for k, v in cfg[key].items() if k != "ratio"} for key in cfg if "dataset" in key]
+        ratios = [cfg[key].get("ratio", 1) for key in cfg if "dataset" in key]
+        return MixDataset([build_dataset(c, default_args) for c in subs], ratios)
+    if kind == "ClassBalancedDataset":
+        raise NotImplementedError("ClassBalancedDataset is not used by the RADet configs and is not implemented")
+    if isinstance(cfg.get("ann_file"), (list, tuple)):
+        return _concat_dataset(cfg, default_args)
     return build_from_cfg(cfg, DATASETS, default_args)
 
 

@@ -6,8 +6,8 @@ arithmetic (NumPy, mmdet 2.x Resize / RandomFlip.bbox_flip) and every random dra
 sample's own generators (`rnd`: a random.Random or the `random` module, `nprnd`: a RandomState or `np.random`).  Planning
 touches no device, so the loader runs it on host threads.  `ImagePipeline.run(planned)` then does the device part of a
 whole batch on the calling thread and stream: the resize of images and backgrounds (radet_resize_linear_u8), mask
-normalisation / resize / flip (radet_mask_transform), the four augmentation launches of csrc/augment.hip and the label
-assigner -- a fixed number of launches whatever the batch size.  A single sample (`BOPDataset.__getitem__`) is a batch
+normalisation / resize / flip (radet_mask_transform), the four augmentation launches of csrc/augment.hip (a mixpbr
+pipeline: merge, hsv_noise, box, finish) and the label assigner -- a fixed number of launches whatever the batch size.  A single sample (`BOPDataset.__getitem__`) is a batch
 of one.  Options the RADet configs do not use raise NotImplementedError."""
 import glob
 import math
@@ -26,11 +26,15 @@ osp = os.path
 DEFAULT_META_KEYS = ("filename", "ori_filename", "ori_shape", "img_shape", "pad_shape", "scale_factor", "flip",
                      "flip_direction", "img_norm_cfg")
 # stage order of the device part (a pipeline lists a subsequence of it; MultiScaleFlipAug's transforms sit in its place)
-_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Resize", "RandomBackground", "CosyPoseAug", "RandomFlip",
-          "GenerateDistanceMap", "LabelAssignment", "Normalize", "Pad", "DefaultFormatBundle", "ImageToTensor", "Collect")
+_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Resize", "RandomBackground", "CosyPoseAug", "RandomHSV",
+          "RandomNoise", "RandomSmooth", "RandomFlip", "GenerateDistanceMap", "LabelAssignment", "Normalize", "Pad",
+          "DefaultFormatBundle", "ImageToTensor", "Collect")
+_MIX = ("RandomHSV", "RandomNoise", "RandomSmooth")          # the mixpbr stages: aug_hsv_noise + aug_box
 _COSY_ORDER = ("PillowBlur", "PillowSharpness", "PillowContrast", "PillowBrightness", "PillowColor")
 # flags of a params row (include/radet_hip.h)
 F_MERGE, F_BLUR, F_SHARP, F_CONTRAST, F_BRIGHT, F_COLOR, F_FLIP, F_TO_RGB = 1, 2, 4, 8, 16, 32, 64, 128
+# flags of a params2 row (the mixpbr stages)
+F2_HSV, F2_NOISE, F2_BOX = 1, 2, 4
 
 
 def _refuse(what):
@@ -292,6 +296,56 @@ class CosyPoseAug:
             t.draw(s, rnd)
 
 
+@PIPELINES.register_module()
+class RandomHSV:
+    """cv2 BGR -> HSV, each channel times uniform(-1, 1) * ratio + 1 (clipped only for factors >= 1), HSV -> BGR
+    (aug_hsv_noise); factors stored in s["aug_hsv"]"""
+
+    def __init__(self, h_ratio, s_ratio, v_ratio, prob=1.0):
+        if not all(0 <= r <= 1 for r in (h_ratio, s_ratio, v_ratio)):
+            _refuse("RandomHSV with a ratio outside [0, 1] (negative factors)")
+        self.h_ratio, self.s_ratio, self.v_ratio, self.prob = h_ratio, s_ratio, v_ratio, prob
+
+    def plan(self, s, rnd, nprnd):
+        if rnd.random() > self.prob:
+            return
+        s["aug_hsv"] = tuple(rnd.uniform(-1, 1) * ratio + 1 for ratio in (self.h_ratio, self.s_ratio, self.v_ratio))
+
+
+@PIPELINES.register_module()
+class RandomNoise:
+    """img + N(0, sigma) * 255, sigma = uniform(0, noise_ratio), clipped and truncated (aug_hsv_noise).  Where the
+    reference draws np.random.normal, the sample's RandomState draws a Philox key instead (two uint64), which keeps every
+    later draw at its place in the stream; the device makes the normals from Philox-4x64-10 under that key (DESIGN.md
+    sections 2 and 9: the reference's distribution, not its stream).  s["aug_noise"] = (sigma, key)"""
+
+    def __init__(self, noise_ratio, prob=1.0):
+        self.noise_ratio, self.prob = noise_ratio, prob
+
+    def plan(self, s, rnd, nprnd):
+        if rnd.random() > self.prob:
+            return
+        sigma = rnd.uniform(0, self.noise_ratio)
+        s["aug_noise"] = (sigma, nprnd.randint(0, 2 ** 64, size=2, dtype=np.uint64))
+
+
+@PIPELINES.register_module()
+class RandomSmooth:
+    """cv2.blur(img, (k, k)), k = random.choice([1, 3, ..., max_kernel_size]) (aug_box); s["aug_smooth"] = k"""
+
+    def __init__(self, max_kernel_size=7, prob=1.0):
+        self.max_kernel_size = max_kernel_size
+        self.kernel_sizes = [i * 2 + 1 for i in range(self.max_kernel_size // 2 + 1)]
+        if max(self.kernel_sizes) > 7:
+            _refuse(f"RandomSmooth(max_kernel_size={max_kernel_size}) (the box kernel takes k up to 7)")
+        self.prob = prob
+
+    def plan(self, s, rnd, nprnd):
+        if rnd.random() > self.prob:
+            return
+        s["aug_smooth"] = rnd.choice(self.kernel_sizes)
+
+
 # ---------------------------------------------------------------------------------------------------- formatting
 @PIPELINES.register_module()
 class DefaultFormatBundle:
@@ -344,6 +398,7 @@ class ImagePipeline:
     """A pipeline that starts from files: host planning per sample, one batched device pass per batch."""
 
     def __init__(self, transforms):
+        self.cfg = list(transforms)                       # (wrapped datasets share one pipeline when their configs are equal)
         self.transforms = [build_from_cfg(t, PIPELINES) if isinstance(t, dict) else t for t in transforms]
         flat = []
         for t in self.transforms:
@@ -352,6 +407,9 @@ class ImagePipeline:
         pos = [(_ORDER.index(n) if n in _ORDER else -1) for n in names]
         if -1 in pos or pos != sorted(set(pos)):
             _refuse(f"pipeline {names} (an image pipeline runs a subsequence of {_ORDER}, each stage once)")
+        if "CosyPoseAug" in names and any(n in _MIX for n in names):
+            _refuse("CosyPoseAug together with RandomHSV / RandomNoise / RandomSmooth")
+        self.mix = any(n in _MIX for n in names)
         for need in ("LoadImageFromFile", "Normalize", "Collect"):
             if need not in names:
                 _refuse(f"an image pipeline without {need}")
@@ -382,15 +440,16 @@ class ImagePipeline:
     def _dev():
         return torch.device("cuda", torch.cuda.current_device())
 
-    def _resize_packed(self, arrays, dst_hw, dev):
-        """u8 HWC images of any sizes -> one packed device buffer of the dst sizes (one resize launch)"""
+    def _resize_packed(self, arrays, dst_hw, dev, align=1):
+        """u8 HWC images of any sizes -> one packed device buffer of the dst sizes (one resize launch); every image starts at
+        a multiple of `align` pixels"""
         src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(dev)
         sdesc, ddesc, so, do = [], [], 0, 0
         for a, (h, w) in zip(arrays, dst_hw):
             sdesc.append((so, a.shape[0], a.shape[1]))
             ddesc.append((do, h, w))
             so += a.shape[0] * a.shape[1]
-            do += h * w
+            do += -(-h * w // align) * align
         dst = torch.empty(do * 3, dtype=torch.uint8, device=dev)
         desc = torch.from_numpy(np.array(sdesc + ddesc, np.int32).reshape(-1, 3)).to(dev)
         n = len(arrays)
@@ -405,7 +464,8 @@ class ImagePipeline:
         for h, w in hw:
             if h > K.AUG_MAX_W or w > K.AUG_MAX_W:
                 raise ValueError(f"image of {h} x {w}: the augmentation kernels take sides up to {K.AUG_MAX_W}")
-        img, offs = self._resize_packed([s["img"] for s in planned], hw, dev)
+        # (mix pipelines: images start at multiples of 4 pixels, so the mix kernels' dword accesses are aligned)
+        img, offs = self._resize_packed([s["img"] for s in planned], hw, dev, align=4 if self.mix else 1)
         with_bg = [i for i, s in enumerate(planned) if "background" in s]
         bg, bg_offs = (self._resize_packed([planned[i]["background"] for i in with_bg], [hw[i] for i in with_bg], dev)
                        if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
@@ -455,10 +515,18 @@ class ImagePipeline:
         out = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=dev)
         mean = cfg0["mean"].astype(np.float64).astype(np.float32)
         stdinv = (1.0 / cfg0["std"].astype(np.float64)).astype(np.float32)
-        K.augment_merge_hblur(img, bg, params, t1, B, max_h, max_w)
-        K.augment_vblur(t1, params, t2, B, max_h, max_w)
-        K.augment_sharp(t2, params, t1, lsum, B, max_h * max_w)
-        K.augment_finish(t1, lsum, params, out, B, Hp, Wp, mean, stdinv)
+        if self.mix:
+            # merge (no Pillow stages in a mix pipeline) -> HSV + noise -> box -> flip / BGR->RGB / Normalize / pad
+            params2 = torch.from_numpy(self._params2(planned, offs, hw)).to(dev)
+            K.augment_merge_hblur(img, bg, params, t1, B, max_h, max_w)
+            K.augment_hsv_noise(t1, params2, t2, B, max(h * w for h, w in hw))
+            K.augment_box(t2, params2, t1, B, max_h, max_w)
+            K.augment_finish(t1, lsum, params, out, B, Hp, Wp, mean, stdinv)
+        else:
+            K.augment_merge_hblur(img, bg, params, t1, B, max_h, max_w)
+            K.augment_vblur(t1, params, t2, B, max_h, max_w)
+            K.augment_sharp(t2, params, t1, lsum, B, max_h * max_w)
+            K.augment_finish(t1, lsum, params, out, B, Hp, Wp, mean, stdinv)
 
         p2g = pw = None
         if self.assigner is not None:
@@ -470,6 +538,29 @@ class ImagePipeline:
                 for j, i in enumerate(idx):
                     p2g[i], pw[i] = a[j], b[j]
         return self._collect(planned, out, p2g, pw, collate)
+
+    @staticmethod
+    def _params2(planned, offs, hw):
+        """the params2 rows of the mix stages (include/radet_hip.h, AUG2_PARAM_INTS)"""
+        P = np.zeros((len(planned), K.AUG2_PARAM_INTS), np.int32)
+        for i, s in enumerate(planned):
+            fl = 0
+            P[i, 0], (P[i, 1], P[i, 2]) = offs[i], hw[i]
+            if "aug_hsv" in s:
+                fl |= F2_HSV
+                a, b, c = s["aug_hsv"]
+                P[i, 4:7] = [_f32_bits(a), _f32_bits(b), _f32_bits(c)]
+                P[i, 7] = int(a < 1) | int(b < 1) << 1 | int(c < 1) << 2        # (the double factor, as the reference tests it)
+            if "aug_noise" in s:
+                fl |= F2_NOISE
+                sigma, key = s["aug_noise"]
+                P[i, 8:10] = np.array([sigma], np.float64).view(np.int32)
+                P[i, 10:14] = np.asarray(key, np.uint64).reshape(2).view(np.int32)
+            if "aug_smooth" in s:
+                fl |= F2_BOX
+                P[i, 14] = s["aug_smooth"]
+            P[i, 3] = fl
+        return P
 
     def _masks(self, planned, hw, dev):
         """normalised (mask / max), nearest-resized instance masks per sample (for the merge) and the same after the

@@ -1516,3 +1516,15 @@ def augment_sharp(src, params, dst, lsum, n, max_px):
 def augment_finish(src, lsum, params, out, n, Hp, Wp, mean, stdinv):
     _lib.call("radet_augment_finish", _ptr(src), _ptr(lsum), _ptr(params), _ptr(out), n, Hp, Wp, *[float(v) for v in mean],
               *[float(v) for v in stdinv], _stream())
+
+
+AUG2_PARAM_INTS = 16
+
+
+def augment_hsv_noise(src, params2, dst, n, max_px):
+    _lib.call("radet_augment_hsv_noise", _ptr(src), _ptr(params2), _ptr(dst), n, max_px, _stream())
+
+
+def augment_box(src, params2, dst, n, max_h, max_w):
+    _lib.call("radet_augment_box", _ptr(src), _ptr(params2), _ptr(dst), src.numel() * src.element_size(), n, max_h, max_w,
+              _stream())

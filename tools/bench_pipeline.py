@@ -4,6 +4,8 @@
                                                                    # (run it under `rocprofv3 --kernel-trace --stats`)
     python tools/bench_pipeline.py --part decode                   # host planning (decode + draws) per thread count
     python tools/bench_pipeline.py --part train [--steps 60]       # r50_ycbv_pbr fp32 bs 16: loader-fed vs one prebuilt batch
+`--pipeline mix` runs the mixpbr train pipeline instead (RandomHSV / RandomNoise / RandomSmooth in place of CosyPoseAug,
+the training set a MixDataset of the tree twice, ratios 2 and 1).
 Each part prints one JSON line (and writes it to --out if given)."""
 import argparse
 import json
@@ -20,25 +22,35 @@ import numpy as np  # noqa: E402
 from tools.synth_bop import pipelines, write_tree  # noqa: E402
 
 
-def dataset(root, n_frames, all_on=False):
+MIX_STAGES = [dict(type="RandomHSV", h_ratio=0.2, s_ratio=0.5, v_ratio=0.5, prob=1.0),
+              dict(type="RandomNoise", noise_ratio=0.1, prob=1.0),
+              dict(type="RandomSmooth", max_kernel_size=7, prob=1.0)]
+
+
+def dataset(root, n_frames, all_on=False, mix=False):
     from radet_amd.datasets import build_dataset
     tree = write_tree(root, n_frames=n_frames, seed=0)
     train, _ = pipelines(tree["background_dir"], bg_prob=1.0 if all_on else 0.3, cosy_p=1.0 if all_on else 0.8)
     if all_on:
         for st in train[4]["pipelines"]:
             st["p"] = 1.0
-    return build_dataset(dict(type="BOPDataset", ann_file=tree["ann_file"], img_prefix=tree["img_prefix"],
-                              seg_prefix=tree["seg_prefix"], pipeline=train))
+    sub = dict(type="BOPDataset", ann_file=tree["ann_file"], img_prefix=tree["img_prefix"], seg_prefix=tree["seg_prefix"])
+    if not mix:
+        return build_dataset(dict(sub, pipeline=train))
+    train = train[:4] + MIX_STAGES + train[5:]
+    return build_dataset(dict(type="MixDataset", dataset_0=dict(sub, pipeline=train, ratio=2),
+                              dataset_1=dict(sub, pipeline=train, ratio=1)))
 
 
 def part_kernels(args, root):
     import torch
     from radet_amd.datasets.loader import sample_generators
-    ds = dataset(root, 16, all_on=True)
+    ds = dataset(root, 16, all_on=True, mix=args.pipeline == "mix")
     planned = [ds.plan_sample(i, *sample_generators(0, 0, i)) for i in range(16)]
-    assert all("background" in s and "aug_color" in s for s in planned)
-    for s in planned:          # every stage on, blur at its widest
-        s["aug_blur"] = 3
+    key = "aug_smooth" if args.pipeline == "mix" else "aug_color"
+    assert all("background" in s and key in s for s in planned)
+    for s in planned:          # every stage on, blur / box at its widest
+        s["aug_smooth" if args.pipeline == "mix" else "aug_blur"] = 7 if args.pipeline == "mix" else 3
     pipe = ds.pipeline
     pipe.run(planned, collate=True)
     torch.cuda.synchronize()
@@ -52,13 +64,16 @@ def part_kernels(args, root):
     # read + write the image; finish reads the image, writes f32 x 3
     masks = sum(int(s["gt_masks"].shape[0]) for s in planned) * 480 * 640
     aug_bytes = (3 * px * 2 + masks + 3 * px) + 3 * px * 2 + 3 * px * 2 + (3 * px + 12 * px)
-    return dict(part="kernels", batch=16, iters=args.iters, host_ms_per_batch=dt * 1e3, aug_kernel_bytes=aug_bytes)
+    # (mix: hsv_noise and box each read + write the image in place of vblur and sharp: the same count; the two mix
+    # launches alone move 4 x 3 px bytes)
+    return dict(part="kernels", pipeline=args.pipeline, batch=16, iters=args.iters, host_ms_per_batch=dt * 1e3,
+                aug_kernel_bytes=aug_bytes, mix_kernel_bytes=4 * 3 * px if args.pipeline == "mix" else None)
 
 
 def part_decode(args, root):
     from concurrent.futures import ThreadPoolExecutor
     from radet_amd.datasets.loader import sample_generators
-    ds = dataset(root, 32)
+    ds = dataset(root, 32, mix=args.pipeline == "mix")
     out = {}
     for threads in (1, 2, 4, 8, 12, 16):
         with ThreadPoolExecutor(threads) as pool:
@@ -69,7 +84,7 @@ def part_decode(args, root):
                 list(pool.map(lambda i: ds.plan_sample(i, *sample_generators(0, rep, i)), range(len(ds))))
                 n += len(ds)
             out[threads] = n / (time.perf_counter() - t0)
-    return dict(part="decode", images_per_s_by_threads=out)
+    return dict(part="decode", pipeline=args.pipeline, images_per_s_by_threads=out)
 
 
 def part_train(args, root):
@@ -78,7 +93,7 @@ def part_train(args, root):
     from radet_amd.datasets import build_dataloader
     from radet_amd.models import build_detector
     from radet_amd.utils import Config
-    ds = dataset(root, 64)
+    ds = dataset(root, 64, mix=args.pipeline == "mix")
     cfg = Config.fromfile(os.path.join(ROOT, "configs", "bop", "r50_ycbv_pbr.py"))
     cfg.model["pretrained"] = None
     torch.manual_seed(0)
@@ -117,7 +132,7 @@ def part_train(args, root):
             res[name].append(16 * args.steps / (time.perf_counter() - t0))
     loader.close()
     med = {k: float(np.median(v)) for k, v in res.items()}
-    return dict(part="train", batch=16, steps=args.steps, rounds=args.rounds, workers=loader.workers,
+    return dict(part="train", pipeline=args.pipeline, batch=16, steps=args.steps, rounds=args.rounds, workers=loader.workers,
                 images_per_s=res, median=med, loader_over_prebuilt=med["loader"] / med["prebuilt"],
                 replays=(rt.tape_stats() or {}).get("replays"))
 
@@ -125,6 +140,7 @@ def part_train(args, root):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", choices=("kernels", "decode", "train"), required=True)
+    ap.add_argument("--pipeline", choices=("pbr", "mix"), default="pbr")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=5)
