@@ -61,7 +61,7 @@ typedef struct RadetConvDesc {
 /* ---- amax slots (round 5, "fp16 hi / lo arithmetic").  The default fp32 conv arithmetic forms fp32-accurate products
  * from TWO fp16 numbers per operand element: t = x 2^e, hi = fp16(t), lo = fp16((t - hi) 2^11), and
  * x x' = 2^-(e + e') (hi hi' + 2^-11 (hi lo' + lo hi')) -- three v_mfma_f32_32x32x16_f16 per K = 16 step instead of the six
- * bf16 plane products of 0x1000000 (the dropped lo lo' term is <= 2^-24 relative; x = 2^-e (hi + 2^-11 lo) to 2^-23
+ * bf16 plane products of RADET_TILE_X3 (the dropped lo lo' term is <= 2^-24 relative; x = 2^-e (hi + 2^-11 lo) to 2^-23
  * relative for every element within 2^-27 of the tensor's largest).  fp16 has 5 exponent bits, so every operand tensor is
  * scaled by an exact power of two 2^e that puts its largest magnitude into [2^14, 2^15).  e comes from the tensor's "amax
  * slot": RADET_AMAX_WORDS = 64 32-bit words, 128 bytes apart (radet_amax_slot_words() = 2048 words = 8 KiB per slot, the
@@ -86,7 +86,7 @@ typedef struct RadetScales {
      * before the launch starts, unlike y's own largest magnitude -- which is stored to yq_amax.  x_true_amax: the slot x's
      * producer RAISED (for a plane-pair x: not the bound its pairs were scaled with, or the bounds of consecutive layers would
      * multiply); w_l1: RadetConvDesc.w_l1; bias_amax / addend_amax: NULL when the launch has no bias / addend.  The next
-     * conv reads yq as its x operand (+0x2000000 | 0x8000000) and needs no operand split in its K loop. */
+     * conv reads yq as its x operand (RADET_TILE_P3 | RADET_TILE_H2) and needs no operand split in its K loop. */
     void* yq;
     void* yq_amax;
     const void* x_true_amax;
@@ -105,34 +105,48 @@ int radet_build_gather_table(int* table, int B, int KH, int KW, int so, int sr, 
 /* Implicit-GEMM conv on MFMA: y[m,n] = sum_{tap,c} x[table[tap][m], c] * w[n][tap][c].  Forward: w = wf.
  * dgrad: x = dy, w = wft (Cin/Cout swapped, dgrad table).
  * Epilogue: y = acc + bias[n] (+ addend[m,n]) ; relu ; then y = mask[m,n] > 0 ? y : 0.
- * tile_override: 0 = heuristic, 1..4 = tile config; +0x100 = tagged kernel symbol (profiling); +0x200 = K step 32;
- * +0x800 = bf16 storage (x, w, addend, mask are bf16 tensors, Cin % 32 == 0; y bf16, or fp32 with +0x10000);
- * +0x400 = bf16 math mode (operands rounded RNE to bf16 between LDS and the matrix core, fp32 accumulate, fp32
- * tensors in HBM -- the arithmetic of mmcv's fp16 wrapper, `apis/train.py:113-117`, in bf16); bits 12-15 force
- * a split-K factor; +0x20000 = 3 LDS stages (fp32, launches that run alone on the device); + (w << 20), w = 1..7 =
- * stream-K schedule with w persistent workgroups per CU (fp32, untagged symbol, tiles 2-4): the K stages of the whole
- * launch are shared evenly, tiles cut by a share boundary are reduced inside the launch in K order (deterministic);
- * plain launch when there is less than one K stage per workgroup; +0x1000000 = fp32 tensors, products formed on the
- * bf16 matrix cores from an exact three-way bf16 split of every fp32 operand (x = hi + mid + lo, 8 significand bits
- * each; 6 of the 9 plane products -- everything above 2^-24 relative -- through v_mfma_f32_32x32x16_bf16, fp32
- * accumulate; Cin % 32 == 0, otherwise the native fp32 MFMA is used), with two more tiles: 7 / 8 = 64 x 64 tiles whose four
- * waves divide the K step (four 16-channel k-groups of a 64-channel stage, Cin % 64 == 0 / two k-groups x two column halves of
- * a 32-channel stage) and add their partial tiles through LDS -- every operand element is split once per workgroup
- * (-1 for these tiles without 0x1000000, with stream-K bits, or when Cin does not divide); +0x2000000 = the same arithmetic with operands
- * that ARRIVE as bf16 plane triples (x rows [3][Cin] bf16, w [Cout][taps][3][Cin] bf16 -- "planes" below; y, addend, mask,
- * bias fp32; Cin % 32 == 0): no operand split in the K loop; tiles 1..4 as above plus 5 = 128 x 128 and 6 = 256 x 128 with
- * 8 waves; K step 32 channels, or 16 with +0x4000000; +0x20000 = one more LDS stage.  splitk_ws (may be NULL): workspace of splitk_ws_floats floats whose first 16384 words are arrival
- * tickets that must be ZERO before the first launch (every launch leaves them zero); when given, launches with too few
- * tiles for 256 CUs split the K loop (<= 8 ways, or only the left-over tiles of the last round) and the workgroup that
- * arrives last at a tile sums the partial tiles in split order and applies the epilogue -- one launch, deterministic.
- * One workspace per stream: concurrent launches must not share it. */
+ * tile_override: a packed word, RADET_TILE_* below.  splitk_ws (may be NULL): workspace of splitk_ws_floats floats whose
+ * first 16384 words are arrival tickets that must be ZERO before the first launch (every launch leaves them zero); when
+ * given, launches with too few tiles for 256 CUs split the K loop (<= 8 ways, or only the left-over tiles of the last
+ * round) and the workgroup that arrives last at a tile sums the partial tiles in split order and applies the epilogue --
+ * one launch, deterministic.  One workspace per stream: concurrent launches must not share it. */
+enum {
+    RADET_TILE_ID_MASK = 0xFF,         /* block tile: 0 = launcher heuristic, 1 = 128 x 128, 2 = 128 x 64, 3 = 64 x 64, 4 = 128 x 32
+                                          (4 waves); 5 = 128 x 128, 6 = 256 x 128 (8 waves, P3 only); 7 / 8 = 64 x 64 whose four
+                                          waves divide a 64- / 32-channel K step and add their partial tiles through LDS */
+    RADET_TILE_SYMBOL = 0x100,         /* tagged kernel symbol (profiling) */
+    RADET_TILE_BK32 = 0x200,           /* K step 32 instead of 16 channels (ignored with P3) */
+    RADET_TILE_MATH_BF16 = 0x400,      /* bf16 math: fp32 tensors, operands rounded RNE to bf16 between LDS and the matrix core */
+    RADET_TILE_STORE_BF16 = 0x800,     /* bf16 storage: x, w, addend, mask and y are bf16 tensors */
+    RADET_TILE_SPLITK = 0x1000,        /* * n (bits 12-15): forced split-K factor n = 1..15 (0 = the launcher's choice) */
+    RADET_TILE_SPLITK_MASK = 0xF000,
+    RADET_TILE_OUT_F32 = 0x10000,      /* with STORE_BF16: y is fp32 */
+    RADET_TILE_STAGES3 = 0x20000,      /* 3 LDS stages (fp32 tensors, launches that run alone on the device) */
+    RADET_TILE_STAGES4 = 0x40000,      /* 4 LDS stages (tile 8 with H2) */
+    RADET_TILE_ROWPAIRS = 0x80000,     /* with P3 | H2, tiles 5 / 6: a tile load fetches both planes of a row (128 bytes) */
+    RADET_TILE_STREAMK = 0x100000,     /* * w (bits 20-22): stream-K schedule with w = 1..7 persistent workgroups per CU */
+    RADET_TILE_STREAMK_MASK = 0x700000,
+    RADET_TILE_X3 = 0x1000000,         /* fp32 tensors, products from three bf16 planes per operand, split in registers */
+    RADET_TILE_P3 = 0x2000000,         /* x and w ARRIVE as planes (bf16 triples; fp16 pairs with H2); y, addend, mask, bias fp32 */
+    RADET_TILE_H2 = 0x8000000,         /* with X3 or P3: fp16 hi / lo arithmetic (RadetScales; the _s entry points) */
+    RADET_TILE_MASKQ = 0x10000000      /* `mask` is an fp16 plane-pair tensor (rows [2][Cout]; fp32 tensors, Cout % 32 == 0) */
+};
+/* MATH_BF16 is the arithmetic of mmcv's fp16 wrapper, `apis/train.py:113-117`, in bf16.  STORE_BF16 and P3 need
+ * Cin % 32 == 0 (-1 otherwise).  X3: x = hi + mid + lo exactly, 8 significand bits each; 6 of the 9 plane products --
+ * everything above 2^-24 relative -- through v_mfma_f32_32x32x16_bf16, fp32 accumulate; ignored (native fp32 MFMA) with
+ * MATH_BF16, STORE_BF16 or Cin % 32 != 0.  P3: x rows [3][Cin] bf16, w [Cout][taps][3][Cin] bf16 ("planes" below), no
+ * operand split in the K loop, K step 32 channels.  Stream-K: fp32 math, untagged symbol, tiles 2-4; the K stages of the
+ * whole launch are shared evenly, tiles cut by a share boundary are reduced inside the launch in K order (deterministic);
+ * plain launch when there is less than one K stage per workgroup; ignored with X3 / P3.  Refused with -1: tiles 5 / 6
+ * without P3; tiles 7 / 8 without X3 (7 also runs with P3 | H2, one problem per launch), with stream-K bits, or when
+ * Cin does not divide by their K step; ROWPAIRS when Cin % 32 != 0; MASKQ with STORE_BF16 or a pair launch. */
 int radet_conv2d_igemm(const float* x, const float* w, const float* bias, const float* addend, const float* mask,
                        float* y, const int* gather_table, int M, int Cin, int Cout, int KH, int KW, int relu,
                        int tile_override, float* splitk_ws, size_t splitk_ws_floats, void* stream);
 /* Two independent convolutions of identical geometry (cls / reg tower layers of the shared head) in ONE launch */
-/* ... with amax slots: tile_override +0x8000000 (together with 0x1000000: fp32 tensors split in registers, tiles 1-4, 7, 8;
- * or with 0x2000000: operands arrive as fp16 plane pairs, tiles 5 / 6) selects the fp16 hi / lo arithmetic described at
- * RadetScales; x_amax and w_amax are required then.  y_amax alone may be used with any arithmetic. */
+/* ... with amax slots: RADET_TILE_H2 (together with X3: fp32 tensors split in registers, tiles 1-4, 7, 8; or with P3:
+ * operands arrive as fp16 plane pairs, tiles 1-3, 5-7) selects the fp16 hi / lo arithmetic described at RadetScales; x_amax
+ * and w_amax are required then.  y_amax alone may be used with any arithmetic. */
 int radet_conv2d_igemm_s(const float* x, const float* w, const float* bias, const float* addend, const float* mask,
                          float* y, const int* gather_table, int M, int Cin, int Cout, int KH, int KW, int relu,
                          int tile_override, float* splitk_ws, size_t splitk_ws_floats, void* stream, const RadetScales* sc);
@@ -177,37 +191,47 @@ int radet_conv2d_igemm_classes(const float* x, const float* w, const float* adde
  * LDS patch: x [rows][Cin] fp32 over all pyramid levels (rows of (level, image) contiguous, row-major H x W), w OHWI
  * [c][9][Cin], y [rows][c].  tiles_dev: ntiles x {base_row, H, W, (tile_y << 16) | tile_x} (int32), one 8 x 16 block of
  * output pixels each.  A second conv on the same input may share the launch (w1 / bias1 / y1 / c1; c0 + c1 <= 32).
- * Arithmetic: fp32 products from three bf16 planes per operand (as tile_override 0x1000000).  Cin % 16 == 0. */
+ * Arithmetic: fp32 products from three bf16 planes per operand (as RADET_TILE_X3).  Cin % 16 == 0. */
 int radet_pred3x3_patch(const float* x, int Cin, const int* tiles_dev, int ntiles, const float* w0, const float* bias0,
                         float* y0, int c0, const float* w1, const float* bias1, float* y1, int c1, void* stream);
 /* wgrad: slabs[s][o][tap][c] = sum over pixel split s of dy[m,o] * x[table[tap][m],c];
  * optional dbias_partials[s][o] = column sums of dy.  S from radet_conv2d_wgrad_splits.
- * flags bit 0: bf16 math mode (as tile_override 0x400 of radet_conv2d_igemm); bit 8 (0x100): fp32 products from three bf16
- * planes per operand (as tile_override 0x1000000); bits 4-5: tile override of the one-tap
- * kernel (1 = 128x128, 2 = 64x64; S is then the caller's choice); bit 6: never use the all-taps kernel; bit 7: 32
- * instead of 16 pixels per LDS stage in the one-tap fp32 kernel; bits 10 / 11 (0x400 / 0x800, with 0x100 and the 64x64 tile):
- * the four waves divide a 64-pixel stage four ways / a 32-pixel stage two ways and share the operand splits;
- * bit 1: bf16 storage -- dy and x are bf16 tensors (ld_dy / Cin in elements, multiples of 8), slabs stay fp32;
- * bit 9 (0x200): dy and x are bf16 plane triples (dy rows [3][ld_dy], x rows [3][Cin]; 3x3 convs with Cin % 32 == 0). */
+ * flags: a packed word, RADET_WGRAD_* below (its bits are NOT those of tile_override). */
+enum {
+    RADET_WGRAD_MATH_BF16 = 0x1,       /* bf16 math (as RADET_TILE_MATH_BF16) */
+    RADET_WGRAD_STORE_BF16 = 0x2,      /* bf16 storage: dy and x are bf16 tensors (ld_dy / Cin in elements, multiples of 8); slabs fp32 */
+    RADET_WGRAD_TILE = 0x10,           /* * t (bits 4-5): tile of the one-tap kernel, Cout x Cin = 1: 128 x 128, 2: 64 x 64,
+                                          3: 128 x 64 (X3 / H2 only); 0 = the launcher's choice.  S is then the caller's choice */
+    RADET_WGRAD_TILE_MASK = 0x30,
+    RADET_WGRAD_ONE_TAP = 0x40,        /* never use the all-taps kernel */
+    RADET_WGRAD_PX32 = 0x80,           /* 32 instead of 16 pixels per LDS stage (one-tap kernel, fp32 tensors, not bf16 math) */
+    RADET_WGRAD_X3 = 0x100,            /* fp32 products from three bf16 planes per operand (as RADET_TILE_X3) */
+    RADET_WGRAD_P3 = 0x200,            /* dy and x arrive as planes: bf16 triples (dy rows [3][ld_dy], x rows [3][Cin]), fp16 pairs with H2 */
+    RADET_WGRAD_KDIV4 = 0x400,         /* X3 / H2, 64 x 64 tile: the four waves divide a 64-pixel stage four ways ... */
+    RADET_WGRAD_KDIV2 = 0x800,         /* ... a 32-pixel stage two ways, and share the operand splits */
+    RADET_WGRAD_H2 = 0x1000,           /* fp16 hi / lo arithmetic (radet_conv2d_wgrad_s: both amax slots required) */
+    RADET_WGRAD_DEEP = 0x2000,         /* P3 | H2, 3 x 3: conv_wgrad9d_kernel (five stage buffers, loads four stages ahead) */
+    RADET_WGRAD_WINDOWS = 0x4000       /* P3 | H2, 3 x 3 (an experiment): conv_wgrad9r_kernel (shifted windows of row segments) */
+};
+/* P3 without H2: 3 x 3 convs with Cin % 32 == 0 and ld_dy % 32 == 0, no MATH_BF16 / STORE_BF16 (-1 otherwise). */
 int radet_conv2d_wgrad_splits(int M, int Cin, int Cout, int KH, int KW);
 int radet_conv2d_wgrad(const float* dy, const float* x, float* slabs, float* dbias_partials, const int* gather_table,
                        int M, int Cin, int Cout, int ld_dy, int KH, int KW, int S, int flags, void* stream);
-/* ... with amax slots: flags +0x1000 = fp16 hi / lo arithmetic (see RadetScales; sc->x_amax = the slot of dy, sc->w_amax = the
- * slot of x, both required): fp32 tensors split in registers with the one-tap tiles (bits 4-5, 7, 10-11 as for 0x100), or,
- * with +0x200, dy rows [2][ld_dy] / x rows [2][Cin] fp16 plane pairs (3x3 convs, Cin % 32 == 0, ld_dy % 32 == 0:
- * conv_wgrad9q_kernel, 128 output x 32 input channels x 9 taps per workgroup).  +0x2000 (with +0x200, 3x3): the gather table
- * is that of a unit-stride conv with padding 1 -- tap (r, q) of pixel m reads what tap (r, 1) of pixel m + q - 1 reads, or
- * padding: row - pixel fits 16 bits -- and the launch runs conv_wgrad9d_kernel (five stage buffers, loads four stages ahead,
- * the table rows of a pixel split copied to LDS; splits of more than 1664 pixels fall back to conv_wgrad9q_kernel).  +0x4000
- * (same geometry, an experiment): the nine taps take shifted windows of three row segments in LDS instead of nine gathered
- * tiles (conv_wgrad9r_kernel).  All three form the same sums in the same order: bit-identical results. */
+/* ... with amax slots: RADET_WGRAD_H2 (see RadetScales; sc->x_amax = the slot of dy, sc->w_amax = the slot of x; no MATH_BF16 /
+ * STORE_BF16): fp32 tensors split in registers with the one-tap tiles (TILE, PX32, KDIV4 / KDIV2 as for X3), or, with P3, dy
+ * rows [2][ld_dy] / x rows [2][Cin] fp16 plane pairs (Cin % 32 == 0, ld_dy % 32 == 0): 3 x 3 convs run conv_wgrad9q_kernel (128
+ * output x 32 input channels x 9 taps per workgroup) unless ONE_TAP is set; every other kernel size, and ONE_TAP, the one-tap
+ * pair kernel (TILE = 1: 128 x 128, otherwise 64 x 64).  DEEP and WINDOWS need the gather table of a unit-stride conv with
+ * padding 1 -- tap (r, q) of pixel m reads what tap (r, 1) of pixel m + q - 1 reads, or padding: row - pixel fits 16 bits;
+ * DEEP copies the table rows of a pixel split to LDS (splits of more than 1664 pixels fall back to conv_wgrad9q_kernel).  All
+ * three all-taps kernels form the same sums in the same order: bit-identical results. */
 int radet_conv2d_wgrad_s(const float* dy, const float* x, float* slabs, float* dbias_partials, const int* gather_table,
                          int M, int Cin, int Cout, int ld_dy, int KH, int KW, int S, int flags, void* stream,
                          const RadetScales* sc);
 /* Grouped wgrad: up to 32 independent weight-gradient GEMMs (one-tap kernel) in ONE launch -- the convs of a backbone
  * stage / of the neck, whose individual grids are too short to fill 256 CUs.  Each job = the arguments of
- * radet_conv2d_wgrad (host array; Cout and Cin multiples of the tile).  flags bit 0: bf16 math mode; bits 4-5 = 1:
- * 128x128 tiles (default 64x64). */
+ * radet_conv2d_wgrad (host array; Cout and Cin multiples of the tile).  flags: only RADET_WGRAD_MATH_BF16 and
+ * RADET_WGRAD_TILE are read (TILE = 1: 128 x 128 tiles, otherwise 64 x 64). */
 typedef struct RadetWgradJob {
     const float* dy;
     const float* x;
@@ -276,8 +300,8 @@ int radet_convert_rows(const void* src, void* dst, size_t rows, int ncols, int s
  * stored as three bf16 numbers hi + mid + lo == x exactly (8 significand bits each, truncation); a row of C channels is
  * [3][C] bf16 = hi | mid | lo, rows back to back (6 bytes per element).  The producers of a tensor that only conv GEMMs read
  * (GroupNorm+ReLU outputs of the head towers, their gradients, folded weights with RadetConvDesc.w16 = 2) write planes once;
- * radet_conv2d_igemm (+0x2000000) and radet_conv2d_wgrad (flags 0x200) multiply them on the bf16 matrix cores with fp32
- * accumulation (6 of the 9 plane products, as +0x1000000) -- same results as splitting the fp32 operands inside the GEMM,
+ * radet_conv2d_igemm (RADET_TILE_P3) and radet_conv2d_wgrad (RADET_WGRAD_P3) multiply them on the bf16 matrix cores with fp32
+ * accumulation (6 of the 9 plane products, as RADET_TILE_X3) -- same results as splitting the fp32 operands inside the GEMM,
  * without the per-use VALU work.  Replaces nothing in the reference by itself: it is the storage format behind the convs of
  * resnet.py:260-299 / fpn.py:170-221 / atss_head.py:118-145.  C % 8 == 0, row strides in floats, % 4 == 0. */
 int radet_split_planes(const float* src, void* dst_planes, size_t rows, int C, int src_ld, void* stream);
@@ -286,7 +310,7 @@ int radet_merge_planes(const void* src_planes, float* dst, size_t rows, int C, i
  * read.  A row of C channels (C % 32 == 0) is C / 32 groups of 128 bytes [hi x 32 | lo x 32] fp16 -- 4 bytes per element,
  * one cache line per 32-channel K stage and row -- holding x 2^e split as described at RadetScales, e from the tensor's amax
  * slot.  radet_split_pairs scales by the slot of src and copies the slot's bits to dst_amax; radet_merge_pairs is the
- * inverse (tests / API boundary).  radet_conv2d_igemm_s (+0x8000000 + 0x2000000) and radet_conv2d_wgrad_s (0x1000 + 0x200)
+ * inverse (tests / API boundary).  radet_conv2d_igemm_s (RADET_TILE_H2 | P3) and radet_conv2d_wgrad_s (RADET_WGRAD_H2 | P3)
  * multiply them with three v_mfma_f32_32x32x16_f16 per K = 16 step and no operand work in their K loops. */
 int radet_split_pairs(const float* src, void* dst_pairs, size_t rows, int C, int src_ld, const void* src_amax, void* dst_amax,
                       void* stream);

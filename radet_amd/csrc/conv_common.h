@@ -621,8 +621,42 @@ __device__ __forceinline__ void h2_combine(f32x16& acc0, const f32x16& acc1, flo
     for (int r = 0; r < 16; ++r) acc0[r] = (fmaf(acc1[r], 1.0f / 2048.0f, acc0[r]) * inv_a) * inv_b;
 }
 
+// ---- host side: the two packed launch words of the C ABI (include/radet_hip.h), decoded once.  These two functions are the
+// only place that applies a mask to `tile_override` / `flags`; the launchers read the fields.
+struct TileWord {             // tile_override of radet_conv2d_igemm* (RADET_TILE_*)
+    int id;                   // block tile, 0 = launcher heuristic
+    int splitk;               // forced split-K factor, 0 = launcher's choice
+    int stages;               // LDS stages asked for: 2, 3 or 4
+    int streamk;              // stream-K workgroups per CU, 0 = off
+    bool symbol, bk32, math_bf16, store_bf16, out_f32, rowpairs, x3, p3, h2, maskq;
+};
+inline TileWord decode_tile(int t) {
+    TileWord r;
+    r.id = t & RADET_TILE_ID_MASK;
+    r.splitk = (t & RADET_TILE_SPLITK_MASK) / RADET_TILE_SPLITK;
+    r.stages = (t & RADET_TILE_STAGES4) ? 4 : ((t & RADET_TILE_STAGES3) ? 3 : 2);
+    r.streamk = (t & RADET_TILE_STREAMK_MASK) / RADET_TILE_STREAMK;
+    r.symbol = t & RADET_TILE_SYMBOL; r.bk32 = t & RADET_TILE_BK32;
+    r.math_bf16 = t & RADET_TILE_MATH_BF16; r.store_bf16 = t & RADET_TILE_STORE_BF16; r.out_f32 = t & RADET_TILE_OUT_F32;
+    r.rowpairs = t & RADET_TILE_ROWPAIRS; r.x3 = t & RADET_TILE_X3; r.p3 = t & RADET_TILE_P3; r.h2 = t & RADET_TILE_H2;
+    r.maskq = t & RADET_TILE_MASKQ;
+    return r;
+}
+struct WgradFlags {           // flags of radet_conv2d_wgrad* (RADET_WGRAD_*)
+    int tile;                 // one-tap tile: 0 launcher, 1 = 128 x 128, 2 = 64 x 64, 3 = 128 x 64
+    bool math_bf16, store_bf16, one_tap, px32, x3, p3, kdiv4, kdiv2, h2, deep, windows;
+};
+inline WgradFlags decode_wgrad(int f) {
+    WgradFlags r;
+    r.tile = (f & RADET_WGRAD_TILE_MASK) / RADET_WGRAD_TILE;
+    r.math_bf16 = f & RADET_WGRAD_MATH_BF16; r.store_bf16 = f & RADET_WGRAD_STORE_BF16; r.one_tap = f & RADET_WGRAD_ONE_TAP;
+    r.px32 = f & RADET_WGRAD_PX32; r.x3 = f & RADET_WGRAD_X3; r.p3 = f & RADET_WGRAD_P3; r.kdiv4 = f & RADET_WGRAD_KDIV4;
+    r.kdiv2 = f & RADET_WGRAD_KDIV2; r.h2 = f & RADET_WGRAD_H2; r.deep = f & RADET_WGRAD_DEEP; r.windows = f & RADET_WGRAD_WINDOWS;
+    return r;
+}
+
 // ---- launchers of the fp16 hi / lo instantiations (conv_h2.hip, conv_wgrad_h2.hip: their own translation units, compiled next to conv_igemm.hip)
 bool radet_launch_igemm_h2(int choice, const ConvArgs& a, hipStream_t st, int tag, int bk, size_t ws_floats, int stages,
                            bool no_tail_split);
 struct WgradArgs;
-int radet_launch_wgrad_h2(const WgradArgs& a, int flags, int bm, int bn, hipStream_t st);
+int radet_launch_wgrad_h2(const WgradArgs& a, const WgradFlags& f, int bm, int bn, hipStream_t st);

@@ -31,7 +31,7 @@
 // in chunks of 16: the 10 x 18 input patch of the chunk (zero outside the image) and the [9][32][16] weight slice go
 // global -> LDS once (LDS-DMA, XOR-swizzled 16-byte slots as in the implicit-GEMM kernel), and the nine taps are nine
 // fragment reads at shifted patch positions: 1.4 fetches per pixel row instead of 9.  Arithmetic: fp32 operands split
-// into three bf16 planes in registers, 6 plane products per K = 16 on the bf16 matrix cores (as TAG bit 3 above).
+// into three bf16 planes in registers, 6 plane products per K = 16 on the bf16 matrix cores (as TAG_X3 above).
 // Up to two convs of the same input share a launch (reg + iou: output columns [0, c0) -> y0, [c0, c0 + c1) -> y1).
 struct PredTile { int base_row, H, W, yx; };      // rows of this (level, image) start at base_row; yx = (tile y << 16) | tile x
 struct PredArgs {
@@ -797,7 +797,7 @@ static const RadetSwitches& radet_switches() {
     return s;
 }
 
-// plane-operand instantiations (TAG bit 4): K step 16 units (32 channels) with 2 or 3 LDS stages, or 8 units with 2 or 4;
+// plane-operand instantiations (TAG_P3): K step 16 units (32 channels) with 2 or 3 LDS stages, or 8 units with 2 or 4;
 // a configuration whose tiles would not fit the CU's 160 KiB of LDS falls back to the next smaller one
 template <int BM, int BN, int WM, int WN>
 static void launch_p3(const ConvArgs& a, hipStream_t st, int tag, int bk, int stages, int tiles) {
@@ -807,10 +807,10 @@ static void launch_p3(const ConvArgs& a, hipStream_t st, int tag, int bk, int st
 #define RADET_LAUNCH_P3(TAGV, BKV, NSV) \
     hipLaunchKernelGGL((conv_igemmg_kernel<BM, BN, WM, WN, TAGV, BKV, NSV>), dim3(tiles, a.sk), dim3(NT), 0, st, a)
     if constexpr (3 * STG16 <= LDS_MAX) {
-        if (stages >= 3) { RADET_LAUNCH_P3(16, 16, 3); return; }
+        if (stages >= 3) { RADET_LAUNCH_P3(TAG_P3, 16, 3); return; }
     }
     if constexpr (2 * STG16 <= LDS_MAX) {
-        if (tag & 1) RADET_LAUNCH_P3(17, 16, 2); else RADET_LAUNCH_P3(16, 16, 2);
+        if (tag & TAG_SYMBOL) RADET_LAUNCH_P3(TAG_P3 | TAG_SYMBOL, 16, 2); else RADET_LAUNCH_P3(TAG_P3, 16, 2);
     }
 #undef RADET_LAUNCH_P3
 }
@@ -819,15 +819,15 @@ template <int BM, int BN, int WM, int WN, bool P3ONLY = false>
 static void launch_igemm(const ConvArgs& a_in, hipStream_t st, int tag, int bk, size_t ws_floats, int stages, int skw) {
     ConvArgs a = a_in;
     const int tiles = igemm_plan<BM, BN>(a, tag, bk, ws_floats, skw, radet_switches().no_tail_split);
-    if (tag & 16) {
+    if (tag & TAG_P3) {
         launch_p3<BM, BN, WM, WN>(a, st, tag, bk, stages, tiles);
         return;
     }
-    if (tag & 32) {                       // K-divided 4-wave tile (fp32 operands split in registers): K step 64 / 32
+    if (tag & TAG_KDIV) {                 // K-divided 4-wave tile (fp32 operands split in registers): K step 64 / 32
         if constexpr (BM == 64 && BN == 64 && WM * WN == 4) {
 #define RADET_LAUNCH_KW(BKV) \
-    do { if (tag & 1) hipLaunchKernelGGL((conv_igemmg_kernel<BM, BN, WM, WN, 41, BKV, 2>), dim3(tiles, a.sk), dim3(256), 0, st, a); \
-         else hipLaunchKernelGGL((conv_igemmg_kernel<BM, BN, WM, WN, 40, BKV, 2>), dim3(tiles, a.sk), dim3(256), 0, st, a); } while (0)
+    do { if (tag & TAG_SYMBOL) hipLaunchKernelGGL((conv_igemmg_kernel<BM, BN, WM, WN, TAG_X3 | TAG_KDIV | TAG_SYMBOL, BKV, 2>), dim3(tiles, a.sk), dim3(256), 0, st, a); \
+         else hipLaunchKernelGGL((conv_igemmg_kernel<BM, BN, WM, WN, TAG_X3 | TAG_KDIV, BKV, 2>), dim3(tiles, a.sk), dim3(256), 0, st, a); } while (0)
             if (bk == 64) RADET_LAUNCH_KW(64); else RADET_LAUNCH_KW(32);
 #undef RADET_LAUNCH_KW
         }
@@ -838,31 +838,31 @@ static void launch_igemm(const ConvArgs& a_in, hipStream_t st, int tag, int bk, 
         if (a.sk_wgs > 0) {                                            // stream-K: tag 0, 2 stages
             if (bk == 32) hipLaunchKernelGGL((conv_igemmg_kernel<BM, BN, WM, WN, 0, 32, 2, true>), dim3(tiles, 1), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((conv_igemmg_kernel<BM, BN, WM, WN, 0, 16, 2, true>), dim3(tiles, 1), dim3(256), 0, st, a);
-        } else if (stages >= 3 && (tag < 2 || (tag & 8))) {
+        } else if (stages >= 3 && (tag <= TAG_SYMBOL || (tag & TAG_X3))) {
 #define RADET_LAUNCH_IGEMM3(TAGV, BKV) hipLaunchKernelGGL((conv_igemmg_kernel<BM, BN, WM, WN, TAGV, BKV, 3>), dim3(tiles, a.sk), dim3(256), 0, st, a)
-            if (tag & 8) { if (tag & 1) RADET_LAUNCH_IGEMM3(9, 32); else RADET_LAUNCH_IGEMM3(8, 32); }
-            else if (bk == 32) { if (tag) RADET_LAUNCH_IGEMM3(1, 32); else RADET_LAUNCH_IGEMM3(0, 32); }
-            else          { if (tag) RADET_LAUNCH_IGEMM3(1, 16); else RADET_LAUNCH_IGEMM3(0, 16); }
+            if (tag & TAG_X3) { if (tag & TAG_SYMBOL) RADET_LAUNCH_IGEMM3(TAG_X3 | TAG_SYMBOL, 32); else RADET_LAUNCH_IGEMM3(TAG_X3, 32); }
+            else if (bk == 32) { if (tag) RADET_LAUNCH_IGEMM3(TAG_SYMBOL, 32); else RADET_LAUNCH_IGEMM3(0, 32); }
+            else          { if (tag) RADET_LAUNCH_IGEMM3(TAG_SYMBOL, 16); else RADET_LAUNCH_IGEMM3(0, 16); }
 #undef RADET_LAUNCH_IGEMM3
-        } else if (tag & 8) {                                          // bf16 x 3 planes (fp32 tensors), K step 32
-            if (tag & 1) RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 9, 32); else RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 8, 32);
+        } else if (tag & TAG_X3) {                                     // bf16 x 3 planes (fp32 tensors), K step 32
+            if (tag & TAG_SYMBOL) RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_X3 | TAG_SYMBOL, 32); else RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_X3, 32);
         } else if (bk == 32) {
             switch (tag) {
                 case 0: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 0, 32); break;
-                case 1: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 1, 32); break;
-                case 2: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 2, 32); break;
-                case 3: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 3, 32); break;
-                case 4: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 4, 32); break;
-                default: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 5, 32); break;
+                case TAG_SYMBOL: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_SYMBOL, 32); break;
+                case TAG_BF16_MATH: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_BF16_MATH, 32); break;
+                case TAG_BF16_MATH | TAG_SYMBOL: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_BF16_MATH | TAG_SYMBOL, 32); break;
+                case TAG_H16: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_H16, 32); break;
+                default: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_H16 | TAG_SYMBOL, 32); break;
             }
         } else {
             switch (tag) {
                 case 0: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 0, 16); break;
-                case 1: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 1, 16); break;
-                case 2: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 2, 16); break;
-                case 3: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 3, 16); break;
-                case 4: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 4, 16); break;
-                default: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, 5, 16); break;
+                case TAG_SYMBOL: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_SYMBOL, 16); break;
+                case TAG_BF16_MATH: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_BF16_MATH, 16); break;
+                case TAG_BF16_MATH | TAG_SYMBOL: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_BF16_MATH | TAG_SYMBOL, 16); break;
+                case TAG_H16: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_H16, 16); break;
+                default: RADET_LAUNCH_IGEMM(conv_igemmg_kernel, TAG_H16 | TAG_SYMBOL, 16); break;
             }
         }
     }
@@ -929,7 +929,7 @@ extern "C" int radet_conv2d_igemm(const float* x, const float* w, const float* b
                       splitk_ws_floats, nullptr, nullptr, 0, stream);
 }
 
-// The same entry points with the amax slots of the fp16 hi / lo arithmetic (tile_override 0x8000000) and / or of the output
+// The same entry points with the amax slots of the fp16 hi / lo arithmetic (RADET_TILE_H2) and / or of the output
 // (sc->y_amax: raised to the largest |y| stored, any arithmetic).  sc is a HOST struct of device pointers.
 extern "C" int radet_conv2d_igemm_s(const float* x, const float* w, const float* bias, const float* addend,
                                     const float* mask, float* y, const int* gather_table, int M, int Cin, int Cout,
@@ -1013,10 +1013,11 @@ static int igemm_impl(const float* x, const float* w, const float* bias, const f
                       int tile_override, float* splitk_ws, size_t splitk_ws_floats, const int* out_rows,
                       const int* tap_ids, int kt_w, void* stream, const ConvPtrs* second, const int* cls,
                       const RadetScales* sc) {
-    const int h16 = (tile_override >> 11) & 1;                 // 0x800: bf16 storage, 0x10000: fp32 output from bf16 inputs
-    // 0x2000000: x and w are bf16 plane triples (x rows [3][Cin], w [Cout][taps][3][Cin]; hi + mid + lo = the fp32 value);
-    // y / addend / mask / bias stay fp32.  +0x4000000: K step of 16 instead of 32 channels
-    const int p3 = ((tile_override >> 25) & 1) && !h16;
+    const TileWord tw = decode_tile(tile_override);
+    const bool h16 = tw.store_bf16;
+    // x and w are bf16 plane triples (x rows [3][Cin], w [Cout][taps][3][Cin]; hi + mid + lo = the fp32 value);
+    // y / addend / mask / bias stay fp32
+    const bool p3 = tw.p3 && !h16;
     if (h16 || p3) {
         if (Cin % 32 != 0) return RADET_ERR_ARG;               // 16 channel pairs per K step at least
         Cin /= 2;                                              // K is counted in channel pairs (4-byte units) from here on
@@ -1026,7 +1027,7 @@ static int igemm_impl(const float* x, const float* w, const float* bias, const f
         (gather_table == nullptr && (KH * KW != 1 || out_rows != nullptr || cls != nullptr)))
         return RADET_ERR_ARG;
     ConvArgs a;
-    a.io = h16 ? (((tile_override >> 16) & 1) ? 2 : 1) : 0;
+    a.io = h16 ? (tw.out_f32 ? 2 : 1) : 0;
     a.out_rows = out_rows;
     for (int t = 0; t < 16; ++t) a.tap_ids[t] = tap_ids ? (t < KH * KW ? tap_ids[t] : 0) : t;
     a.cls_nt = 0; a.cls_b[0] = a.cls_b[1] = a.cls_b[2] = 0x7fffffff;
@@ -1039,9 +1040,9 @@ static int igemm_impl(const float* x, const float* w, const float* bias, const f
     }
     a.KTw = kt_w > 0 ? kt_w : KH * KW;
     { static const int dbg = getenv("RADET_DBG_IGEMM") ? atoi(getenv("RADET_DBG_IGEMM")) : 0; a.dbg = dbg; }
-    // 0x10000000: `mask` is an fp16 plane-pair tensor (rows [2][Cout]) -- the ReLU mask of an activation that exists only as
-    // pairs (fp32 tensors only)
-    a.maskq = ((tile_override >> 28) & 1) && mask != nullptr;
+    // `mask` is an fp16 plane-pair tensor (rows [2][Cout]) -- the ReLU mask of an activation that exists only as pairs (fp32
+    // tensors only)
+    a.maskq = tw.maskq && mask != nullptr;
     if (a.maskq && (h16 || Cout % 32 != 0 || second != nullptr)) return RADET_ERR_ARG;
     // y may be NULL when the output is wanted as plane pairs only (RadetScales.yq): the launch then stores no fp32 tensor
     if (y == nullptr && (sc == nullptr || sc->yq == nullptr)) return RADET_ERR_ARG;
@@ -1076,47 +1077,47 @@ static int igemm_impl(const float* x, const float* w, const float* bias, const f
     a.M = M;
     a.Mp = radet_gather_table_rows(M);
     hipStream_t st = (hipStream_t)stream;
-    int tag = h16 ? (4 | ((tile_override >> 8) & 1))
-                  : (((tile_override >> 8) & 1) | (((tile_override >> 10) & 1) << 1));   // 0x100 symbol tag, 0x400 bf16 math
-    int bk = ((tile_override >> 9) & 1) ? 32 : 16;
+    const int sym = tw.symbol ? TAG_SYMBOL : 0;
+    int tag = sym | (h16 ? TAG_H16 : (tw.math_bf16 ? TAG_BF16_MATH : 0));
+    int bk = tw.bk32 ? 32 : 16;
     if (Cin % 32 != 0) bk = 16;
-    // 0x1000000: fp32 tensors, products from three bf16 planes per operand (6 bf16 MFMAs per K = 16 step); K step 32
-    const bool x3 = ((tile_override >> 24) & 1) && !h16 && !p3 && !((tile_override >> 10) & 1) && Cin % 32 == 0;
-    if (x3) { bk = 32; tag |= 8; }
-    if (p3) { tag = 16 | ((tile_override >> 8) & 1); bk = 16; }
-    // 0x8000000 (with 0x1000000 or 0x2000000): fp16 hi / lo arithmetic -- operands scaled by the power of two their amax
-    // slots give, two fp16 planes each, three f16 MFMAs per K = 16 step (common.h "h2"); with 0x2000000 the operands ARRIVE
-    // as fp16 plane pairs.  Needs the slots (radet_conv2d_igemm_s).  Without a plane-capable K (Cin % 32) the launch falls
-    // back to the native fp32 MFMA like 0x1000000 does.
-    const bool h2 = ((tile_override >> 27) & 1) && (x3 || p3);
+    // fp32 tensors, products from three bf16 planes per operand (6 bf16 MFMAs per K = 16 step); K step 32
+    const bool x3 = tw.x3 && !h16 && !p3 && !tw.math_bf16 && Cin % 32 == 0;
+    if (x3) { bk = 32; tag |= TAG_X3; }
+    if (p3) { tag = TAG_P3 | sym; bk = 16; }
+    // fp16 hi / lo arithmetic (with x3 or p3) -- operands scaled by the power of two their amax slots give, two fp16 planes
+    // each, three f16 MFMAs per K = 16 step (common.h "h2"); with p3 the operands ARRIVE as fp16 plane pairs.  Needs the
+    // slots (radet_conv2d_igemm_s).  Without a plane-capable K (Cin % 32) the launch falls back to the native fp32 MFMA like
+    // x3 does.
+    const bool h2 = tw.h2 && (x3 || p3);
     if (h2) {
         for (int g = 0; g < a.groups; ++g)
             if (a.p[g].xs == nullptr || a.p[g].ws == nullptr) return RADET_ERR_ARG;
-        tag |= 64;
+        tag |= TAG_H2;
     }
-    int choice = tile_override & 0xFF;
-    if (p3 && h2 && ((tile_override >> 19) & 1) && (choice == 5 || choice == 6)) {
-        // 0x80000: row-interleaved plane pairs for the 8-wave tiles (TAG bit 7 with bit 4): one wave load fetches both planes
+    int choice = tw.id;
+    if (p3 && h2 && tw.rowpairs && (choice == 5 || choice == 6)) {
+        // row-interleaved plane pairs for the 8-wave tiles (TAG_PAIRS with TAG_P3): one wave load fetches both planes
         // of 8 tile rows (128 contiguous bytes per row) instead of one plane of 16 -- the launch counts K in channels again
         // (a pair row is as long as the fp32 row) and its stage is 32 four-byte units
         Cin *= 2;
         a.Cin = Cin;
         if (Cin % 32 != 0) return RADET_ERR_ARG;
-        tag |= 128; bk = 32;
+        tag |= TAG_PAIRS; bk = 32;
     }
     if (choice == 7 && p3 && h2) {
         // K-divided 64 x 64 tile on fp16 plane PAIRS (round 6): a pair row has the fp32 row's byte length, so the launch is
-        // the fp32 K-divided one (K counted in channels again, 64-channel stages) with the reader's pair flag (TAG bit 7)
+        // the fp32 K-divided one (K counted in channels again, 64-channel stages) with the reader's pair flag (TAG_PAIRS)
         Cin *= 2;
         a.Cin = Cin;
-        if (Cin % 64 != 0 || ((tile_override >> 20) & 7) || a.groups != 1) return RADET_ERR_ARG;
-        tag = 8 | 32 | 64 | 128; bk = 64;
+        if (Cin % 64 != 0 || tw.streamk || a.groups != 1) return RADET_ERR_ARG;
+        tag = TAG_X3 | TAG_KDIV | TAG_H2 | TAG_PAIRS; bk = 64;
     } else
-    if (choice == 7 || choice == 8) {                          // 64 x 64 tiles whose four waves divide the K step (see TAG bit 5):
+    if (choice == 7 || choice == 8) {                          // 64 x 64 tiles whose four waves divide the K step (see TAG_KDIV):
         // 7: four k-groups of a 64-channel stage; 8: two k-groups x two column halves of a 32-channel stage
         const int kbk = choice == 7 ? 64 : 32;
-        if (!x3 || Cin % kbk != 0 || ((tile_override >> 20) & 7)) return RADET_ERR_ARG;
-        tag |= 32; bk = kbk;
+        if (!x3 || Cin % kbk != 0 || tw.streamk) return RADET_ERR_ARG;
+        tag |= TAG_KDIV; bk = kbk;
     } else
     if (choice > 4 && !p3) return RADET_ERR_ARG;               // the 8-wave tiles exist for plane operands only
     if (choice == 6 && cls != nullptr) return RADET_ERR_ARG;   // class boundaries are multiples of 128 rows
@@ -1135,10 +1136,10 @@ static int igemm_impl(const float* x, const float* w, const float* bias, const f
     // split-K for launches that cannot fill 256 CUs twice over (low-M stages): each split keeps >= 8 K stages
     const int nK = KH * KW * (Cin / bk);
     int sk = 1;
-    // 0x20000: 3 LDS stages (launches that run alone); 0x40000: 4 (the fp16 hi / lo K-divided tile 8 only)
-    const int stages3 = ((tile_override >> 18) & 1) ? 4 : (((tile_override >> 17) & 1) ? 3 : 2);
-    const int skw = cls ? 0 : (tile_override >> 20) & 7;     // 0x100000 * w: stream-K, w workgroups per CU
-    const int sk_force = skw ? 1 : (tile_override >> 12) & 0xF;
+    // 3 LDS stages: launches that run alone; 4: the fp16 hi / lo K-divided tile 8 only
+    const int stages3 = tw.stages;
+    const int skw = cls ? 0 : tw.streamk;                      // stream-K, skw workgroups per CU
+    const int sk_force = skw ? 1 : tw.splitk;
     const long tiles = igemm_tiles(a.M, Cout, choice) * a.groups;
     if (splitk_ws != nullptr && a.groups == 1 && !radet_switches().no_splitk) {
         if (sk_force) sk = sk_force;
@@ -1162,7 +1163,7 @@ static int igemm_impl(const float* x, const float* w, const float* bias, const f
         a.it_per_split = nK;
         splitk_ws_floats = 0;
     }
-    if (tag & 64) {                                            // (stream-K bits are ignored, as for the bf16-plane arithmetic)
+    if (tag & TAG_H2) {                                        // (stream-K bits are ignored, as for the bf16-plane arithmetic)
         if (!radet_launch_igemm_h2(choice, a, st, tag, bk, splitk_ws_floats, stages3, radet_switches().no_tail_split))
             return RADET_ERR_ARG;
         return radet_check_launch();
@@ -1214,6 +1215,19 @@ static void wgrad_tile(int M, int Cout, int Cin, int KT, int* bm, int* bn) {
     if (M <= mthr && s128 >= 4) { *bm = 64; *bn = 64; }
 }
 
+// Tile of a one-tap launch: the launcher's choice unless the flags name one (the autotuned tile, radet_amd/kernels.py).  The
+// 32 x 128 tile of the small heads is never overridden.  The bf16-storage kernel has two tiles and reads the field as
+// "1 = 128 x 128, anything else = 64 x 64" -- also 0, where the other arithmetics keep the launcher's choice: kept exactly.
+// 128 (output channels) x 64 (input channels): two accumulators per wave -- three operand splits per two MFMA blocks instead of
+// two per block; exists for the plane arithmetics (has_128x64), where the 64 x 64 tile is VALU-bound.
+static void wgrad_onetap_tile(const WgradFlags& f, bool has_128x64, int M, int Cout, int Cin, int KT, int* bm, int* bn) {
+    wgrad_tile(M, Cout, Cin, KT, bm, bn);
+    if (*bm == 32) return;
+    if (f.tile == 1) *bm = *bn = 128;
+    else if (f.tile == 2 || f.store_bf16) *bm = *bn = 64;
+    else if (f.tile == 3 && has_128x64) { *bm = 128; *bn = 64; }
+}
+
 // Number of pixel splits the wgrad launcher will use (callers size the slab buffer with it).
 extern "C" int radet_conv2d_wgrad_splits(int M, int Cin, int Cout, int KH, int KW) {
     int bm, bn;
@@ -1255,7 +1269,7 @@ extern "C" int radet_conv2d_wgrad(const float* dy, const float* x, float* slabs,
                                   int flags, void* stream) {
     return wgrad_impl(dy, x, slabs, dbias_partials, gather_table, M, Cin, Cout, ld_dy, KH, KW, S, flags, stream, nullptr);
 }
-// with the amax slots of the fp16 hi / lo arithmetic (flags 0x1000): sc->x_amax = the slot of dy, sc->w_amax = the slot of x
+// with the amax slots of the fp16 hi / lo arithmetic (RADET_WGRAD_H2): sc->x_amax = the slot of dy, sc->w_amax = the slot of x
 extern "C" int radet_conv2d_wgrad_s(const float* dy, const float* x, float* slabs, float* dbias_partials,
                                     const int* gather_table, int M, int Cin, int Cout, int ld_dy, int KH, int KW, int S,
                                     int flags, void* stream, const RadetScales* sc) {
@@ -1267,7 +1281,8 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* dbia
     if (Cin % 4 != 0 || S < 1 || ld_dy < Cout || (ld_dy & 3) || ((Cout + 3) / 4) * 4 > ld_dy || M <= 0 ||
         (gather_table == nullptr && KH * KW != 1))
         return RADET_ERR_ARG;
-    if ((flags & 2) && ((Cout + 7) / 8) * 8 > ld_dy) return RADET_ERR_ARG;   // whole 8-channel groups per dy row
+    const WgradFlags f = decode_wgrad(flags);
+    if (f.store_bf16 && ((Cout + 7) / 8) * 8 > ld_dy) return RADET_ERR_ARG;   // whole 8-channel groups per dy row
     WgradArgs a;
     a.ld_dy = ld_dy;
     a.dy = dy; a.x = x; a.slabs = slabs; a.dbias_partials = dbias_partials;
@@ -1277,29 +1292,24 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* dbia
     a.Mp = radet_gather_table_rows(M);
     a.S = S;
     a.dbg = radet_switches().dbg_wgrad;
-    a.math = (flags & 1) ? 1 : (((flags >> 8) & 1) && !(flags & 2) ? 2 : 0);   // 0x100: fp32 products from 3 bf16 planes
-    a.bp32 = (flags >> 7) & 1;
+    a.math = f.math_bf16 ? 1 : (f.x3 && !f.store_bf16 ? 2 : 0);              // 2: fp32 products from 3 bf16 planes
+    a.bp32 = f.px32;
     a.dys = sc ? (const unsigned*)sc->x_amax : nullptr;
     a.xss = sc ? (const unsigned*)sc->w_amax : nullptr;
     const int chunks = (a.M + 15) / 16;
     a.chunks_per_split = (chunks + S - 1) / S;
     hipStream_t st = (hipStream_t)stream;
-    if (flags & 0x1000) {
-        // fp16 hi / lo arithmetic (common.h "h2"): fp32 tensors split in registers (one-tap tiles), or, with 0x200, operands
-        // that arrive as fp16 plane pairs (all-taps kernel, 3 x 3 only); needs both amax slots
-        if ((flags & 3) || a.dys == nullptr || a.xss == nullptr) return RADET_ERR_ARG;
+    if (f.h2) {
+        // fp16 hi / lo arithmetic (common.h "h2"): fp32 tensors split in registers (one-tap tiles), or, with p3, operands
+        // that arrive as fp16 plane pairs; needs both amax slots
+        if (f.math_bf16 || f.store_bf16 || a.dys == nullptr || a.xss == nullptr) return RADET_ERR_ARG;
         a.math = 3;
         int bm = 0, bn = 0;
-        if (!(flags & 0x200)) {
-            wgrad_tile(M, Cout, Cin, KH * KW, &bm, &bn);
-            if (bm != 32 && ((flags >> 4) & 3) == 1) bm = bn = 128;
-            if (bm != 32 && ((flags >> 4) & 3) == 2) bm = bn = 64;
-            if (bm != 32 && ((flags >> 4) & 3) == 3) { bm = 128; bn = 64; }
-        }
-        return radet_launch_wgrad_h2(a, flags, bm, bn, st);
+        if (!f.p3) wgrad_onetap_tile(f, true, M, Cout, Cin, KH * KW, &bm, &bn);
+        return radet_launch_wgrad_h2(a, f, bm, bn, st);
     }
-    if (flags & 0x200) {   // plane operands: dy rows [3][ld_dy] bf16, x rows [3][Cin] bf16 (hi | mid | lo)
-        if ((ld_dy & 31) || (Cin & 31) || (flags & 3)) return RADET_ERR_ARG;
+    if (f.p3) {   // plane operands: dy rows [3][ld_dy] bf16, x rows [3][Cin] bf16 (hi | mid | lo)
+        if ((ld_dy & 31) || (Cin & 31) || f.math_bf16 || f.store_bf16) return RADET_ERR_ARG;
         if (KH == 3 && KW == 3 && Cin % 32 == 0) {
             const int tiles9 = ((Cout + 255) / 256) * (Cin / 32) * S;
             hipLaunchKernelGGL(conv_wgrad9p_kernel, dim3(tiles9), dim3(512), 0, st, a);
@@ -1307,24 +1317,22 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* dbia
         }
         return RADET_ERR_ARG;
     }
-    if (flags & 2) {   // bf16 storage: dy / x are bf16 (ld_dy, Cin in elements; 16-byte aligned rows)
+    if (f.store_bf16) {   // bf16 storage: dy / x are bf16 (ld_dy, Cin in elements; 16-byte aligned rows)
         if ((ld_dy & 7) || (Cin & 7)) return RADET_ERR_ARG;
-        if (use_wgrad9(M, Cin, Cout, KH, KW) && wgrad9_bm(Cout) == 256 && !(flags & 0x40) && !radet_switches().no_wgrad9) {
+        if (use_wgrad9(M, Cin, Cout, KH, KW) && wgrad9_bm(Cout) == 256 && !f.one_tap && !radet_switches().no_wgrad9) {
             const int tiles9 = ((Cout + 255) / 256) * (Cin / 32) * S;
             hipLaunchKernelGGL(conv_wgrad9h_kernel, dim3(tiles9), dim3(512), 0, st, a);
             return radet_check_launch();
         }
         int bm, bn;
-        wgrad_tile(M, Cout, Cin, KH * KW, &bm, &bn);
-        if (bm != 32 && ((flags >> 4) & 3) == 1) bm = bn = 128;
-        if (bm != 32 && ((flags >> 4) & 3) != 1) bm = bn = 64;
+        wgrad_onetap_tile(f, false, M, Cout, Cin, KH * KW, &bm, &bn);
         const int tiles = ((Cout + bm - 1) / bm) * ((Cin + bn - 1) / bn) * KH * KW * S;
         if (bm == 32) hipLaunchKernelGGL((conv_wgradh_kernel<32, 128, 1, 4>), dim3(tiles), dim3(256), 0, st, a);
         else if (bm == 64) hipLaunchKernelGGL((conv_wgradh_kernel<64, 64, 2, 2>), dim3(tiles), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((conv_wgradh_kernel<128, 128, 2, 2>), dim3(tiles), dim3(256), 0, st, a);
         return radet_check_launch();
     }
-    if (use_wgrad9(M, Cin, Cout, KH, KW) && !(flags & 0x40) && (a.math == 0 || wgrad9_bm(Cout) == 256)) {
+    if (use_wgrad9(M, Cin, Cout, KH, KW) && !f.one_tap && (a.math == 0 || wgrad9_bm(Cout) == 256)) {
         if (wgrad9_bm(Cout) == 256) {
             const int tiles = ((Cout + 255) / 256) * (Cin / 32) * S;
             if (a.math == 2) hipLaunchKernelGGL((conv_wgrad9g_kernel<8, 2>), dim3(tiles), dim3(512), 0, st, a);
@@ -1337,17 +1345,12 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* dbia
         return radet_check_launch();
     }
     int bm, bn;
-    wgrad_tile(M, Cout, Cin, KH * KW, &bm, &bn);
-    if (bm != 32 && ((flags >> 4) & 3) == 1) bm = bn = 128;      // autotuned tile (radet_amd/kernels.py)
-    if (bm != 32 && ((flags >> 4) & 3) == 2) bm = bn = 64;
-    // 128 (output channels) x 64 (input channels): two accumulators per wave -- three operand splits per two MFMA blocks
-    // instead of two per block; offered to the tuner with the bf16-plane arithmetic, where the 64 x 64 tile is VALU-bound
-    if (bm != 32 && ((flags >> 4) & 3) == 3 && a.math == 2) { bm = 128; bn = 64; }
-    // 0x400 / 0x800 (bf16-plane arithmetic, 64 x 64 tile): the four waves divide a 64-pixel stage four ways / a 32-pixel
+    wgrad_onetap_tile(f, a.math == 2, M, Cout, Cin, KH * KW, &bm, &bn);
+    // kdiv4 / kdiv2 (bf16-plane arithmetic, 64 x 64 tile): the four waves divide a 64-pixel stage four ways / a 32-pixel
     // stage two ways (x two column halves) and share the operand splits (see wgradg_body, KD)
-    if (bm == 64 && a.math == 2 && (flags & 0xC00)) {
+    if (bm == 64 && a.math == 2 && (f.kdiv4 || f.kdiv2)) {
         const int tiles = ((a.Cout + 63) / 64) * ((a.Cin + 63) / 64) * a.KH * a.KW * a.S;
-        if (flags & 0x400) hipLaunchKernelGGL((conv_wgradg_kernel<64, 64, 2, 2, 2, 64, 4>), dim3(tiles), dim3(256), 0, st, a);
+        if (f.kdiv4) hipLaunchKernelGGL((conv_wgradg_kernel<64, 64, 2, 2, 2, 64, 4>), dim3(tiles), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((conv_wgradg_kernel<64, 64, 2, 2, 2, 32, 2>), dim3(tiles), dim3(256), 0, st, a);
     } else
     if (bm == 32) launch_wgrad<32, 128, 1, 4>(a, st);
@@ -1361,10 +1364,11 @@ static int wgrad_impl(const float* dy, const float* x, float* slabs, float* dbia
 }
 
 // Grouped one-tap wgrad (see conv_wgradg_group_kernel): jobs[i] describes one conv exactly like the arguments of
-// radet_conv2d_wgrad.  flags bit 0: bf16 math mode; bits 4-5: tile (1 = 128x128, otherwise 64x64).
+// radet_conv2d_wgrad.  Of the flags only math_bf16 and tile are read (1 = 128 x 128, otherwise 64 x 64).
 extern "C" int radet_conv2d_wgrad_group(const RadetWgradJob* jobs, int njobs, int flags, void* stream) {
     if (njobs < 1 || njobs > WG_MAX || jobs == nullptr) return RADET_ERR_ARG;
-    const int bm = ((flags >> 4) & 3) == 1 ? 128 : 64;
+    const WgradFlags f = decode_wgrad(flags);
+    const int bm = f.tile == 1 ? 128 : 64;
     WgradGroup g;
     g.n = njobs;
     int total = 0;
@@ -1376,7 +1380,7 @@ extern "C" int radet_conv2d_wgrad_group(const RadetWgradJob* jobs, int njobs, in
         WgradArgs& a = g.p[i];
         a.dy = j.dy; a.x = j.x; a.slabs = j.slabs; a.dbias_partials = j.dbias_partials; a.rowtab = j.gather_table;
         a.M = j.M; a.Mp = radet_gather_table_rows(j.M); a.Cin = j.Cin; a.Cout = j.Cout; a.KH = j.KH; a.KW = j.KW;
-        a.ld_dy = j.ld_dy; a.S = j.S; a.dbg = 0; a.math = flags & 1; a.bp32 = 0; a.dys = a.xss = nullptr;
+        a.ld_dy = j.ld_dy; a.S = j.S; a.dbg = 0; a.math = f.math_bf16; a.bp32 = 0; a.dys = a.xss = nullptr;
         const int chunks = (j.M + 15) / 16;
         a.chunks_per_split = (chunks + j.S - 1) / j.S;
         g.begin[i] = total;
@@ -1385,10 +1389,10 @@ extern "C" int radet_conv2d_wgrad_group(const RadetWgradJob* jobs, int njobs, in
     g.begin[njobs] = total;
     hipStream_t st = (hipStream_t)stream;
     if (bm == 128) {
-        if (flags & 1) hipLaunchKernelGGL((conv_wgradg_group_kernel<128, 128, 2, 2, 1>), dim3(total), dim3(256), 0, st, g);
+        if (f.math_bf16) hipLaunchKernelGGL((conv_wgradg_group_kernel<128, 128, 2, 2, 1>), dim3(total), dim3(256), 0, st, g);
         else hipLaunchKernelGGL((conv_wgradg_group_kernel<128, 128, 2, 2, 0>), dim3(total), dim3(256), 0, st, g);
     } else {
-        if (flags & 1) hipLaunchKernelGGL((conv_wgradg_group_kernel<64, 64, 2, 2, 1>), dim3(total), dim3(256), 0, st, g);
+        if (f.math_bf16) hipLaunchKernelGGL((conv_wgradg_group_kernel<64, 64, 2, 2, 1>), dim3(total), dim3(256), 0, st, g);
         else hipLaunchKernelGGL((conv_wgradg_group_kernel<64, 64, 2, 2, 0>), dim3(total), dim3(256), 0, st, g);
     }
     return radet_check_launch();

@@ -12,8 +12,18 @@ static __device__ __attribute__((aligned(16))) float radet_zero_page[512];
 // k-quad q ^ swz(r), swz(r) = (r / (64 / BK)) % (BK / 4); the reader of k-quad kq looks in slot kq ^ swz(r).
 // Stage order per K step: issue the next stage's loads into the other buffer, then fragment reads (software
 // pipelined one 8-wide k slice ahead) + MFMAs on the current buffer, then vmcnt(0) + barrier.
-// TAG only changes the kernel's symbol name: TAG=1 marks the head-tower GEMM family (M = B*6400, N = 256,
-// K = 2304) so that rocprofv3 --stats reports it on its own line (bench.py's roofline kernel).
+// TAG selects the arithmetic / operand format (bits below; described where the kernel reads them).  TAG_SYMBOL only changes
+// the kernel's symbol name: it marks the head-tower GEMM family (M = B*6400, N = 256, K = 2304) so that rocprofv3 --stats
+// reports it on its own line (bench.py's roofline kernel).  The values are part of the mangled kernel symbols that profiles
+// are keyed by: they stay.
+constexpr int TAG_SYMBOL = 1;       // profiling symbol
+constexpr int TAG_BF16_MATH = 2;    // bf16 math mode
+constexpr int TAG_H16 = 4;          // bf16 storage
+constexpr int TAG_X3 = 8;           // fp32 tensors split into planes in registers
+constexpr int TAG_P3 = 16;          // operands arrive as planes
+constexpr int TAG_KDIV = 32;        // the waves divide the K step (with TAG_X3)
+constexpr int TAG_H2 = 64;          // fp16 hi / lo arithmetic (with TAG_X3 or TAG_P3)
+constexpr int TAG_PAIRS = 128;      // with TAG_P3: row-interleaved plane pairs; with TAG_KDIV: K-divided tile on plane pairs
 template <int BM, int BN, int WM, int WN, int TAG, int BK, int NSTG = 2, bool SK = false>
 __global__ __launch_bounds__(WM * WN * 64) void conv_igemmg_kernel(const ConvArgs a) {
     constexpr int NW = WM * WN;           // waves per workgroup: 4, or 8 (plane-operand tiles that own a whole CU's LDS)
@@ -23,48 +33,48 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemmg_kernel(const ConvArg
     constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
     constexpr int A_INSTR = BM / RPI, B_INSTR = BN / RPI;
     constexpr int A_PW = (A_INSTR + NW - 1) / NW, B_PW = (B_INSTR + NW - 1) / NW;
-    constexpr int NS = ((TAG & 128) && (TAG & 16)) ? 2 : BK / 8;   // K = 8-wide k slices per stage (row-interleaved pairs: two K = 16 slices of a 32-channel group)
-    constexpr bool BF16 = (TAG & 2) != 0;                     // TAG bit 0: profiling symbol, bit 1: bf16 math mode
-    constexpr bool H16 = (TAG & 4) != 0;                      // bit 2: bf16 storage (a 16-byte slot = 8 bf16 = one MFMA operand)
-    // bit 3: fp32 tensors, fp32-accurate products on the bf16 matrix cores: every operand is split into three bf16 planes
+    constexpr int NS = ((TAG & TAG_PAIRS) && (TAG & TAG_P3)) ? 2 : BK / 8;   // K = 8-wide k slices per stage (row-interleaved pairs: two K = 16 slices of a 32-channel group)
+    constexpr bool BF16 = (TAG & TAG_BF16_MATH) != 0;
+    constexpr bool H16 = (TAG & TAG_H16) != 0;                // (a 16-byte slot = 8 bf16 = one MFMA operand)
+    // TAG_X3: fp32 tensors, fp32-accurate products on the bf16 matrix cores: every operand is split into three bf16 planes
     // in registers and 6 of the 9 plane products (everything above 2^-24 relative) are accumulated by
     // v_mfma_f32_32x32x16_bf16, which retires 16x the MACs per cycle of v_mfma_f32_32x32x2_f32
-    constexpr bool X3 = (TAG & 8) != 0;
-    // bit 4: the operands ARRIVE as bf16 plane triples (x rows [3][Cin] bf16 = hi | mid | lo with hi + mid + lo == the fp32
+    constexpr bool X3 = (TAG & TAG_X3) != 0;
+    // TAG_P3: the operands ARRIVE as bf16 plane triples (x rows [3][Cin] bf16 = hi | mid | lo with hi + mid + lo == the fp32
     // value exactly, written once by the producer of the tensor; weights [Cout][taps][3][Cin]): the same 6 plane products as
     // X3, but no operand split anywhere in the K loop -- it is ds_read_b128 + v_mfma only.  Byte geometry per plane = the
     // bf16-storage path (K counted in channel pairs, a 16-byte LDS slot = 8 bf16 = one MFMA operand); outputs stay fp32
-    constexpr bool P3 = (TAG & 16) != 0;
-    // bit 6 (with bit 3, bits 3 + 5, or bit 4): fp16 hi / lo arithmetic (common.h "h2") -- two fp16 planes per operand
+    constexpr bool P3 = (TAG & TAG_P3) != 0;
+    // TAG_H2 (with TAG_X3, TAG_X3 + TAG_KDIV, or TAG_P3): fp16 hi / lo arithmetic (common.h "h2") -- two fp16 planes per operand
     // instead of three bf16 ones, 3 v_mfma_f32_32x32x16_f16 per K = 16 step into an accumulator PAIR (hi hi' | hi lo' + lo hi')
     // instead of 6 bf16 MFMAs into one; operands scaled by the exact power of two their amax slots give (ConvPtrs::xs / ws),
-    // pair combined and un-scaled right behind the K loop.  With bit 4 the planes arrive as fp16 pairs: rows of 32-channel
+    // pair combined and un-scaled right behind the K loop.  With TAG_P3 the planes arrive as fp16 pairs: rows of 32-channel
     // groups [hi x 32 | lo x 32], 4 bytes per element.
-    constexpr bool H2 = (TAG & 64) != 0;
-    static_assert(!H2 || X3 || P3, "fp16 hi / lo arithmetic: in-register split (bit 3) or plane pairs (bit 4)");
-    // bit 7 with bit 4 (round 6): ROW-INTERLEAVED plane pairs.  A stage of the plane-pair tiles is one 32-channel group = 128
+    constexpr bool H2 = (TAG & TAG_H2) != 0;
+    static_assert(!H2 || X3 || P3, "fp16 hi / lo arithmetic: in-register split (TAG_X3) or plane pairs (TAG_P3)");
+    // TAG_PAIRS with TAG_P3 (round 6): ROW-INTERLEAVED plane pairs.  A stage of the plane-pair tiles is one 32-channel group = 128
     // contiguous bytes [hi x 32 | lo x 32] of every tile row; fetched plane by plane (two 64-byte pieces per row in two wave
     // loads) the global -> LDS path runs at its 64-byte-chunk rate, 52-55 GB/s per CU for one 8-wave workgroup per CU, against
     // 73-84 GB/s for 128-byte chunks (profiles/round3_fill_probe.txt) -- and the tower GEMM's 48 KiB per stage at 52 GB/s are
     // 0.92 us next to 0.66 us of MFMA issue.  With this bit a wave load fetches 8 rows x 128 bytes (both planes of a row in
     // one line-sized piece): the loaders and LDS images are those of an fp32 tile with a 32-deep K step (BK = 32: 128-byte
     // rows, 8 swizzled 16-byte slots), the reader takes slots 2 s + lh (hi) and 4 + 2 s + lh (lo) of K = 16 slice s
-    constexpr bool RI = P3 && (TAG & 128) != 0;
+    constexpr bool RI = P3 && (TAG & TAG_PAIRS) != 0;
     static_assert(!RI || (H2 && BK == 32), "row-interleaved pairs: fp16 hi / lo planes, 128-byte tile rows");
     constexpr int NPLC = P3 ? (H2 ? 2 : 3) : 1;              // planes of an operand (compute side)
     constexpr int NPL = RI ? 1 : NPLC;                       // plane tiles per LDS stage / loads per row (loader side)
-    // bit 5 (with bit 3): the waves divide the K step as well as the tile.  A stage of BK = 16 KD channels is cut into KD
+    // TAG_KDIV (with TAG_X3): the waves divide the K step as well as the tile.  A stage of BK = 16 KD channels is cut into KD
     // k-groups; wave (kg, nh) accumulates ALL BM rows x its BN / WNK columns over k-group kg, and the KD partial tiles of a
     // column group are added through LDS after the K loop.  A wave's operand splits (VALU work) and fragment reads (LDS
     // bandwidth) then serve TMA x TNA accumulator blocks instead of one: (TMA + TNA) splits per 6 TMA TNA MFMAs -- for the
     // 64 x 64 tile 1 split per 6 MFMAs with KD = 4 (2 x 2 blocks per wave) or 1.5 with KD = 2 (2 x 1), against 2 for the
     // 2 x 2-wave tile whose waves each split one A and one B fragment per 6 MFMAs
-    constexpr bool KW = (TAG & 32) != 0;
-    // bit 7 (with bits 3 + 5 + 6, round 6): K-divided tile on fp16 plane PAIRS.  A pair row is as long as the fp32 row (4 bytes
+    constexpr bool KW = (TAG & TAG_KDIV) != 0;
+    // TAG_PAIRS (with TAG_X3 + TAG_KDIV + TAG_H2, round 6): K-divided tile on fp16 plane PAIRS.  A pair row is as long as the fp32 row (4 bytes
     // per channel: 32-channel groups [hi x 32 | lo x 32]), so a 64-channel stage is the same 256 contiguous bytes per tile row and
     // the fp32 loaders / LDS images are used unchanged; only the reader differs -- wave kg takes the hi and the lo 16-byte slot of
     // ITS 16 channels (group kg / 2, half kg % 2) straight into the MFMA: no operand split, the same two ds_read_b128 per block
-    constexpr bool PQ = (TAG & 128) != 0 && (TAG & 32) != 0;    // (bit 7 with bit 4 instead of bit 5: row-interleaved pairs, below)
+    constexpr bool PQ = (TAG & TAG_PAIRS) != 0 && (TAG & TAG_KDIV) != 0;    // (with TAG_P3 instead of TAG_KDIV: row-interleaved pairs, RI)
     static_assert(!PQ || (KW && H2 && BK == 64), "pair operands in the K-divided tile: 64-channel stages");
     constexpr int KD = KW ? BK / 16 : 1;                                  // k-groups per stage
     constexpr int WNK = NW / KD;                                          // column groups of waves
@@ -118,7 +128,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemmg_kernel(const ConvArg
     // HERE, in front of everything, and reduced behind the prologue's wait for the first tiles -- every launch starts on cold
     // L2s, and a reduction in this place kept the tile loads of each workgroup waiting for the slot's round trip (1.5-2.5 us)
     unsigned raw_xs = 0u, raw_ws = 0u;
-    if constexpr ((TAG & 64) != 0) { raw_xs = h2_scale_load(P.xs); raw_ws = h2_scale_load(P.ws); }
+    if constexpr ((TAG & TAG_H2) != 0) { raw_xs = h2_scale_load(P.xs); raw_ws = h2_scale_load(P.ws); }
     PairScaleRaw raw_q = {0u, 0u, 0u, 0u};
     const bool pair_copy = P.yq != nullptr;                      // (uniform)
     if (pair_copy) raw_q = igemm_pair_scale_load(P);

@@ -931,19 +931,18 @@ __global__ __launch_bounds__(256) void conv_wgradq_kernel(const WgradArgs a) {
         }
 }
 
-// the h2 weight-gradient launches behind radet_conv2d_wgrad_s: flags 0x1000 (fp32 tensors, split in registers: the one-tap
-// tiles; bits 4-5 / 7 / 10-11 select tile / 32-pixel stages / pixel-divided tiles as for the bf16-plane arithmetic) or
-// 0x1000 | 0x200 (fp16 plane pairs: the all-taps kernel above)
-int radet_launch_wgrad_h2(const WgradArgs& a, int flags, int bm, int bn, hipStream_t st) {
-    if (flags & 0x200) {
+// the h2 weight-gradient launches behind radet_conv2d_wgrad_s (f.h2): fp32 tensors split in registers (the one-tap tiles
+// bm x bn; px32 / kdiv4 / kdiv2 as for the bf16-plane arithmetic) or, with f.p3, fp16 plane pairs (the all-taps kernels above)
+int radet_launch_wgrad_h2(const WgradArgs& a, const WgradFlags& f, int bm, int bn, hipStream_t st) {
+    if (f.p3) {
         if ((a.ld_dy & 31) || (a.Cin & 31)) return RADET_ERR_ARG;
-        if (a.KH == 3 && a.KW == 3 && !(flags & 0x40)) {               // all nine taps per workgroup
+        if (a.KH == 3 && a.KW == 3 && !f.one_tap) {               // all nine taps per workgroup
             const int tiles9 = ((a.Cout + 127) / 128) * (a.Cin / 32) * a.S;
-            if ((flags & 0x2000) && a.chunks_per_split * 16 <= RADET_W9D_TCAP) {      // unit stride, padding 1: deep pipeline, table in LDS
+            if (f.deep && a.chunks_per_split * 16 <= RADET_W9D_TCAP) {      // unit stride, padding 1: deep pipeline, table in LDS
                 hipLaunchKernelGGL(conv_wgrad9d_kernel<5>, dim3(tiles9), dim3(512), 0, st, a);
                 return radet_check_launch();
             }
-            if (flags & 0x4000) {                                        // (experiment) unit stride, padding 1: x as shifted windows
+            if (f.windows) {                        // (experiment) unit stride, padding 1: x as shifted windows
                 hipLaunchKernelGGL(conv_wgrad9r_kernel<2>, dim3(tiles9), dim3(512), 0, st, a);
                 return radet_check_launch();
             }
@@ -958,9 +957,9 @@ int radet_launch_wgrad_h2(const WgradArgs& a, int flags, int bm, int bn, hipStre
             else hipLaunchKernelGGL((conv_wgrad9q_kernel<2, false>), dim3(tiles9), dim3(512), 0, st, a);
             return radet_check_launch();
         }
-        // one tap per workgroup (0x40, or not a 3 x 3): bits 4-5 = 1: 128 x 128 tile, otherwise 64 x 64
+        // one tap per workgroup (one_tap, or not a 3 x 3): tile 1 = 128 x 128, otherwise 64 x 64
         const int KTq = a.KH * a.KW;
-        if (((flags >> 4) & 3) == 1) {
+        if (f.tile == 1) {
             const int tiles = ((a.Cout + 127) / 128) * ((a.Cin + 127) / 128) * KTq * a.S;
             hipLaunchKernelGGL((conv_wgradq_kernel<128, 128, 2, 2>), dim3(tiles), dim3(256), 0, st, a);
         } else {
@@ -973,9 +972,9 @@ int radet_launch_wgrad_h2(const WgradArgs& a, int flags, int bm, int bn, hipStre
     // experiment (RADET_WGRAD_LDS_PAD = bytes of unused dynamic LDS per workgroup): fewer weight-gradient workgroups fit a CU,
     // so the dgrad chain's workgroups find LDS there -- see DESIGN.md 7 for what it measured
     static const int pad = getenv("RADET_WGRAD_LDS_PAD") ? atoi(getenv("RADET_WGRAD_LDS_PAD")) : 0;
-    if (bm == 64 && (flags & 0xC00)) {
+    if (bm == 64 && (f.kdiv4 || f.kdiv2)) {
         const int tiles = ((a.Cout + 63) / 64) * ((a.Cin + 63) / 64) * KT * a.S;
-        if (flags & 0x400) hipLaunchKernelGGL((conv_wgradg_kernel<64, 64, 2, 2, 3, 64, 4>), dim3(tiles), dim3(256), pad, st, a);
+        if (f.kdiv4) hipLaunchKernelGGL((conv_wgradg_kernel<64, 64, 2, 2, 3, 64, 4>), dim3(tiles), dim3(256), pad, st, a);
         else hipLaunchKernelGGL((conv_wgradg_kernel<64, 64, 2, 2, 3, 32, 2>), dim3(tiles), dim3(256), pad, st, a);
         return radet_check_launch();
     }

@@ -143,14 +143,14 @@ class Engine:
     # ------------------------------------------------------------------ profiling hook
     # own kernel symbol for the head-tower GEMM family (see conv_igemm.hip) + its measured-best tile:
     # 64x64 block tile with a 32-deep K step (bench_conv.py: 98.7 vs 88.8 TFLOP/s for the heuristic pick)
-    TOWER_TAG = 0x100 | 0x200 | 3        # backward: 64 x 64 tile, K step 32
-    TOWER_TAG_FWD = 0x100 | 0x200 | 2    # forward: 128 x 64 tile (2 accumulators per wave), K step 32
+    TOWER_TAG = K.SYMBOL | K.BK32 | 3        # backward: 64 x 64 tile, K step 32
+    TOWER_TAG_FWD = K.SYMBOL | K.BK32 | 2    # forward: 128 x 64 tile (2 accumulators per wave), K step 32
 
     # plane-operand tower tiles with three LDS stages (144 KiB; experiment switch)
     tower_stages = K.STAGES3 if os.environ.get("RADET_TOWER_STAGES3", "0") == "1" else 0
     tower_tile = int(os.environ.get("RADET_TOWER_TILE", "6"))       # 6: 256 x 128 (one workgroup per CU), 5: 128 x 128 (two)
-    if os.environ.get("RADET_TOWER_ROWPAIRS", "0") == "1":          # (K.ROWPAIRS: 128-byte pieces, both planes of a row per load)
-        tower_tile |= 0x80000
+    if os.environ.get("RADET_TOWER_ROWPAIRS", "0") == "1":          # (128-byte pieces, both planes of a row per load)
+        tower_tile |= K.ROWPAIRS
 
     def _ttile(self, c, bwd=False, tag=True, pair=True):
         """tile_override of a tower conv launch + profiling tag.  Forward: a fixed, measured tile with a 32-deep K step
@@ -164,24 +164,24 @@ class Engine:
         if self.p3:
             # plane operands: 256 x 128 tiles, 8 waves (one workgroup per CU owns its LDS: 2 x 72 KiB of stages) for the
             # grouped cls + reg launches, 128 x 128 / 8 waves for a single tower GEMM (tools/bench_p3.py)
-            return (6 if pair else 5) | (0x100 if tag else 0) | self.tower_stages
+            return (6 if pair else 5) | (K.SYMBOL if tag else 0) | self.tower_stages
         if fp32 and self.x3:
             # products from bf16 planes: the operand split is VALU work per fragment, so the tile with the most MFMAs per
             # fragment wins -- 128 x 128 (4 accumulators per wave), 2 LDS stages, forward (178 vs 158 TFLOP/s fp32-equivalent
             # for 128 x 64) and backward (-0.15 ms per step)
-            t = 0x200 | 1
+            t = K.BK32 | 1
         elif bwd:
-            t = (self.TOWER_TAG & ~0x100) if fp32 else (self.tower_bwd_tile_h16 or c.geom.bwd_tile)
+            t = (self.TOWER_TAG & ~K.SYMBOL) if fp32 else (self.tower_bwd_tile_h16 or c.geom.bwd_tile)
         else:
-            t = (self.TOWER_TAG_FWD & ~0x100) | (K.STAGES3 if fp32 else 0)
+            t = (self.TOWER_TAG_FWD & ~K.SYMBOL) | (K.STAGES3 if fp32 else 0)
             if not fp32 and self.tower_fwd_tile_h16:
                 t = self.tower_fwd_tile_h16
-        return t | (0x100 if tag else 0)
+        return t | (K.SYMBOL if tag else 0)
     tower_fwd_tile_h16 = int(os.environ.get("RADET_TOWER_FWD_TILE", "0"), 0)     # bf16 modes: tower forward tile (0: 128 x 64, K step 32)
     # bf16 modes: tower dgrad tile.  The tuner times a launch ALONE and picks 64 x 64 / K step 16 for M = 25 600, K = 2304; in the
     # step the two towers' dgrads run next to each other and to the weight gradients, where 128 x 128 / K step 32 is the faster
-    # one: bf16-storage step 5.35 -> 5.11 ms (round 6, same box: 0x203 5.24, 0x202 5.18, 0x1 5.16).  0: the tuner's pick
-    tower_bwd_tile_h16 = int(os.environ.get("RADET_TOWER_BWD_TILE", "0x201"), 0)
+    # one: bf16-storage step 5.35 -> 5.11 ms (round 6, same box: 64 x 64 / K step 32 5.24, 128 x 64 / 32 5.18, 128 x 128 / 16 5.16).  0: the tuner's pick
+    tower_bwd_tile_h16 = int(os.environ.get("RADET_TOWER_BWD_TILE", str(K.BK32 | 1)), 0)
     tower_events = None  # when a list: (start, end) torch.cuda.Event pairs around every tower GEMM launch
     _pfx_ready = None    # (image key, buffer set, event) of a frozen prefix computed ahead of its step (prefetch_prefix)
 
@@ -542,7 +542,7 @@ class Engine:
                     K.autotune_wgrad(c.geom)
         for c in self.convs:                  # backbone / neck weight gradients on plane pairs: the one-tap pair kernel with the
             if c.geom is not None and hasattr(c.geom, "wgrad_pair_flags") and c not in self.cls_tower + self.reg_tower:
-                c.geom.wgrad_pair_flags = 0x40 | (c.geom.wgrad_flags & 0x30)        # tuned tile class (128 x 128, else 64 x 64)
+                c.geom.wgrad_pair_flags = K.WG_ONE_TAP | (c.geom.wgrad_flags & K.WG_TILE_MASK)        # tuned tile class (128 x 128, else 64 x 64)
         # wgrad slabs / bias partials + descriptor table
         n_slab = sum(c.geom.nsplit * c.wsize for c in self.convs if c.trainable)
         n_bp = sum(c.geom.nsplit * c.cout for c in self.convs if c.trainable)
@@ -1111,7 +1111,7 @@ class Engine:
         b, p = self.buf, self.p
         c = tower[i]
         z, y = b[f"{t}.z{i}"], b[f"{t}.y{i}"]
-        self._tower_launch(K.conv_fwd, c.geom, x, c.wf, None, z, tile=self.tower_tile | 0x100 | (1 << 12) | self.tower_stages)
+        self._tower_launch(K.conv_fwd, c.geom, x, c.wf, None, z, tile=self.tower_tile | K.SYMBOL | K.splitk(1) | self.tower_stages)
         gn = f"bbox_head.{t}_convs.{i}.gn"
         pl = K._isp(y)                  # the last layer's output feeds the predictor convs: fp32
         if self.h2:
@@ -1349,7 +1349,7 @@ class Engine:
                 x = b[f"{t}.y{i - 1}"] if i > 0 else b["Pp"]
                 wg_done[(t, i)] = self._wgrad_async(tower[i].geom, b[f"{t}.dz{i & 1}"], x, tower[i].slabs, None)
                 if i > 0:
-                    K.conv_dgrad(tower[i].geom, b[f"{t}.dz{i & 1}"], tower[i].wft, b[f"{t}.dy"], tile=self.tower_tile | (1 << 12))
+                    K.conv_dgrad(tower[i].geom, b[f"{t}.dz{i & 1}"], tower[i].wft, b[f"{t}.dy"], tile=self.tower_tile | K.splitk(1))
             self._tower_bwd_head_async("cls")
             self._fork(cs)
             with torch.cuda.stream(cs):
@@ -1359,10 +1359,10 @@ class Engine:
                 with torch.cuda.stream(cs):
                     layer("reg", self.reg_tower, self.gn_ws2, i)
             # both first layers write dL/dP: cls on this stream, then reg accumulates onto it on the chain stream
-            K.conv_dgrad(self.cls_tower[0].geom, b["cls.dz0"], self.cls_tower[0].wft, dP, tile=self.tower_tile | (1 << 12))
+            K.conv_dgrad(self.cls_tower[0].geom, b["cls.dz0"], self.cls_tower[0].wft, dP, tile=self.tower_tile | K.splitk(1))
             self._fork(cs)
             with torch.cuda.stream(cs):
-                K.conv_dgrad(self.reg_tower[0].geom, b["reg.dz0"], self.reg_tower[0].wft, dP, addend=dP, tile=self.tower_tile | (1 << 12))
+                K.conv_dgrad(self.reg_tower[0].geom, b["reg.dz0"], self.reg_tower[0].wft, dP, addend=dP, tile=self.tower_tile | K.splitk(1))
             self._join(cs)
         elif self.tower_mode in ("pair", "pairbwd"):
             p, g = self.p, self.g

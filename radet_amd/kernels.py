@@ -7,6 +7,64 @@ import torch
 
 from . import _lib
 
+# ---------------------------------------------------------------------- launch flag words
+# The two packed integers that steer a conv launch, defined in include/radet_hip.h: RADET_TILE_<N> is <N> here, RADET_WGRAD_<N>
+# is WG_<N>; TAG_<N> are the bits of conv_igemmg_kernel's template argument (csrc/conv_igemm_kernel.h).  tests/test_host.py
+# holds the two sides together.  The same number means different things in the two words: use the names.
+# tile_override of radet_conv2d_igemm*:
+ID_MASK = 0xFF                            # block tile, TILE_SHAPE below (0: launcher heuristic)
+SYMBOL = 0x100                            # tagged kernel symbol (profiling)
+BK32 = 0x200                              # K step 32 instead of 16 channels (no meaning with P3)
+MATH_BF16 = 0x400                         # bf16 math: fp32 tensors, operands rounded to bf16 in front of the matrix core
+STORE_BF16, OUT_F32 = 0x800, 0x10000      # bf16 tensors in HBM / fp32 output from bf16 inputs (predictor heads)
+SPLITK, SPLITK_MASK = 0x1000, 0xF000      # * n (1..15): forced split-K factor, splitk(n)
+STAGES3 = 0x20000                         # 3 LDS stages in the fp32 implicit-GEMM kernel (forward launches)
+STAGES4 = 0x40000                         # 4 LDS stages (fp16 hi / lo arithmetic, K-divided tile 8)
+ROWPAIRS = 0x80000                        # plane-pair operands, 8-wave tiles: both planes of a tile row in one 128-byte piece per load
+STREAMK, STREAMK_MASK = 0x100000, 0x700000    # * w (1..7): stream-K schedule with w persistent workgroups per CU (fp32 tags), streamk(w)
+X3 = 0x1000000                            # fp32 tensors, products from three bf16 planes per operand on the bf16 matrix cores
+P3 = 0x2000000                            # x / w arrive as plane tensors (bf16 triples, or fp16 pairs with H2); fp32 outputs
+H2 = 0x8000000                            # fp16 hi / lo arithmetic (with X3 or P3): 3 f16 MFMAs per K = 16 step, needs amax slots
+MASKQ = 0x10000000                        # the launch's ReLU mask tensor is an fp16 plane-pair tensor (round 6: pairs-only activations)
+# flags of radet_conv2d_wgrad*:
+WG_MATH_BF16, WG_STORE_BF16 = 0x1, 0x2    # bf16 math / dy and x are bf16 tensors
+WG_TILE, WG_TILE_MASK = 0x10, 0x30        # * t: tile of the one-tap kernel, WG_TILE_SHAPE below (0: the launcher's choice)
+WG_ONE_TAP = 0x40                         # never the all-taps kernel
+WG_PX32 = 0x80                            # 32 instead of 16 pixels per LDS stage
+WG_X3 = 0x100                             # fp32 products from three bf16 planes per operand
+WG_P3 = 0x200                             # dy / x arrive as plane tensors
+WG_KDIV4, WG_KDIV2 = 0x400, 0x800         # 64 x 64 tile: the waves divide a 64-pixel stage four ways / a 32-pixel stage two ways
+WG_H2 = 0x1000                            # fp16 hi / lo arithmetic
+WG_DEEP, WG_WINDOWS = 0x2000, 0x4000      # all-taps pair kernel: conv_wgrad9d_kernel / conv_wgrad9r_kernel (experiments)
+# template argument TAG of conv_igemmg_kernel:
+TAG_SYMBOL, TAG_BF16_MATH, TAG_H16, TAG_X3, TAG_P3, TAG_KDIV, TAG_H2, TAG_PAIRS = 1, 2, 4, 8, 16, 32, 64, 128
+# ---------------------------------------------------------------------- end of the launch flag words
+
+TILE_SHAPE = {1: (128, 128), 2: (128, 64), 3: (64, 64), 4: (128, 32), 5: (128, 128), 6: (256, 128), 7: (64, 64), 8: (64, 64)}   # rows x Cout
+WG_TILE_SHAPE = {1: (128, 128), 2: (64, 64), 3: (128, 64)}                                                                   # Cout x Cin
+
+
+def splitk(n):
+    return n * SPLITK
+
+
+def streamk(w):
+    return w * STREAMK
+
+
+def tile_id(t):
+    return t & ID_MASK
+
+
+def with_tile(t, tid):
+    """t with block tile tid and no forced split-K factor (which belonged to the tile it replaces)"""
+    return (t & ~(ID_MASK | SPLITK_MASK)) | tid
+
+
+def wg_tile(flags):
+    return (flags & WG_TILE_MASK) // WG_TILE
+
+
 
 def _ptr(t):
     """device address of a contiguous device tensor (None -> NULL) as a plain int: ctypes converts it per the argtypes.
@@ -123,35 +181,36 @@ _TILES = {1: "128, 128, 2, 2", 2: "128, 64, 2, 2", 3: "64, 64, 2, 2", 4: "128, 3
 
 def _igemm_key(t, x):
     """kernel symbol an implicit-GEMM launch with tile_override word t dispatches to (conv_igemm.hip: igemm_impl)"""
-    tid = t & 0xFF
+    tid = tile_id(t)
     if tid == 0:
         return "conv_igemmg_kernel<launcher heuristic>"
+    sym = TAG_SYMBOL if t & SYMBOL else 0
     if t & H2 and (t & P3 or t & X3):
         if t & P3 and tid == 7:                 # K-divided 64 x 64 tile on plane pairs (round 6)
-            return "conv_igemmg_kernel<64, 64, 2, 2, 232, 64, 2, false>"
+            return f"conv_igemmg_kernel<64, 64, 2, 2, {TAG_X3 | TAG_KDIV | TAG_H2 | TAG_PAIRS}, 64, 2, false>"
         if t & P3 and t & ROWPAIRS and tid in (5, 6):
-            return f"conv_igemmg_kernel<{_TILES[tid]}, {208 | ((t >> 8) & 1)}, 32, 2, false>"
+            return f"conv_igemmg_kernel<{_TILES[tid]}, {TAG_P3 | TAG_H2 | TAG_PAIRS | sym}, 32, 2, false>"
         if t & P3:
-            tag, bk = 80 | ((t >> 8) & 1), 16
+            tag, bk = TAG_P3 | TAG_H2 | sym, 16
         else:
-            tag, bk = 72 | ((t >> 8) & 1), 32
+            tag, bk = TAG_X3 | TAG_H2 | sym, 32
             if tid >= 7:
                 nst = 2 if tid == 7 else (4 if t & STAGES4 else (3 if t & STAGES3 else 2))
-                return f"conv_igemmg_kernel<{_TILES[tid]}, {(tag | 32) & ~1}, {64 if tid == 7 else 32}, {nst}, false>"
+                return f"conv_igemmg_kernel<{_TILES[tid]}, {TAG_X3 | TAG_H2 | TAG_KDIV}, {64 if tid == 7 else 32}, {nst}, false>"
         return f"conv_igemmg_kernel<{_TILES.get(tid, '?')}, {tag}, {bk}, {3 if t & STAGES3 else 2}, false>"
     if t & P3:
-        tag, bk = 16 | ((t >> 8) & 1), 16
+        tag, bk = TAG_P3 | sym, 16
     elif t & STORE_BF16:
-        tag, bk = 4 | ((t >> 8) & 1), 32 if t & 0x200 else 16
+        tag, bk = TAG_H16 | sym, 32 if t & BK32 else 16
     elif t & X3:
-        tag, bk = 8 | ((t >> 8) & 1), 32
+        tag, bk = TAG_X3 | sym, 32
         if tid >= 7:                        # K-divided 64 x 64 tiles: 7 = four k-groups of a 64-channel stage,
-            tag, bk = tag | 32, 64 if tid == 7 else 32          # 8 = two k-groups x two column halves of 32 channels
+            tag, bk = tag | TAG_KDIV, 64 if tid == 7 else 32    # 8 = two k-groups x two column halves of 32 channels
             return f"conv_igemmg_kernel<{_TILES[tid]}, {tag}, {bk}, 2, false>"
     else:
-        tag, bk = ((t >> 8) & 1) | (2 if t & MATH_BF16 else 0), 32 if t & 0x200 else 16
-    skw = (t >> 20) & 7
-    stages = 3 if (t & STAGES3) and (tag < 2 or tag & 24) and not skw else 2
+        tag, bk = sym | (TAG_BF16_MATH if t & MATH_BF16 else 0), 32 if t & BK32 else 16
+    skw = (t & STREAMK_MASK) // STREAMK
+    stages = 3 if (t & STAGES3) and (tag <= TAG_SYMBOL or tag & (TAG_X3 | TAG_P3)) and not skw else 2
     return f"conv_igemmg_kernel<{_TILES.get(tid, '?')}, {tag}, {bk}, {stages}, {'true' if skw and tag == 0 else 'false'}>"
 
 
@@ -225,7 +284,7 @@ class ConvGeom:
         self.pairs = False                    # forward launches read x as plane pairs written by its producer (fwd_tile_q)
         self.fwd_tile_q = 0
         self.bwd_tile_q = 0                   # dgrad launches whose dy arrives as plane pairs (pairs-only gradients, round 6)
-        self.wgrad_pair_flags = 0             # weight gradient on fp16 plane pairs: 0x40 one-tap kernel, bits 4-5 its tile (1: 128 x 128)
+        self.wgrad_pair_flags = 0             # weight gradient on fp16 plane pairs: WG_ONE_TAP = one-tap kernel, WG_TILE its tile (1: 128 x 128)
         self.nsplit_pairs = 0                 # its pixel splits (0: nsplit)
         self._ft = self._bt = self._classes = None
         self._cgroup = 0                                   # 0 = not looked at yet, None = no class launch for this geometry
@@ -452,6 +511,16 @@ TUNE_REPS = int(os.environ.get("RADET_TUNE_REPS", "3"))      # timed samples per
 TUNE_BURST = max(1, int(os.environ.get("RADET_TUNE_BURST", "4")))
 
 
+def _ntiles(t, m, n):
+    bm, bn = TILE_SHAPE[tile_id(t)]
+    return -(-m // bm) * -(-n // bn)
+
+
+def _splitk_cands(t, m, n, nk):
+    """short grids: t with explicit split-K factors (that leave >= 4 of its nk K stages per split) instead of the launcher's heuristic"""
+    return [t | splitk(sk) for sk in (1, 2, 3, 4, 5, 6, 8) if nk // sk >= 4] if _ntiles(t, m, n) < 1024 else []
+
+
 def autotune(g, need_dgrad=True, reps=None):
     """Pick the fastest (block tile, K step) of the implicit-GEMM kernel for this geometry by timing the
     candidates once (results cached per shape, so identical layers and identical models agree)."""
@@ -480,8 +549,7 @@ def autotune(g, need_dgrad=True, reps=None):
         tiles = [4] if n <= 32 else [1, 2, 3]
         c = [t for t in tiles]
         if kdim % 32 == 0:
-            c += [t | 0x200 for t in tiles]
-        # short grids: also try explicit split-K factors (bits 12-15) instead of the launcher's heuristic
+            c += [t | BK32 for t in tiles]
         if getattr(g, "x3", False) and not g.math and not g.h16 and n > 32:
             # K-divided 64 x 64 tiles (the waves share the operand splits): K steps of 64 / 32 channels
             c += ([7] if kdim % 64 == 0 else []) + ([8] if kdim % 32 == 0 else [])
@@ -490,15 +558,12 @@ def autotune(g, need_dgrad=True, reps=None):
                 c += [8 | STAGES3, 8 | STAGES4]
         out = list(c)
         for t in c:
-            bm = 64 if (t & 0xFF) in (3, 7, 8) else 128
-            bn = {1: 128, 2: 64, 3: 64, 4: 32, 7: 64, 8: 64}[t & 0xFF]
-            ntiles = -(-m // bm) * -(-n // bn)
-            nk = taps * kdim // (64 if (t & 0xFF) == 7 else (32 if (t & 0x200 or (t & 0xFF) == 8) else 16))
-            if ntiles < 1024:
-                out += [t | (sk << 12) for sk in (1, 2, 3, 4, 5, 6, 8) if nk // sk >= 4]
-                # stream-K (fp32 tensors, fp32 / bf16-rounded math is decided by the launcher's tag: fp32 only)
-                if not g.math and not g.h16 and (t & 0xFF) in (2, 3, 4) and ntiles % 256:      # (not the K-divided tiles)
-                    out += [t | (w * STREAMK) for w in (1, 2, 3, 4) if ntiles * nk >= 256 * w]
+            ntiles = _ntiles(t, m, n)
+            nk = taps * kdim // (64 if tile_id(t) == 7 else (32 if (t & BK32 or tile_id(t) == 8) else 16))
+            out += _splitk_cands(t, m, n, nk)
+            # stream-K (fp32 tensors, fp32 / bf16-rounded math is decided by the launcher's tag: fp32 only)
+            if ntiles < 1024 and not g.math and not g.h16 and tile_id(t) in (2, 3, 4) and ntiles % 256:      # (not the K-divided tiles)
+                out += [t | streamk(w) for w in (1, 2, 3, 4) if ntiles * nk >= 256 * w]
         return out
 
     global _TUNE_DIRTY, TUNE_RUNS
@@ -512,8 +577,8 @@ def autotune(g, need_dgrad=True, reps=None):
         y = torch.empty(g.lout.rows, g.cout, device=dev, dtype=dt)
         tmp_keys = _tune_slots(g, x, w, outputs=(y,))
         fc = cands(g.cin, g.cout, g.lout.rows, g.k * g.k)
-        if not g.math and not g.h16:      # forward launches run alone on the device: 3 LDS stages may pay (0x20000)
-            fc = fc + [t | STAGES3 for t in fc if (t & 0xFF) < 7 and not t & (STAGES3 | STAGES4)]
+        if not g.math and not g.h16:      # forward launches run alone on the device: 3 LDS stages may pay
+            fc = fc + [t | STAGES3 for t in fc if tile_id(t) < 7 and not t & (STAGES3 | STAGES4)]
         ft = best_of(lambda t: conv_fwd(g, x, w, None, y, relu=True, tile=t), fc)
         bt = 0
         if need_dgrad and g.cout % 16 == 0:
@@ -539,12 +604,7 @@ def autotune(g, need_dgrad=True, reps=None):
             y = torch.empty(g.lout.rows, g.cout, device=dev)
             cq = [1, 2, 3, 1 | STAGES3, 2 | STAGES3, 3 | STAGES3] + ([7] if g.cin % 64 == 0 else [])
             for t in list(cq):
-                bm = 64 if (t & 0xFF) in (3, 7) else 128
-                bn = {1: 128, 2: 64, 3: 64, 7: 64}[t & 0xFF]
-                ntiles = -(-g.lout.rows // bm) * -(-g.cout // bn)
-                nk = g.k * g.k * g.cin // (64 if (t & 0xFF) == 7 else 32)
-                if ntiles < 1024:
-                    cq += [t | (sk << 12) for sk in (1, 2, 3, 4, 5, 6, 8) if nk // sk >= 4]
+                cq += _splitk_cands(t, g.lout.rows, g.cout, g.k * g.k * g.cin // (64 if tile_id(t) == 7 else 32))
             ftq = best_of(lambda t: conv_fwd(g, xq, wq, None, y, relu=True, tile=t), cq)
             btq = 0
             if need_dgrad and g.stride == 1 and g.cout % 32 == 0:
@@ -555,12 +615,7 @@ def autotune(g, need_dgrad=True, reps=None):
                 tmp_q = _tune_slots(g, outputs=(dx,))
                 cb = [1, 2, 3] + ([7] if g.cout % 64 == 0 else [])
                 for t in list(cb):
-                    bm = 64 if (t & 0xFF) in (3, 7) else 128
-                    bn = {1: 128, 2: 64, 3: 64, 7: 64}[t & 0xFF]
-                    ntiles = -(-g.lin.rows // bm) * -(-g.cin // bn)
-                    nk = g.k * g.k * g.cout // (64 if (t & 0xFF) == 7 else 32)
-                    if ntiles < 1024:
-                        cb += [t | (sk << 12) for sk in (1, 2, 3, 4, 5, 6, 8) if nk // sk >= 4]
+                    cb += _splitk_cands(t, g.lin.rows, g.cin, g.k * g.k * g.cout // (64 if tile_id(t) == 7 else 32))
                 btq = best_of(lambda t: conv_dgrad(g, dyq, wtq, dx, mask=xq, tile=t), cb)
                 unregister_amax(tmp_q)
             _TUNE_CACHE[keyq] = (ftq, btq)
@@ -594,23 +649,6 @@ def _tune_slots(g, *tensors, outputs=()):
             t.zero_()                               # (an uninitialised output may hold NaN bit patterns: they must not be read back)
             keys.append(register_amax(t, new_amax(t.device)))
     return keys
-
-
-MATH_BF16 = 0x400      # tile_override bit of the implicit-GEMM entry points
-
-
-STAGES3 = 0x20000                         # 3 LDS stages in the fp32 implicit-GEMM kernel (forward launches)
-STAGES4 = 0x40000                         # 4 LDS stages (fp16 hi / lo arithmetic, K-divided tile 8)
-X3 = 0x1000000                            # fp32 tensors, products from three bf16 planes per operand on the bf16 matrix cores
-STREAMK = 0x100000                        # * w (1..7): stream-K schedule with w persistent workgroups per CU (fp32 tags)
-STORE_BF16, OUT_F32 = 0x800, 0x10000      # bf16 tensors in HBM / fp32 output from bf16 inputs (predictor heads)
-
-
-P3 = 0x2000000                            # x / w arrive as plane tensors (bf16 triples, or fp16 pairs with H2); fp32 outputs
-P3_BK8 = 0x4000000                        # ... with a K step of 16 instead of 32 channels
-H2 = 0x8000000                            # fp16 hi / lo arithmetic (with X3 or P3): 3 f16 MFMAs per K = 16 step, needs amax slots
-ROWPAIRS = 0x80000                        # plane-pair operands, 8-wave tiles: both planes of a tile row in one 128-byte piece per load
-MASKQ = 0x10000000                        # the launch's ReLU mask tensor is an fp16 plane-pair tensor (round 6: pairs-only activations)
 
 
 # ---------------------------------------------------------------------- amax slots (fp16 hi / lo arithmetic, radet_hip.h)
@@ -802,10 +840,10 @@ def _is16(t):
 def _tile(g, tile, default, x=None, y=None):
     """tile_override word: explicit or tuned tile + arithmetic mode flags, derived from the tensors' dtypes"""
     t = (tile or default) | (MATH_BF16 if g.math else 0)
-    if _isp(x):                                          # plane operands: 0x200 (the fp32 paths' K-step bit) has no meaning here
-        if (t & 0xFF) == 8:                              # (tile 8 splits in registers: fp32 operands only; tile 7 has a pair reader)
-            t = (t & ~0xF0FF) | 3
-        return (t & ~(MATH_BF16 | 0x200)) | P3 | (H2 if x.kind == "h2" else 0)
+    if _isp(x):                                          # plane operands: BK32 (the fp32 paths' K-step bit) has no meaning here
+        if tile_id(t) == 8:                              # (tile 8 splits in registers: fp32 operands only; tile 7 has a pair reader)
+            t = with_tile(t, 3)
+        return (t & ~(MATH_BF16 | BK32)) | P3 | (H2 if x.kind == "h2" else 0)
     if getattr(g, "x3", False) and not g.math and not _is16(x):
         t |= X3 | (H2 if getattr(g, "h2", False) else 0)
     if _is16(x):
@@ -876,19 +914,17 @@ def autotune_wgrad(g, reps=None):
         s0 = g.nsplit
         cands = [(0, s0)]
         if g.cout > 64 and g.cin > 64:
-            shapes = [(1 << 4, 128, 128), (2 << 4, 64, 64)]
-            if getattr(g, "x3", False):
-                shapes.append((3 << 4, 128, 64))          # plane arithmetic only: fewer operand splits per MFMA block
-            for tflag, t, tn in shapes:
+            for tid in (1, 2, 3) if getattr(g, "x3", False) else (1, 2):   # (3, 128 x 64, plane arithmetic only: fewer operand splits per MFMA block)
+                tflag, (t, tn) = tid * WG_TILE, WG_TILE_SHAPE[tid]
                 tiles = -(-g.cout // t) * -(-g.cin // tn) * kk
                 for blocks in (256, 512, 768, 1024):
                     S = max(1, min(64, round(blocks / tiles), (M + 127) // 128))
-                    cands.append((tflag | 0x40, S))
+                    cands.append((tflag | WG_ONE_TAP, S))
                     if not g.math and not g.h16:
-                        cands.append((tflag | 0x40 | 0x80, S))       # 32 pixels per stage
+                        cands.append((tflag | WG_ONE_TAP | WG_PX32, S))
                     if getattr(g, "x3", False) and t == 64:
                         # the waves divide the pixels of a stage (64 four ways / 32 two ways) and share the operand splits
-                        cands += [(tflag | 0x40 | 0x400, S), (tflag | 0x40 | 0x800, S)]
+                        cands += [(tflag | WG_ONE_TAP | WG_KDIV4, S), (tflag | WG_ONE_TAP | WG_KDIV2, S)]
         cands = sorted(set(cands))
         dt = torch.bfloat16 if g.h16 else torch.float32
         dy = torch.randn(M, g.cout, device=dev).to(dt)
@@ -992,7 +1028,7 @@ def _conv_dgrad(g, dy, wft, dx, addend, mask, kc, tile, ws, splitk, skip_zero_ro
                 continue
             # rows that receive no tap at all only need the epilogue: one 16-deep stage over an all-(-1) table (a K-divided
             # tile needs 32 / 64 channels per stage: the plain 64 x 64 tile instead, no split-K)
-            ct = ((tile & ~0xF0FF) | 3) if (c["zero"] and (tile & 0xFF) >= 7) else tile
+            ct = with_tile(tile, 3) if (c["zero"] and tile_id(tile) >= 7) else tile
             _lib.call("radet_conv2d_igemm_taps_s", _ptr(dy), _ptr(wft), _ptr(addend), _ptr(mask), _ptr(dx), _ptr(c["table"]),
                       _ptr(c["out_rows"]), c["tap_ids"], c["ntaps"], g.k * g.k, c["rows"],
                       (32 if _is16(dy) else 16) if c["zero"] else kc, g.cin,
@@ -1015,27 +1051,27 @@ WGRAD9_DEEP = os.environ.get("RADET_WGRAD9_DEEP", "0") == "1"
 
 
 def _wgrad_key(g, dy, co):
+    def onetap(fl):
+        tile = ("launcher tile" if not wg_tile(fl) else "%d, %d" % WG_TILE_SHAPE[wg_tile(fl)]) if co > 32 else "32, 128"
+        kd = ", 64 px / 4 waves" if fl & WG_KDIV4 else (", 32 px / 2 waves" if fl & WG_KDIV2 else "")
+        return tile, (", 32 px" if fl & WG_PX32 else "") + kd
+
     if _isp(dy):
-        if dy.kind == "h2" and (g.k != 3 or g.wgrad_pair_flags & 0x40):
-            return f"conv_wgradq_kernel<{'128, 128' if (g.wgrad_pair_flags >> 4) & 3 == 1 else '64, 64'}> (fp16 plane pairs)"
+        if dy.kind == "h2" and (g.k != 3 or g.wgrad_pair_flags & WG_ONE_TAP):
+            return f"conv_wgradq_kernel<{'128, 128' if wg_tile(g.wgrad_pair_flags) == 1 else '64, 64'}> (fp16 plane pairs)"
         if dy.kind == "h2":
             if g.stride == 1 and g.pad == 1 and WGRAD9_DEEP and -(-g.lout.rows // (16 * (g.nsplit_pairs or g.nsplit))) * 16 <= 1664:
                 return "conv_wgrad9d_kernel"
             return "conv_wgrad9r_kernel" if (g.stride == 1 and g.pad == 1 and WGRAD9_WINDOWS) else "conv_wgrad9q_kernel"
         return "conv_wgrad9p_kernel"
+    tile, px = onetap(g.wgrad_flags)
     if getattr(g, "h2", False) and getattr(g, "x3", False) and not g.math and not _is16(dy):
-        tf = (g.wgrad_flags >> 4) & 3
-        tile = {0: "launcher tile", 1: "128, 128", 2: "64, 64", 3: "128, 64"}[tf] if co > 32 else "32, 128"
-        kd = ", 64 px / 4 waves" if g.wgrad_flags & 0x400 else (", 32 px / 2 waves" if g.wgrad_flags & 0x800 else "")
-        return f"conv_wgradg_kernel<{tile}> (fp16 hi/lo in registers{', 32 px' if g.wgrad_flags & 0x80 else ''}{kd})"
-    nine = g.k == 3 and g.cin % 32 == 0 and co >= 256 and g.lout.rows >= 16384 and not (g.wgrad_flags & 0x40)
+        return f"conv_wgradg_kernel<{tile}> (fp16 hi/lo in registers{px})"
+    nine = g.k == 3 and g.cin % 32 == 0 and co >= 256 and g.lout.rows >= 16384 and not (g.wgrad_flags & WG_ONE_TAP)
     mode = "bf16 storage" if _is16(dy) else ("bf16 math" if g.math else ("planes in registers" if getattr(g, "x3", False) else "fp32 MFMA"))
     if nine:
         return f"conv_wgrad9{'h' if _is16(dy) else 'g'}_kernel ({mode})"
-    tf = (g.wgrad_flags >> 4) & 3
-    tile = {0: "launcher tile", 1: "128, 128", 2: "64, 64", 3: "128, 64"}[tf] if co > 32 else "32, 128"
-    kd = ", 64 px / 4 waves" if g.wgrad_flags & 0x400 else (", 32 px / 2 waves" if g.wgrad_flags & 0x800 else "")
-    return f"conv_wgrad{'h' if _is16(dy) else 'g'}_kernel<{tile}> ({mode}{', 32 px' if g.wgrad_flags & 0x80 else ''}{kd})"
+    return f"conv_wgrad{'h' if _is16(dy) else 'g'}_kernel<{tile}> ({mode}{px})"
 
 
 def conv_wgrad(g, dy, x, slabs, dbias_partials=None, cout=None, ld_dy=None):
@@ -1053,29 +1089,29 @@ def _conv_wgrad(g, dy, x, slabs, dbias_partials=None, cout=None, ld_dy=None):
     if _isp(dy):
         assert _isp(x) and x.kind == dy.kind
         if dy.kind == "h2":
-            # all nine taps per workgroup for 3 x 3 convs unless the geometry's flags ask for the one-tap pair kernel (0x40;
-            # bits 4-5 = its tile), which also serves every other kernel size
-            nine = g.k == 3 and not (g.wgrad_pair_flags & 0x40)
-            fl = 0x1000 | 0x200 | (g.wgrad_pair_flags if nine else (0x40 | (g.wgrad_pair_flags & 0x30)))
+            # all nine taps per workgroup for 3 x 3 convs unless the geometry's flags ask for the one-tap pair kernel (WG_ONE_TAP;
+            # WG_TILE = its tile), which also serves every other kernel size
+            nine = g.k == 3 and not (g.wgrad_pair_flags & WG_ONE_TAP)
+            fl = WG_H2 | WG_P3 | (g.wgrad_pair_flags if nine else (WG_ONE_TAP | (g.wgrad_pair_flags & WG_TILE_MASK)))
             if nine and g.stride == 1 and g.pad == 1:       # unit stride, padding 1 (what the two kernels below rely on)
-                fl |= (0x2000 if WGRAD9_DEEP else 0) | (0x4000 if WGRAD9_WINDOWS else 0)
+                fl |= (WG_DEEP if WGRAD9_DEEP else 0) | (WG_WINDOWS if WGRAD9_WINDOWS else 0)
             _lib.call("radet_conv2d_wgrad_s", _ptr(dy.t), _ptr(x.t), _ptr(slabs), _ptr(dbias_partials), _ptr(g.fwd_table),
                       g.lout.rows, g.cin, co, co if ld_dy is None else ld_dy, g.k, g.k,
                       g.nsplit_pairs or g.nsplit, fl, _stream(), _scales(dy, x, None))
             return
         _lib.call("radet_conv2d_wgrad", _ptr(dy.t), _ptr(x.t), _ptr(slabs), _ptr(dbias_partials), _ptr(g.fwd_table), g.lout.rows,
-                  g.cin, co, co if ld_dy is None else ld_dy, g.k, g.k, g.nsplit, 0x200 | (g.wgrad_flags & 0x40), _stream())
+                  g.cin, co, co if ld_dy is None else ld_dy, g.k, g.k, g.nsplit, WG_P3 | (g.wgrad_flags & WG_ONE_TAP), _stream())
         return
     if getattr(g, "h2", False) and getattr(g, "x3", False) and not g.math and not _is16(dy):
         # fp16 hi / lo arithmetic on fp32 tensors: one-tap tiles only (an accumulator pair per tap does not fit the all-taps
-        # tile); 0x40 keeps the launcher away from it for the geometries the tuner has not seen
+        # tile); WG_ONE_TAP keeps the launcher away from it for the geometries the tuner has not seen
         _lib.call("radet_conv2d_wgrad_s", _ptr(dy), _ptr(x), _ptr(slabs), _ptr(dbias_partials), _ptr(g.fwd_table), g.lout.rows,
-                  g.cin, co, co if ld_dy is None else ld_dy, g.k, g.k, g.nsplit, 0x1000 | 0x40 | g.wgrad_flags, _stream(),
+                  g.cin, co, co if ld_dy is None else ld_dy, g.k, g.k, g.nsplit, WG_H2 | WG_ONE_TAP | g.wgrad_flags, _stream(),
                   _scales(dy, x, None))
         return
     _lib.call("radet_conv2d_wgrad", _ptr(dy), _ptr(x), _ptr(slabs), _ptr(dbias_partials), _ptr(g.fwd_table), g.lout.rows,
               g.cin, co, co if ld_dy is None else ld_dy, g.k, g.k, g.nsplit,
-              (2 if _is16(dy) else (1 if g.math else (0x100 if getattr(g, "x3", False) else 0))) | g.wgrad_flags, _stream())
+              (WG_STORE_BF16 if _is16(dy) else (WG_MATH_BF16 if g.math else (WG_X3 if getattr(g, "x3", False) else 0))) | g.wgrad_flags, _stream())
 
 
 def conv_wgrad_group(jobs, tile=128, math=0):
@@ -1089,7 +1125,7 @@ def conv_wgrad_group(jobs, tile=128, math=0):
             a.dy, a.x, a.slabs = _ptr(j["dy"]), _ptr(j["x"]), _ptr(j["slabs"])
             a.dbias_partials, a.gather_table = _ptr(j.get("dbias")), _ptr(g.fwd_table)
             a.M, a.Cin, a.Cout, a.ld_dy, a.KH, a.KW, a.S = g.lout.rows, g.cin, g.cout, g.cout, g.k, g.k, g.nsplit
-        _lib.call("radet_conv2d_wgrad_group", arr, len(part), (1 if math else 0) | ((1 if tile == 128 else 2) << 4), _stream())
+        _lib.call("radet_conv2d_wgrad_group", arr, len(part), (WG_MATH_BF16 if math else 0) | (1 if tile == 128 else 2) * WG_TILE, _stream())
 
 
 def group_splits(geoms, tile=128, slots=512):

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from radet_amd import kernels as FL   # the names of the launch flag bits, for the parametrised cases (tests use the fixture K)
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4   # north_star: fp32 boxes / scores within 1e-4
@@ -48,10 +50,10 @@ CONV_CASES = [
     (2, 256, 256, 30, 40, 3, 1, 1),
     (2, 256, 256, 30, 40, 3, 1, 2),
     (2, 256, 256, 30, 40, 3, 1, 3),
-    (1, 512, 512, 15, 20, 3, 1, 0x3003),     # forced split-K = 3, 64x64 tiles
-    (1, 1024, 256, 15, 20, 1, 1, 0x2000),    # forced split-K = 2, heuristic tile
+    (1, 512, 512, 15, 20, 3, 1, FL.splitk(3) | 3),     # forced split-K = 3, 64x64 tiles
+    (1, 1024, 256, 15, 20, 1, 1, FL.splitk(2)),    # forced split-K = 2, heuristic tile
     (4, 2048, 512, 15, 20, 1, 1, 0),         # layer4 shape: heuristic picks split-K
-    (4, 256, 256, 80, 80, 3, 1, 0x203),      # 1600 tiles: the 64 left-over tiles are split along K (tail split)
+    (4, 256, 256, 80, 80, 3, 1, FL.BK32 | 3),      # 1600 tiles: the 64 left-over tiles are split along K (tail split)
     (3, 128, 256, 40, 56, 3, 1, 2),          # 53 x 4 = 212... tiles with a ragged last M tile
     (2, 256, 21, 48, 64, 3, 1, 0),           # predictor heads at M >= 4096: single-wave all-taps wgrad kernel
     (2, 256, 4, 48, 66, 3, 1, 0),
@@ -128,18 +130,18 @@ KDIV_CASES = [
 
 
 @pytest.mark.parametrize("arith", [True, "h2"], ids=["bf16x3", "fp16x2"])
-@pytest.mark.parametrize("kd", [7, 8, 8 | 0x20000, 8 | 0x40000], ids=["4-kgroups", "2-kgroups", "2-kgroups-3stages", "2-kgroups-4stages"])
+@pytest.mark.parametrize("kd", [7, 8, 8 | FL.STAGES3, 8 | FL.STAGES4], ids=["4-kgroups", "2-kgroups", "2-kgroups-3stages", "2-kgroups-4stages"])
 @pytest.mark.parametrize("case", KDIV_CASES)
 def test_k_divided_tiles(K, case, kd, arith):
     """The 64 x 64 tiles whose four waves divide the K step (tile 7: four 16-channel k-groups of a 64-channel stage, every
     wave accumulates the whole tile; tile 8: two k-groups x two column halves of a 32-channel stage) and add their partial
-    tiles through LDS; and the pixel-divided one-tap wgrad (flags 0x400 / 0x800).  Same fp64 reference and tolerance as
+    tiles through LDS; and the pixel-divided one-tap wgrad (flags WG_KDIV4 / WG_KDIV2).  Same fp64 reference and tolerance as
     every other fp32 path; bit-identical from run to run."""
     B, Cin, Cout, H, W, k, s, sk = case
     if kd > 8 and arith != "h2":
         pytest.skip("deeper pipelines of the K-divided tile exist for the fp16 hi / lo arithmetic only")
-    g = torch.Generator().manual_seed(sum(case) + (kd & 0xFF) + (kd >> 17))
-    kd, deep = kd & 0xFF, kd & ~0xFF
+    g = torch.Generator().manual_seed(sum(case) + K.tile_id(kd) + (kd & (K.STAGES3 | K.STAGES4)) // K.STAGES3)
+    kd, deep = K.tile_id(kd), kd & ~K.ID_MASK
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
     bias = torch.randn(Cout, generator=g)
@@ -155,7 +157,7 @@ def test_k_divided_tiles(K, case, kd, arith):
     lv = K.Levels([(H, W)], B)
     geom = K.ConvGeom(lv, Cin, Cout, k, s, pad)
     geom.x3 = arith
-    tile = kd | deep | (sk << 12)
+    tile = kd | deep | K.splitk(sk)
     xr, wf = to_rows(x).to(dev), fold_w(w).to(dev)
     y = torch.full((B * Ho * Wo, Cout), float("nan"), device=dev)
     y2 = torch.full_like(y, float("nan"))
@@ -174,7 +176,7 @@ def test_k_divided_tiles(K, case, kd, arith):
     # pixel-divided wgrad, a few split counts (the last split is ragged)
     dyr = to_rows(dy).to(dev)
     for S in (1, 3):
-        geom.wgrad_flags, geom.nsplit = (2 << 4) | 0x40 | (0x400 if kd == 7 else 0x800), S
+        geom.wgrad_flags, geom.nsplit = 2 * K.WG_TILE | K.WG_ONE_TAP | (K.WG_KDIV4 if kd == 7 else K.WG_KDIV2), S
         slabs = torch.full((S, Cout, k * k, Cin), float("nan"), device=dev)
         bp = torch.full((S, Cout), float("nan"), device=dev)
         K.conv_wgrad(geom, dyr, xr, slabs, bp)
@@ -187,10 +189,10 @@ def test_k_divided_tiles(K, case, kd, arith):
 @pytest.mark.parametrize("shape", [
     # B, Cin, Cout, H, W, tile
     (2, 128, 128, 18, 22, 0),
-    (1, 256, 256, 13, 7, 0x5203),       # odd sizes (classes of unequal size, ragged last tiles), forced split-K 5
-    (4, 256, 256, 15, 20, 0x3203),      # the FPN P6 shape
+    (1, 256, 256, 13, 7, FL.splitk(5) | FL.BK32 | 3),       # odd sizes (classes of unequal size, ragged last tiles), forced split-K 5
+    (4, 256, 256, 15, 20, FL.splitk(3) | FL.BK32 | 3),      # the FPN P6 shape
     (2, 64, 128, 31, 33, 2),
-    (3, 512, 512, 9, 11, 0x201),        # 128 x 128 tiles over classes shorter than one tile
+    (3, 512, 512, 9, 11, FL.BK32 | 1),        # 128 x 128 tiles over classes shorter than one tile
 ])
 def test_strided_dgrad_class_launch(K, shape, x3, monkeypatch):
     """All four parity classes of a 3x3 / 2 dgrad in one launch (radet_conv2d_igemm_classes) against the fp64 dgrad, with
@@ -275,9 +277,9 @@ def test_fp32_from_bf16_planes_is_as_accurate_as_the_fp32_mfma(K):
         g = K.ConvGeom(lv, C, C, 3, 1, 1)
         g.x3 = x3
         y = torch.empty(lv.rows, C, device="cuda")
-        K.conv_fwd(g, xr, wf, None, y, tile=0x202)
+        K.conv_fwd(g, xr, wf, None, y, tile=K.BK32 | 2)
         y2 = torch.empty_like(y)
-        K.conv_fwd(g, xr * 4, wf * 0.5, None, y2, tile=0x202)
+        K.conv_fwd(g, xr * 4, wf * 0.5, None, y2, tile=K.BK32 | 2)
         assert torch.equal(y2, y * 2)
         slabs = torch.empty(g.nsplit, C, 9, C, device="cuda")
         K.conv_wgrad(g, dyr, xr, slabs)
@@ -286,8 +288,9 @@ def test_fp32_from_bf16_planes_is_as_accurate_as_the_fp32_mfma(K):
         assert torch.equal(slabs, s2)
         gw = slabs.double().sum(0).reshape(C, 3, 3, C).permute(0, 3, 1, 2)
         errs[x3] = (rel_err(from_rows(y, B, H, W), ref_y), rel_err(gw, ref_gw.cuda() if gw.is_cuda else ref_gw))
-        if x3:      # every one-tap tile of the plane arithmetic, 16- and 32-pixel stages (0x40: not the all-taps kernel)
-            for fl in (0x40 | (1 << 4), 0x40 | (2 << 4), 0x40 | (3 << 4), 0xC0 | (2 << 4), 0xC0 | (3 << 4)):
+        if x3:      # every one-tap tile of the plane arithmetic, 16- and 32-pixel stages (WG_ONE_TAP: not the all-taps kernel)
+            for fl in (K.WG_ONE_TAP | 1 * K.WG_TILE, K.WG_ONE_TAP | 2 * K.WG_TILE, K.WG_ONE_TAP | 3 * K.WG_TILE,
+                       K.WG_ONE_TAP | K.WG_PX32 | 2 * K.WG_TILE, K.WG_ONE_TAP | K.WG_PX32 | 3 * K.WG_TILE):
                 g.wgrad_flags, g.nsplit = fl, 6
                 s3 = torch.empty(6, C, 9, C, device="cuda")
                 K.conv_wgrad(g, dyr, xr, s3)
@@ -297,7 +300,7 @@ def test_fp32_from_bf16_planes_is_as_accurate_as_the_fp32_mfma(K):
         assert planes < 1e-5
 
 
-def _conv_errs(K, x4, w4, dy4, mode, tile=0x202, wflags=None):
+def _conv_errs(K, x4, w4, dy4, mode, tile=FL.BK32 | 2, wflags=None):
     """(forward, dgrad, wgrad) error of one 3x3 conv against fp64, relative to the largest reference magnitude"""
     B, C, H, W = x4.shape
     Co = w4.shape[0]
@@ -349,12 +352,13 @@ def test_fp32_from_fp16_pairs_is_as_accurate_as_the_fp32_mfma(K):
     zd[:, ::2] = 0
     cases["zero rows"] = (zr, torch.randn(C, C, 3, 3, generator=gen) / (C * 9) ** 0.5, zd)
     for name, (x4, w4, dy4) in cases.items():
-        for tile, wfl in ((0x202, 0x40 | (1 << 4)), (1, 0x40 | (3 << 4)), (3, 0xC0 | (2 << 4)), (7, 0x40 | (2 << 4) | 0x400),
-                          (8, 0x40 | (2 << 4) | 0x800)):
+        for tile, wfl in ((K.BK32 | 2, K.WG_ONE_TAP | 1 * K.WG_TILE), (1, K.WG_ONE_TAP | 3 * K.WG_TILE),
+                          (3, K.WG_ONE_TAP | K.WG_PX32 | 2 * K.WG_TILE), (7, K.WG_ONE_TAP | 2 * K.WG_TILE | K.WG_KDIV4),
+                          (8, K.WG_ONE_TAP | 2 * K.WG_TILE | K.WG_KDIV2)):
             # the native instruction on the same tile and the same pixel splits (the summation structure is part of the error;
             # the K-divided tiles and the 128 x 64 weight-gradient tile exist for the plane arithmetics only: 64 x 64 there)
-            native, _ = _conv_errs(K, x4, w4, dy4, False, tile=tile if (tile & 0xFF) < 7 else 3,
-                                   wflags=(wfl & ~0xC00) if ((wfl >> 4) & 3) != 3 else 0x40 | (2 << 4))
+            native, _ = _conv_errs(K, x4, w4, dy4, False, tile=tile if K.tile_id(tile) < 7 else 3,
+                                   wflags=(wfl & ~(K.WG_KDIV4 | K.WG_KDIV2)) if K.wg_tile(wfl) != 3 else K.WG_ONE_TAP | 2 * K.WG_TILE)
             errs, outs = _conv_errs(K, x4, w4, dy4, "h2", tile=tile, wflags=wfl)
             for e_n, e_h, what in zip(native, errs, ("fwd", "dgrad", "wgrad")):
                 assert e_h <= 1.25 * e_n + 1e-9, (name, hex(tile), what, e_h, e_n)
@@ -381,16 +385,16 @@ PAIR_CASES = [
     (2, 256, 256, 30, 40, 3, 5),            # 128 x 128, 8 waves
     (2, 256, 256, 30, 40, 3, 6),            # 256 x 128, 8 waves
     (1, 128, 128, 17, 23, 3, 5),            # ragged last M tile, image-border taps
-    (1, 512, 256, 15, 20, 3, 0x3005),       # forced split-K = 3
-    (4, 256, 256, 80, 80, 3, 0x20006),      # 3 LDS stages, tail split
-    (1, 1024, 256, 15, 20, 1, 0x2005),      # 1 x 1, forced split-K = 2
+    (1, 512, 256, 15, 20, 3, FL.splitk(3) | 5),       # forced split-K = 3
+    (4, 256, 256, 80, 80, 3, FL.STAGES3 | 6),      # 3 LDS stages, tail split
+    (1, 1024, 256, 15, 20, 1, FL.splitk(2) | 5),      # 1 x 1, forced split-K = 2
     (2, 64, 128, 20, 24, 1, 5),
 ]
 
 
 @pytest.mark.parametrize("case", PAIR_CASES)
 def test_plane_pair_operand_conv(K, case):
-    """radet_conv2d_igemm_s with x / w as fp16 plane pairs (tile_override 0x2000000 | 0x8000000): the pair split represents
+    """radet_conv2d_igemm_s with x / w as fp16 plane pairs (tile_override P3 | H2): the pair split represents
     every element to 2^-22 relative, and the conv is held to the same fp64 reference and tolerance as the fp32 paths (forward
     with bias + residual + ReLU, dgrad with mask); 3x3 cases also run the plane-pair all-taps wgrad (conv_wgrad9q_kernel)
     incl. its bias column sums."""
@@ -538,7 +542,7 @@ def test_wgrad_group_launch(K, tile, math):
         slabs, bp = torch.zeros(S, Cout, k * k, Cin, device="cuda"), torch.zeros(S, Cout, device="cuda")
         jobs.append(dict(g=geom, dy=dyr, x=xr, slabs=slabs, dbias=bp))
         s1, b1 = torch.zeros_like(slabs), torch.zeros_like(bp)
-        geom.wgrad_flags = ((1 if tile == 128 else 2) << 4) | 0x40
+        geom.wgrad_flags = (1 if tile == 128 else 2) * K.WG_TILE | K.WG_ONE_TAP
         K.conv_wgrad(geom, dyr, xr, s1, b1)
         singles.append((s1, b1))
     K.conv_wgrad_group(jobs, tile=tile, math=math)
@@ -552,10 +556,10 @@ def test_wgrad_group_launch(K, tile, math):
 H16_CASES = [
     # B, Cin, Cout, H, W, k, stride, tile
     (2, 256, 256, 30, 40, 3, 1, 1),
-    (2, 256, 256, 30, 40, 3, 1, 0x203),
-    (4, 256, 256, 80, 80, 3, 1, 0x203),      # tail split
+    (2, 256, 256, 30, 40, 3, 1, FL.BK32 | 3),
+    (4, 256, 256, 80, 80, 3, 1, FL.BK32 | 3),      # tail split
     (2, 64, 256, 20, 24, 1, 1, 0),
-    (1, 512, 512, 15, 20, 3, 1, 0x3003),     # forced split-K
+    (1, 512, 512, 15, 20, 3, 1, FL.splitk(3) | 3),     # forced split-K
     (2, 128, 128, 18, 22, 3, 2, 0),          # strided (parity-class dgrad)
     (1, 256, 21, 15, 20, 3, 1, 0),           # predictor head: fp32 output from bf16 inputs
 ]
@@ -563,8 +567,8 @@ H16_CASES = [
 
 @pytest.mark.parametrize("case", H16_CASES)
 def test_conv_bf16_storage(K, case):
-    """bf16-storage mode of the implicit-GEMM kernel (tile_override 0x800): bf16 activations / weights / residual /
-    mask in HBM, v_mfma_f32_32x32x16_bf16, fp32 accumulate, bf16 (or, +0x10000, fp32) output.  Reference = fp64
+    """bf16-storage mode of the implicit-GEMM kernel (tile_override STORE_BF16): bf16 activations / weights / residual /
+    mask in HBM, v_mfma_f32_32x32x16_bf16, fp32 accumulate, bf16 (or, + OUT_F32, fp32) output.  Reference = fp64
     convolution of the same bf16 values; a bf16 output may differ from the rounded reference by one bf16 step where
     the fp32 accumulation order moves the value across a rounding boundary."""
     B, Cin, Cout, H, W, k, s, tile = case
@@ -585,7 +589,7 @@ def test_conv_bf16_storage(K, case):
     small = Cout < 32
     y = torch.empty(B * Ho * Wo, Cout, device=dev, dtype=torch.float32 if small else bf)
     K.conv_fwd(geom, xr, wf, bias.to(dev), y, addend=to_rows(res).to(dev), relu=True,
-               tile=tile | 0x800 | (0x10000 if small else 0))
+               tile=tile | K.STORE_BF16 | (K.OUT_F32 if small else 0))
     got = from_rows(y.float(), B, Ho, Wo).double().cpu()
     if small:
         assert rel_err(got, out_ref) < 1e-5
@@ -601,7 +605,7 @@ def test_conv_bf16_storage(K, case):
     wft = w.permute(1, 2, 3, 0).reshape(Cin, k * k, Cout).contiguous().to(dev)
     mask = to_rows(torch.randn(B, Cin, H, W, generator=g)).to(bf).to(dev)
     dx = torch.empty(B * H * W, Cin, device=dev, dtype=bf)
-    K.conv_dgrad(geom, to_rows(dy).to(dev), wft, dx, mask=mask, tile=tile | 0x800)
+    K.conv_dgrad(geom, to_rows(dy).to(dev), wft, dx, mask=mask, tile=tile | K.STORE_BF16)
     gx_m = gx * (from_rows(mask.float().cpu(), B, H, W) > 0)
     got = from_rows(dx.float(), B, H, W).double().cpu()
     err = (got - gx_m).abs()
@@ -610,10 +614,10 @@ def test_conv_bf16_storage(K, case):
 
 
 @pytest.mark.parametrize("case", [(2, 256, 256, 30, 40, 3, 1, 0), (1, 128, 512, 33, 21, 1, 1, 0), (2, 128, 128, 18, 22, 3, 2, 0),
-                                  (1, 256, 21, 15, 20, 3, 1, 0), (2, 512, 256, 16, 20, 1, 1, 1 << 4),
+                                  (1, 256, 21, 15, 20, 3, 1, 0), (2, 512, 256, 16, 20, 1, 1, 1 * FL.WG_TILE),
                                   (4, 256, 256, 80, 80, 3, 1, 0)])
 def test_wgrad_bf16_storage(K, case):
-    """bf16-storage wgrad (flags bit 1): bf16 dy / x, transposing LDS reads, fp32 slabs == fp64 wgrad of the same
+    """bf16-storage wgrad (flags WG_STORE_BF16): bf16 dy / x, transposing LDS reads, fp32 slabs == fp64 wgrad of the same
     bf16 values (fp32 accumulation tolerance), incl. the fused bias column sums, ragged pixel counts, strided and
     small-Cout cases."""
     import ctypes as C
@@ -698,10 +702,10 @@ def test_streamk_schedule_matches_plain_launch(K, shape):
     w = (torch.randn(cout * k * k * cin, generator=gen) / (cin * k * k) ** 0.5).cuda()
     add = torch.randn(lv.rows, cout, generator=gen).cuda()
     ref = torch.empty(lv.rows, cout, device="cuda")
-    K.conv_fwd(g, x, w, None, ref, addend=add, relu=True, tile=3 | (1 << 12), splitk=False)
+    K.conv_fwd(g, x, w, None, ref, addend=add, relu=True, tile=3 | K.splitk(1), splitk=False)
     scale = float(ref.abs().max())
     for tile in (3, 4, 2):
-        for bk in (0, 0x200):
+        for bk in (0, K.BK32):
             if bk and cin % 32:
                 continue
             for wgs in (1, 2, 3, 4):
@@ -1164,15 +1168,15 @@ PLANE_CASES = [
     (2, 256, 256, 30, 40, 3, 1, 1),
     (2, 256, 256, 30, 40, 3, 1, 5),            # 128 x 128, 8 waves
     (2, 256, 256, 30, 40, 3, 1, 6),            # 256 x 128, 8 waves
-    (1, 512, 512, 15, 20, 3, 1, 0x3003),       # forced split-K = 3
-    (4, 256, 256, 80, 80, 3, 1, 0x20001),      # 3 LDS stages, tail split
-    (1, 1024, 256, 15, 20, 1, 1, 0x2003),      # forced split-K = 2
+    (1, 512, 512, 15, 20, 3, 1, FL.splitk(3) | 3),       # forced split-K = 3
+    (4, 256, 256, 80, 80, 3, 1, FL.STAGES3 | 1),      # 3 LDS stages, tail split
+    (1, 1024, 256, 15, 20, 1, 1, FL.splitk(2) | 3),      # forced split-K = 2
 ]
 
 
 @pytest.mark.parametrize("case", PLANE_CASES)
 def test_plane_operand_conv(K, case):
-    """radet_conv2d_igemm with x / w as bf16 plane triples (tile_override 0x2000000): the plane split is exact, and the
+    """radet_conv2d_igemm with x / w as bf16 plane triples (tile_override P3): the plane split is exact, and the
     conv is held to the same fp64 reference and tolerance as the fp32 paths (forward with bias + residual + ReLU, dgrad
     with mask); the 3x3 / 256-channel cases also run the plane-operand all-taps wgrad."""
     B, Cin, Cout, H, W, k, s, tile = case
@@ -1266,7 +1270,7 @@ def test_split_k_in_launch_reduction_under_uneven_load(K):
     for mode in ("fp32", "x3", "planes"):
         geom.x3 = mode == "x3"
         xs, ws = (K.Planes.from_float(x), K.Planes.from_float(w)) if mode == "planes" else (x, w.view(-1))
-        tile = (5 if mode == "planes" else 3) | 0x5000       # forced split-K = 5
+        tile = (5 if mode == "planes" else 3) | K.splitk(5)       # forced split-K = 5
         y0, y = torch.empty(lv.rows, Cout, device=dev), torch.empty(lv.rows, Cout, device=dev)
         K.conv_fwd(geom, xs, ws, None, y0, tile=tile)
         torch.cuda.synchronize()
@@ -1285,7 +1289,7 @@ def test_split_k_in_launch_reduction_under_uneven_load(K):
 @pytest.mark.parametrize("case", [(2, 256, 256, 30, 40, 3, 1, 2), (1, 128, 512, 33, 21, 1, 1, 2), (2, 128, 128, 18, 22, 3, 2, 1),
                                   (2, 512, 256, 16, 20, 1, 1, 1), (4, 1024, 256, 15, 20, 1, 1, 2), (3, 96, 160, 17, 23, 3, 1, 2)])
 def test_wgrad_one_tap_on_plane_pairs(K, case):
-    """conv_wgradq_kernel (radet_conv2d_wgrad_s flags 0x1000 | 0x200 | 0x40): the one-tap weight gradient with dy / x as fp16
+    """conv_wgradq_kernel (radet_conv2d_wgrad_s flags WG_H2 | WG_P3 | WG_ONE_TAP): the one-tap weight gradient with dy / x as fp16
     plane pairs (transposing LDS reads) == fp64 wgrad, incl. the bias column sums, ragged pixel counts / channel tiles,
     strided and 1 x 1 (no gather table) cases, both tiles."""
     B, Cin, Cout, H, W, k, s, tile = case
@@ -1296,7 +1300,7 @@ def test_wgrad_one_tap_on_plane_pairs(K, case):
     dy = torch.randn(B, Cout, Ho, Wo, generator=g) * 1e-2
     gw = torch.nn.grad.conv2d_weight(x.double(), (Cout, Cin, k, k), dy.double(), stride=s, padding=pad)
     geom = K.ConvGeom(K.Levels([(H, W)], B), Cin, Cout, k, s, pad)
-    geom.wgrad_pair_flags = 0x40 | (tile << 4)
+    geom.wgrad_pair_flags = K.WG_ONE_TAP | tile * K.WG_TILE
     xq, dyq = K.Planes.from_float(to_rows(x).cuda(), kind="h2"), K.Planes.from_float(to_rows(dy).cuda(), kind="h2")
     for S in (1, 3):
         geom.nsplit = S
@@ -1307,7 +1311,7 @@ def test_wgrad_one_tap_on_plane_pairs(K, case):
         assert rel_err(bp.sum(0), dy.double().sum((0, 2, 3))) < 2e-5, S
 
 
-@pytest.mark.parametrize("case", [(2, 64, 64, 20, 24, 3, 3), (1, 128, 128, 17, 23, 3, 8), (2, 256, 64, 12, 16, 3, 0x2003), (2, 64, 128, 9, 11, 1, 7)])
+@pytest.mark.parametrize("case", [(2, 64, 64, 20, 24, 3, 3), (1, 128, 128, 17, 23, 3, 8), (2, 256, 64, 12, 16, 3, FL.splitk(2) | 3), (2, 64, 128, 9, 11, 1, 7)])
 def test_pairs_only_tensors_of_a_bottleneck_block(K, case):
     """Round 6 (Engine.po): a tensor that only conv GEMMs and a ReLU mask read exists ONLY as fp16 plane pairs.
     (1) a forward launch with y = NULL writes nothing but the pairs (bound-scaled), raises the true-amax slot and the pairs
@@ -1386,7 +1390,7 @@ def test_pairs_only_tensors_of_a_bottleneck_block(K, case):
     wtq = K.Planes.from_float(wft2.reshape(Ci * k * k, Co), kind="h2")
     ref = torch.nn.grad.conv2d_input((B, Ci, H, W), w.double(), from_rows(dy.cpu(), B, H, W).double(), stride=1, padding=pad)
     ref = ref * (from_rows(act.cpu(), B, H, W) > 0)
-    for t in [(tile & 0xF000) | 3] + ([(tile & 0xF000) | 7] if Co % 64 == 0 else []):     # 4-wave pair tile; K-divided pair tile (round 6)
+    for t in [(tile & K.SPLITK_MASK) | 3] + ([(tile & K.SPLITK_MASK) | 7] if Co % 64 == 0 else []):     # 4-wave pair tile; K-divided pair tile (round 6)
         dx_a.fill_(float("nan"))
         K.conv_dgrad(geom, dyq, wtq, dx_a, mask=actq, tile=t)
         assert rel_err(from_rows(dx_a, B, H, W), ref) < 1e-5, hex(t)
@@ -1396,7 +1400,7 @@ def test_pairs_only_tensors_of_a_bottleneck_block(K, case):
         y3, y7 = torch.empty(R, Co, device=dev), torch.empty(R, Co, device=dev)
         y_ref = torch.relu(F.conv2d(x.double(), w.double(), bias.double(), padding=pad))
         K.conv_fwd(geom, xq, wq, br, y3, relu=True, tile=3)
-        for t in (7, 0x2007):
+        for t in (7, K.splitk(2) | 7):
             y7.fill_(float("nan"))
             K.conv_fwd(geom, xq, wq, br, y7, relu=True, tile=t)
             assert rel_err(from_rows(y7, B, H, W), y_ref) < 1e-5, hex(t)
@@ -1404,7 +1408,7 @@ def test_pairs_only_tensors_of_a_bottleneck_block(K, case):
 
 
 @pytest.mark.parametrize("case", [(2, 64, 64, 20, 24, 1, 1, 3), (2, 256, 128, 18, 22, 3, 2, 2), (1, 128, 256, 17, 23, 3, 1, 1),
-                                  (2, 512, 128, 15, 20, 1, 1, 0x3003), (1, 64, 256, 9, 11, 1, 1, 7), (2, 128, 128, 12, 16, 3, 1, 8)])
+                                  (2, 512, 128, 15, 20, 1, 1, FL.splitk(3) | 3), (1, 64, 256, 9, 11, 1, 1, 7), (2, 128, 128, 12, 16, 3, 1, 8)])
 def test_conv_epilogue_writes_plane_pair_copy(K, case):
     """RadetScales.yq: a conv launch (any fp32-tensor tile, here the in-register fp16 hi / lo ones, and plane-pair inputs)
     writes its output once more as fp16 plane pairs, scaled by a bound it can form before it starts,
@@ -1437,7 +1441,7 @@ def test_conv_epilogue_writes_plane_pair_copy(K, case):
     for xin, win in ((xr, wf), (K.Planes.from_float(xr, kind="h2"), K.Planes.from_float(wf.reshape(Cout * k * k, Cin), kind="h2"))):
         if K._isp(xin):
             xin.true_amax = K.amax_slot(xr, compute=True)
-            t = (tile & 0xF000) | (3 if (tile & 0xFF) >= 7 else tile & 0xFF)          # (no K-divided tile for plane operands)
+            t = (tile & K.SPLITK_MASK) | (3 if K.tile_id(tile) >= 7 else K.tile_id(tile))          # (no K-divided tile for plane operands)
         else:
             t = tile
         y.fill_(float("nan")); yq.t.zero_(); ys.zero_()
@@ -1465,9 +1469,9 @@ def test_conv_epilogue_writes_plane_pair_copy(K, case):
                                            ([(60, 80)], 1, 256, 256)])                     # a tower level of the headline config
 def test_all_taps_wgrad_variants_are_bit_identical(K, monkeypatch, hw, B, cin, cout):
     """The all-taps weight gradient on fp16 plane pairs of a unit-stride 3 x 3 conv, three kernels (radet_conv2d_wgrad_s flags):
-    conv_wgrad9q_kernel (two stage buffers), conv_wgrad9d_kernel (+0x2000, round 6, the default: five buffers, loads four stages
+    conv_wgrad9q_kernel (two stage buffers), conv_wgrad9d_kernel (WG_DEEP, round 6, off by default: five buffers, loads four stages
     ahead, the gather table of the pixel split in LDS as 16-bit differences, bias sums by inline-asm LDS reads) and
-    conv_wgrad9r_kernel (+0x4000, an experiment: the nine taps read shifted windows of three row segments, pixels whose tap is
+    conv_wgrad9r_kernel (WG_WINDOWS, an experiment: the nine taps read shifted windows of three row segments, pixels whose tap is
     padding zeroed in registers).  They form the same products in the same order, so slabs and bias column sums are equal bit
     for bit -- on multi-level geometries whose rows are shorter than / do not divide the 16-pixel stages, with ragged pixel
     splits and splits shorter than the pipeline -- and agree with the fp64 weight gradient (reference: the autograd of

@@ -19,12 +19,12 @@ def test_tower_gemm_is_exactly_linear_in_powers_of_two():
     x = torch.randn(lv.rows, 256, generator=gen).cuda()
     w = (torch.randn(256, 9, 256, generator=gen) * 0.02).cuda()
     y1, y2 = torch.empty(lv.rows, 256, device="cuda"), torch.empty(lv.rows, 256, device="cuda")
-    for tile in (0x203, 0x203 | K.STAGES3, 1):
+    for tile in (K.BK32 | 3, K.BK32 | 3 | K.STAGES3, 1):
         K.conv_fwd(g, x, w, None, y1, tile=tile)
         K.conv_fwd(g, 2 * x, w / 4, None, y2, tile=tile)
         assert torch.equal(y2 * 2, y1)
-    K.conv_dgrad(g, x, w, y1, tile=0x203)
-    K.conv_dgrad(g, x * 0.5, w * 8, y2, tile=0x203)
+    K.conv_dgrad(g, x, w, y1, tile=K.BK32 | 3)
+    K.conv_dgrad(g, x * 0.5, w * 8, y2, tile=K.BK32 | 3)
     assert torch.equal(y2 * 0.25, y1)
     S = g.nsplit
     s1, s2 = torch.empty(S, 256, 9, 256, device="cuda"), torch.empty(S, 256, 9, 256, device="cuda")

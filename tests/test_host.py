@@ -35,6 +35,80 @@ def test_cabi_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.RadetScales) == 96                    # 12 device pointers
 
 
+# The ABI pin of the two packed conv launch words (include/radet_hip.h) and of conv_igemmg_kernel's TAG argument
+# (csrc/conv_igemm_kernel.h; part of the mangled kernel symbols): an accidental renumbering fails here.
+TILE_WORD = dict(ID_MASK=0xFF, SYMBOL=0x100, BK32=0x200, MATH_BF16=0x400, STORE_BF16=0x800, SPLITK=0x1000, SPLITK_MASK=0xF000,
+                 OUT_F32=0x10000, STAGES3=0x20000, STAGES4=0x40000, ROWPAIRS=0x80000, STREAMK=0x100000, STREAMK_MASK=0x700000,
+                 X3=0x1000000, P3=0x2000000, H2=0x8000000, MASKQ=0x10000000)
+WGRAD_WORD = dict(MATH_BF16=0x1, STORE_BF16=0x2, TILE=0x10, TILE_MASK=0x30, ONE_TAP=0x40, PX32=0x80, X3=0x100, P3=0x200, KDIV4=0x400,
+                  KDIV2=0x800, H2=0x1000, DEEP=0x2000, WINDOWS=0x4000)
+TAG_BITS = dict(SYMBOL=1, BF16_MATH=2, H16=4, X3=8, P3=16, KDIV=32, H2=64, PAIRS=128)
+
+
+def test_conv_flag_words_header_and_python_agree():
+    """Every field of tile_override (RADET_TILE_<N>) and of the weight-gradient flags (RADET_WGRAD_<N>) is defined once in the
+    header and once in radet_amd/kernels.py -- as <N> resp. WG_<N> -- with the values pinned above; TAG_<N> likewise between
+    csrc/conv_igemm_kernel.h and kernels.TAG_<N>.  Within a word the fields are pairwise disjoint (a multi-bit field counts by
+    its <N>_MASK, whose lowest bit is the unit <N>)."""
+    from radet_amd import kernels as K
+    hdr = open(os.path.join(REPO, "include", "radet_hip.h")).read()
+    defs = {n: int(v, 0) for n, v in re.findall(r"^\s*(?:#define\s+)?(RADET_(?:TILE|WGRAD)_[A-Z0-9_]+)\s*=?\s*(0x[0-9A-Fa-f]+|\d+)\b", hdr, re.M)}
+    tile = {n[len("RADET_TILE_"):]: v for n, v in defs.items() if n.startswith("RADET_TILE_")}
+    wgrad = {n[len("RADET_WGRAD_"):]: v for n, v in defs.items() if n.startswith("RADET_WGRAD_")}
+    kh = open(os.path.join(REPO, "radet_amd", "csrc", "conv_igemm_kernel.h")).read()
+    tags = {n: int(v) for n, v in re.findall(r"^constexpr int TAG_([A-Z0-9_]+) = (\d+);", kh, re.M)}
+    assert tile == TILE_WORD and wgrad == WGRAD_WORD and tags == TAG_BITS
+    # the Python side: every constant of the definition block of kernels.py, and nothing else in it
+    src = open(os.path.join(REPO, "radet_amd", "kernels.py")).read()
+    block = src[src.index("launch flag words\n"):src.index("end of the launch flag words")]
+    names = [n.strip() for lhs in re.findall(r"^([A-Z][A-Z0-9_, ]*?) = ", block, re.M) for n in lhs.split(",")]
+    py = {n: getattr(K, n) for n in names}
+    want = dict(TILE_WORD)
+    want.update({"WG_" + n: v for n, v in WGRAD_WORD.items()})
+    want.update({"TAG_" + n: v for n, v in TAG_BITS.items()})
+    assert py == want, set(py.items()) ^ set(want.items())
+    for word in (TILE_WORD, WGRAD_WORD, TAG_BITS):
+        fields = dict(word)
+        for n in [n for n in word if n.endswith("_MASK") and n != "ID_MASK"]:
+            unit = fields.pop(n[:-len("_MASK")])
+            assert unit == word[n] & -word[n], n                   # the unit is the field's lowest bit
+        vals = list(fields.values())
+        assert sum(vals) == np.bitwise_or.reduce(vals), word        # pairwise disjoint
+    assert K.splitk(3) == 0x3000 and K.streamk(2) == 0x200000 and K.wg_tile(0x4e0) == 2 and K.tile_id(0x3003) == 3
+
+
+def test_conv_kernel_keys_unchanged():
+    """kernels._igemm_key / _wgrad_key name the kernel instantiation of a launch for bench.py, which parses the strings.
+    tests/golden/conv_keys.json holds what the functions returned BEFORE they were rewritten on the named flag fields: for every
+    distinct igemm word of the two committed tune files under each arithmetic's mode bits, the engine's fixed tower words,
+    tiles 7 / 8 with 3 / 4 stages and stream-K words; and for every distinct wgrad flag word of the tune files on 3 x 3 and
+    1 x 1 geometries in every arithmetic and operand format.  Runs without a device."""
+    import json
+    import types
+    from radet_amd import kernels as K
+    gold = json.load(open(os.path.join(REPO, "tests", "golden", "conv_keys.json")))
+    assert len(gold["igemm"]) >= 910 and len(gold["wgrad"]) >= 700
+    for t, ki in gold["igemm"]:
+        assert K._igemm_key(t, None) == gold["igemm_keys"][ki], hex(t)
+
+    def operand(kind):
+        if kind in ("f32", "bf16"):
+            return torch.empty(0, 8, dtype=torch.float32 if kind == "f32" else torch.bfloat16)
+        return K.Planes(0, 8, device="cpu", kind=kind, amax=torch.zeros(1))
+    saved = K.WGRAD9_DEEP, K.WGRAD9_WINDOWS
+    try:
+        for row in gold["wgrad"]:
+            c = dict(zip(gold["wgrad_fields"], row))
+            g = types.SimpleNamespace(k=c["k"], pad=c["pad"], stride=c["stride"], cin=c["cin"], cout=c["co"], nsplit=c["nsplit"],
+                                      nsplit_pairs=c["nsplit_pairs"], wgrad_flags=c["wgrad_flags"],
+                                      wgrad_pair_flags=c["wgrad_pair_flags"], math=c["math"], x3=c["x3"], h2=c["h2"],
+                                      lout=types.SimpleNamespace(rows=c["rows"]))
+            K.WGRAD9_DEEP, K.WGRAD9_WINDOWS = c["deep"], c["windows"]
+            assert K._wgrad_key(g, operand(c["dy"]), c["co"]) == gold["wgrad_keys"][c["key"]], c
+    finally:
+        K.WGRAD9_DEEP, K.WGRAD9_WINDOWS = saved
+
+
 def test_tape_thunks_are_current_and_replay_runs_host_calls():
     """The launch tape's generated thunks (radet_amd/csrc/tape_thunks.c) match _lib.SIGNATURES; radet_tape_replay unpacks
     the argument words of a recorded call correctly (checked on entry points that fail on bad arguments before they touch

@@ -42,7 +42,7 @@ def main():
         y = torch.empty(g.lout.rows, cout, device=dev)
         fl = 2.0 * g.lout.rows * cout * cin * k * k
         res = []
-        for tile in (1, 2, 3, 0, 0x201, 0x202, 0x203):
+        for tile in (1, 2, 3, 0, K.BK32 | 1, K.BK32 | 2, K.BK32 | 3):
             t = timeit(lambda: K.conv_fwd(g, x, w, None, y, relu=True, tile=tile))
             res.append(f"t{tile:x}:{fl / t / 1e12:5.1f}")
         dy = torch.randn(g.lout.rows, cout, device=dev)

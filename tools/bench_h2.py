@@ -45,8 +45,8 @@ def main():
         keys = [K.register_amax(x, slots[0]), K.register_amax(w, slots[1])]
         row = [f"M={g.lout.rows:6d} {Cin:4d}->{Cout:4d} k{k}"]
         if what == "fwd":
-            for tile in (1, 2, 3, 7, 8, 8 | 0x20000, 8 | 0x40000):
-                if (tile & 0xFF) == 7 and Cin % 64:
+            for tile in (1, 2, 3, 7, 8, 8 | K.STAGES3, 8 | K.STAGES4):
+                if K.tile_id(tile) == 7 and Cin % 64:
                     row.append("      -      ")
                     continue
                 g.x3, g.h2 = True, False
@@ -64,16 +64,17 @@ def main():
                 thd = timeit(lambda: zf(dummy))
                 thz = timeit(lambda: zf(slots[2]))
                 K.unregister_amax([ky])
-                row.append(f"t{tile & 0xFF}{chr(97 + (tile >> 17))}: {t3:5.1f} {th:5.1f} {tha:5.1f} [{thd:5.1f} {thz:5.1f}]")
+                row.append(f"t{K.tile_id(tile)}{chr(97 + (tile & (K.STAGES3 | K.STAGES4)) // K.STAGES3)}: {t3:5.1f} {th:5.1f} {tha:5.1f} [{thd:5.1f} {thz:5.1f}]")
             xq, wq = K.Planes.from_float(x, kind="h2"), K.Planes.from_float(w.view(Cout * k * k, Cin), kind="h2")
-            for tile in (1, 2, 3, 3 | 0x20000):
+            for tile in (1, 2, 3, 3 | K.STAGES3):
                 tq = timeit(lambda: K.conv_fwd(g, xq, wq, None, y, relu=True, tile=tile))
-                row.append(f"pairs t{tile & 0xFF}{chr(97 + (tile >> 17))}: {tq:5.1f}")
+                row.append(f"pairs t{K.tile_id(tile)}{chr(97 + (tile & (K.STAGES3 | K.STAGES4)) // K.STAGES3)}: {tq:5.1f}")
         else:
             dy = torch.randn(g.lout.rows, Cout, device=dev)
             K.absmax(dy, slots[2])
             keys.append(K.register_amax(dy, slots[2]))
-            for fl in ((1 << 4) | 0x40, (2 << 4) | 0x40, (3 << 4) | 0x40, (2 << 4) | 0x40 | 0x400, (2 << 4) | 0x40 | 0x800):
+            for fl in (1 * K.WG_TILE | K.WG_ONE_TAP, 2 * K.WG_TILE | K.WG_ONE_TAP, 3 * K.WG_TILE | K.WG_ONE_TAP,
+                       2 * K.WG_TILE | K.WG_ONE_TAP | K.WG_KDIV4, 2 * K.WG_TILE | K.WG_ONE_TAP | K.WG_KDIV2):
                 g.wgrad_flags, g.nsplit = fl, max(1, min(16, 512 // (max(1, Cout // 64) * max(1, Cin // 64) * k * k)))
                 slabs = torch.empty(g.nsplit * Cout * k * k * Cin, device=dev)
                 g.x3, g.h2 = True, False

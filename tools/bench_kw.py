@@ -42,9 +42,9 @@ def main(what="fwd"):
 
         def run(t, y):
             K.conv_fwd(g, x, w, None, y, relu=True, tile=t)
-        ref_c = [t | 0x200 | (sk << 12) for t in (1, 2, 3) for sk in (0, 1, 2, 3, 4, 6, 8) if sk <= 1 or (k * k * cin // 32) // sk >= 4]
+        ref_c = [t | K.BK32 | K.splitk(sk) for t in (1, 2, 3) for sk in (0, 1, 2, 3, 4, 6, 8) if sk <= 1 or (k * k * cin // 32) // sk >= 4]
         t_ref, best_ref = min((timeit(lambda: run(t, y0), n=10, warm=2), t) for t in ref_c)
-        run(3 | 0x200, y0)
+        run(3 | K.BK32, y0)
         res = []
         per = {}
         for tid in (7, 8):
@@ -52,7 +52,7 @@ def main(what="fwd"):
                 continue
             nkt = k * k * cin // (64 if tid == 7 else 32)
             for sk in [sk for sk in (1, 2, 3, 4, 6, 8) if sk == 1 or nkt // sk >= 3]:
-                t = tid | (sk << 12)
+                t = tid | K.splitk(sk)
                 y1.zero_()
                 run(t, y1)
                 torch.cuda.synchronize()
@@ -87,12 +87,12 @@ def wgrad():
         ref = None
         per = {}
         worst = 0.0
-        for tname, fl, t, tn in (("128x128", 1 << 4, 128, 128), ("64x64", 2 << 4, 64, 64), ("64x64/32px", 2 << 4 | 0x80, 64, 64),
-                                 ("128x64", 3 << 4, 128, 64), ("64x64 KD4", 2 << 4 | 0x400, 64, 64), ("64x64 KD2", 2 << 4 | 0x800, 64, 64)):
+        for tname, fl, t, tn in (("128x128", 1 * K.WG_TILE, 128, 128), ("64x64", 2 * K.WG_TILE, 64, 64), ("64x64/32px", 2 * K.WG_TILE | K.WG_PX32, 64, 64),
+                                 ("128x64", 3 * K.WG_TILE, 128, 64), ("64x64 KD4", 2 * K.WG_TILE | K.WG_KDIV4, 64, 64), ("64x64 KD2", 2 * K.WG_TILE | K.WG_KDIV2, 64, 64)):
             tiles = -(-cout // t) * -(-cin // tn) * kk
             for blocks in (256, 512, 768, 1024):
                 S = max(1, min(64, round(blocks / tiles), (M + 127) // 128))
-                g.wgrad_flags, g.nsplit = fl | 0x40, S
+                g.wgrad_flags, g.nsplit = fl | K.WG_ONE_TAP, S
                 slabs = torch.zeros(S * cout * kk * cin, device=dev)
                 K.conv_wgrad(g, dy, x, slabs)
                 torch.cuda.synchronize()

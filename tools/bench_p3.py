@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Plane-operand conv GEMMs (radet_conv2d_igemm +0x2000000, radet_conv2d_wgrad flags 0x200) against the in-register split
+"""Plane-operand conv GEMMs (radet_conv2d_igemm tile_override P3, radet_conv2d_wgrad flags WG_P3) against the in-register split
 (X3) kernels: agreement on the same data and time per launch over the tile configurations.  GPU only.
 
     python tools/bench_p3.py [tower|layer3|all]
@@ -46,13 +46,13 @@ def run_shape(name, lv, cin, cout, k, stride, pair=False, tiles=None):
     x2p = Planes.from_float(x2)
     y0b = torch.empty_like(y0)
 
-    def ref(t=0x200 | 1):
+    def ref(t=K.BK32 | 1):
         if pair:
             K.conv_fwd_pair(g, dict(x=x, w=w.view(-1), y=y0), dict(x=x2, w=w.view(-1), y=y0b), tile=t)
         else:
             K.conv_fwd(g, x, w.view(-1), None, y0, tile=t)
     ref()
-    t_ref = min(timeit(lambda: ref(0x200 | t)) for t in (1, 2, 3))
+    t_ref = min(timeit(lambda: ref(K.BK32 | t)) for t in (1, 2, 3))
     print(f"== {name}: M={g.lout.rows} {cin}->{cout} k{k}s{stride} pair={pair}  X3 (in-register split, best tile): "
           f"{t_ref:8.1f} us  {flop / t_ref / 1e6:7.1f} TFLOP/s")
     y1 = torch.empty_like(y0)

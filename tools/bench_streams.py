@@ -10,7 +10,7 @@ xa, wa, ya = mk(); xb, wb, yb = mk()
 dy = torch.randn(lv.rows, 256, device="cuda")
 slabs = torch.empty(g.nsplit * 256 * 9 * 256, device="cuda")
 s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
-TILE = 0x203
+TILE = K.BK32 | 3
 def seq(n):
     for _ in range(n):
         K.conv_fwd(g, xa, wa, None, ya, tile=TILE, splitk=False); K.conv_fwd(g, xb, wb, None, yb, tile=TILE, splitk=False)

@@ -20,12 +20,12 @@ def t(fn, n=30):
 for name, fx in (("gaussian activations", lambda t: t), ("ReLU'd activations (half zeros)", torch.relu), ("all-zero activations", torch.zeros_like),
                  ("constant activations", torch.ones_like)):
     xs = [fx(t) for t in x]
-    fn = lambda: K.conv_fwd_pair(g, dict(x=xs[0], w=w[0], y=y[0]), dict(x=xs[1], w=w[1], y=y[1]), relu=True, tile=0x201)
+    fn = lambda: K.conv_fwd_pair(g, dict(x=xs[0], w=w[0], y=y[0]), dict(x=xs[1], w=w[1], y=y[1]), relu=True, tile=K.BK32 | 1)
     us = t(fn)
     print(f"128x128 BK32, {name}: {us:7.1f} us  {fl / us / 1e6:6.1f} TF fp32-equivalent")
 g.x3 = False
 for name, fx in (("gaussian activations", lambda t: t), ("ReLU'd activations (half zeros)", torch.relu)):
     xs = [fx(t) for t in x]
-    fn = lambda: K.conv_fwd_pair(g, dict(x=xs[0], w=w[0], y=y[0]), dict(x=xs[1], w=w[1], y=y[1]), relu=True, tile=0x202)
+    fn = lambda: K.conv_fwd_pair(g, dict(x=xs[0], w=w[0], y=y[0]), dict(x=xs[1], w=w[1], y=y[1]), relu=True, tile=K.BK32 | 2)
     us = t(fn)
     print(f"native fp32 MFMA 128x64 BK32, {name}: {us:7.1f} us  {fl / us / 1e6:6.1f} TF")

@@ -14,6 +14,6 @@ x = torch.relu(torch.randn(lv.rows, 256, device=dev)); w = torch.randn(256 * 9, 
 xp, wp = Planes.from_float(x, kind="h2"), Planes.from_float(w, kind="h2")
 y = torch.empty(lv.rows, 256, device=dev)
 flop = 2.0 * lv.rows * 256 * 256 * 9
-for t in [6 | (1 << 12), 6 | (1 << 12) | K.ROWPAIRS, 5 | (1 << 12)]:
+for t in [6 | K.splitk(1), 6 | K.splitk(1) | K.ROWPAIRS, 5 | K.splitk(1)]:
     us = timeit(lambda: K.conv_fwd(g, xp, wp, None, y, tile=t))
     print(f"dbg={os.environ.get('RADET_DBG_IGEMM','0'):>2s} tile {t:#x}: {us:8.1f} us {flop/us/1e6:7.1f} TFLOP/s (fp32-equivalent)", flush=True)

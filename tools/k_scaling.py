@@ -4,7 +4,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from radet_amd import kernels as K
 H, W, cout = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
-tile = int(sys.argv[4], 0) if len(sys.argv) > 4 else 0x203
+tile = int(sys.argv[4], 0) if len(sys.argv) > 4 else K.BK32 | 3
 lv = K.Levels([(H, W)], 4)
 KS = [int(v) for v in os.environ.get('KS', '32,64,128,256,512,1024,2048').split(',')]
 for cin in KS:

@@ -13,12 +13,12 @@ w = torch.randn(cout * k * k * cin, device="cuda") * 0.05
 y = torch.empty(lv.rows, cout, device="cuda")
 cands = []
 for t in (1, 2, 3, 4):
-    for bk in (0, 0x200):
+    for bk in (0, K.BK32):
         for st in (0, K.STAGES3):
             for sk in (0, 1, 2, 3, 4, 5, 6, 8):
-                cands.append(t | bk | st | (sk << 12))
+                cands.append(t | bk | st | K.splitk(sk))
         if t != 1:
-            cands += [t | bk | (w * K.STREAMK) for w in (1, 2, 3, 4)]
+            cands += [t | bk | K.streamk(w) for w in (1, 2, 3, 4)]
 res = []
 flops = 2.0 * lv.rows * cin * cout * k * k
 for t in cands:
@@ -35,5 +35,6 @@ for t in cands:
     res.append((best, t))
 names = {1: "128x128", 2: "128x64", 3: "64x64", 4: "128x32"}
 for ms, t in sorted(res)[:14]:
-    print(f"{names[t & 0xff]:8s} BK{32 if t & 0x200 else 16} stages{3 if t & K.STAGES3 else 2} sk={(t >> 12) & 15} streamk={(t >> 20) & 7}: "
+    print(f"{names[K.tile_id(t)]:8s} BK{32 if t & K.BK32 else 16} stages{3 if t & K.STAGES3 else 2} sk={(t & K.SPLITK_MASK) // K.SPLITK} "
+          f"streamk={(t & K.STREAMK_MASK) // K.STREAMK}: "
           f"{ms * 1e3:7.1f} us  {flops / ms / 1e9:6.1f} TF")

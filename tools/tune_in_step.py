@@ -39,17 +39,16 @@ def candidates(g):
     tiles = [4] if n <= 32 else [1, 2, 3]
     c = list(tiles)
     if kdim % 32 == 0:
-        c += [t | 0x200 for t in tiles]
+        c += [t | K.BK32 for t in tiles]
     if getattr(g, "x3", False) and not g.math and not g.h16 and n > 32:
         c += ([7] if kdim % 64 == 0 else []) + ([8] if kdim % 32 == 0 else [])
     out = list(c)
     for t in c:
-        bm = 64 if (t & 0xFF) in (3, 7, 8) else 128
-        bn = {1: 128, 2: 64, 3: 64, 4: 32, 7: 64, 8: 64}[t & 0xFF]
+        bm, bn = K.TILE_SHAPE[K.tile_id(t)]
         ntiles = -(-m // bm) * -(-n // bn)
-        nk = taps * kdim // (64 if (t & 0xFF) == 7 else (32 if (t & 0x200 or (t & 0xFF) == 8) else 16))
+        nk = taps * kdim // (64 if K.tile_id(t) == 7 else (32 if (t & K.BK32 or K.tile_id(t) == 8) else 16))
         if ntiles < 1024:
-            out += [t | (sk << 12) for sk in (1, 2, 3, 4, 6, 8) if nk // sk >= 4]
+            out += [t | K.splitk(sk) for sk in (1, 2, 3, 4, 6, 8) if nk // sk >= 4]
     return out
 
 

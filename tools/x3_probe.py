@@ -17,9 +17,9 @@ def run(cin, cout, k, H, W, B=4):
     w = w4.permute(0, 2, 3, 1).reshape(-1).contiguous().cuda()          # OHWI
     y = torch.empty(lv.rows, cout, device="cuda")
     flops = 2.0 * lv.rows * cin * cout * k * k
-    for name, tile in (("fp32 64x64", 0x203), ("x3   64x64", 0x203 | K.X3), ("fp32 128x64", 0x202), ("x3   128x64", 0x202 | K.X3),
-                       ("fp32 128x128", 0x201), ("x3   128x128", 0x201 | K.X3)):
-        K.conv_fwd(g, x, w, None, y, tile=tile | (1 << 12))
+    for name, tile in (("fp32 64x64", K.BK32 | 3), ("x3   64x64", K.BK32 | 3 | K.X3), ("fp32 128x64", K.BK32 | 2), ("x3   128x64", K.BK32 | 2 | K.X3),
+                       ("fp32 128x128", K.BK32 | 1), ("x3   128x128", K.BK32 | 1 | K.X3)):
+        K.conv_fwd(g, x, w, None, y, tile=tile | K.splitk(1))
         err = (y.double() - ref).abs().max().item() / ref.abs().max().item()
         rms = ((y.double() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
         best = 1e9
@@ -27,7 +27,7 @@ def run(cin, cout, k, H, W, B=4):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
             for _b in range(5):
-                K.conv_fwd(g, x, w, None, y, tile=tile | (1 << 12))
+                K.conv_fwd(g, x, w, None, y, tile=tile | K.splitk(1))
             e.record(); e.synchronize()
             best = min(best, s.elapsed_time(e) / 5)
         print(f"{cin:5d}->{cout:4d} k{k} M={lv.rows:6d} {name:13s}: {best * 1e3:7.1f} us {flops / best / 1e9:7.1f} TFLOP/s   max err {err:.2e}  rms err {rms:.2e}")
