@@ -561,6 +561,35 @@ int radet_adamw_step(float* p, const float* g, float* m, float* v, size_t n, flo
                      float eps, float weight_decay, int step, float max_norm, float grad_div,
                      const float* partials, int npartials, float* grad_norm_out, void* stream);
 
+/* ---- COCO-protocol box evaluation (radet_amd/datasets/cocoeval.py:COCOeval, the yardstick: both entry points equal it bit
+ *      for bit; IEEE fp64 + - * / and comparisons only).
+ *      A segment is one (category, image) pair, numbered category * n_images + image in the evaluator's (sorted) id order --
+ *      one per image with useCats = 0.  Ground truths [gt_off[s], gt_off[s+1]) and detections [dt_off[s], dt_off[s+1]) belong
+ *      to segment s; detections of a segment are in descending-score order (stable), cut to maxDets[-1].
+ *      A segment may hold at most RADET_COCO_MAX_GT ground truths (the IoU row and the visiting orders live in LDS):
+ *      max_seg_gt above it makes radet_coco_match return RADET_ERR_COCO_OVERSIZE before anything is launched or written.
+ *      Also required: n_area <= 8 and n_area * n_thr <= 64 (one lane per pair), else -1. */
+#define RADET_COCO_MAX_GT 512
+#define RADET_ERR_COCO_OVERSIZE -3
+/* dt_xyxy f32[D,4]: the detector's corners (x, y, w = x2 - x1, h = y2 - y1, area = w * h are formed in fp64);
+ * gt_xywh f64[G,4], gt_area f64[G] (the annotation's `area`), gt_flags u8[G]: bit 0 iscrowd, bit 1 "annotation id is 0" (which
+ * the host evaluator reads as unmatched); iou_thrs f64[n_thr]; area_rng f64[n_area,2] (closed ranges).
+ * Outputs, with c = a * n_thr + t: dt_match i32[D, n_area*n_thr] index of the matched gt inside its segment (-1: none),
+ * dt_flag u8[D, n_area*n_thr] bit 0 matched, bit 1 dtIgnore; gt_match i32[G, n_area*n_thr] rank of the matching detection
+ * inside its segment (the caller pre-fills -1); gt_ignore u8[G, n_area]. */
+int radet_coco_match(const float* dt_xyxy, const int* dt_off, const double* gt_xywh, const double* gt_area,
+                     const uint8_t* gt_flags, const int* gt_off, int nseg, int max_seg_gt, const double* iou_thrs, int n_thr,
+                     const double* area_rng, int n_area, int* dt_match, uint8_t* dt_flag, int* gt_match, uint8_t* gt_ignore,
+                     void* stream);
+/* The detections of category k are rows [dt_cat_off[k], dt_cat_off[k+1]) of dt_flag_sorted u8[D, A*T] / dt_rank_sorted i32[D]
+ * (rank inside the segment) / dt_score_sorted f32[D], stable-sorted by descending score over all images; its ground truths are
+ * rows [gt_cat_off[k], gt_cat_off[k+1]) of gt_ignore.  Writes precision f64[T,R,K,A,M], recall f64[T,K,A,M] and scores
+ * f64[T,R,K,A,M] where the host evaluator writes them; the caller pre-fills -1. */
+int radet_coco_accumulate(const uint8_t* dt_flag_sorted, const int* dt_rank_sorted, const float* dt_score_sorted,
+                          const int* dt_cat_off, const uint8_t* gt_ignore, const int* gt_cat_off, const int* max_dets,
+                          const double* rec_thrs, int T, int R, int K, int A, int M, double* precision, double* recall,
+                          double* scores, void* stream);
+
 /* ---- launch tape (round 6): the host side of a steady-state train step as ONE call.  The reference drives its step from
  *      Python, one autograd node and one cuDNN / ATen launch at a time (mmcv's EpochBasedRunner.train -> model.train_step ->
  *      radet/models/detectors/base.py:218-253 -> optimizer hook); here a step is ~250 C-ABI calls on four HIP streams, and

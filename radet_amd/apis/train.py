@@ -129,10 +129,50 @@ def wrap_fp16_model(model, mode="bf16-storage"):
     return model
 
 
-def train_detector(model, batches, cfg, max_iters=None, log=print, checkpoint_path=None):
+_EVAL_HOOK_KEYS = ("interval", "start", "by_epoch", "save_best", "rule", "gpu_collect", "tmpdir", "broadcast_bn_buffer")
+
+
+def evaluate_during_training(model, rt, val_loader, cfg, it, log=print, eval_log=None):
+    """What the reference's EvalHook / DistEvalHook do after iteration `it` (radet/apis/train.py:131-149): the model goes to
+    eval(), the validation loader is tested (every rank its share when a process group is initialised), rank 0 evaluates
+    with `cfg.evaluation`'s metric and options on the device, logs one line and appends (it, metrics) to `eval_log`.
+    The training state is put back explicitly: train mode (the weights are folded again by the next step), the launch tape is
+    dropped (it is recorded again from the next steady-state step; a replay is bit-identical to the eager step), the engine
+    switches back to the training batch's plan on the next forward pass, and detect_stream has already handed the head-output
+    buffers back to their plans when its loop ended."""
+    from .test import multi_gpu_test, single_gpu_test
+    ev = dict(cfg.get("evaluation", None) or {})
+    kw = {k: v for k, v in ev.items() if k not in _EVAL_HOOK_KEYS}
+    kw.setdefault("logger", "silent")
+    distributed = dist.is_available() and dist.is_initialized()
+    rank = dist.get_rank() if distributed else 0
+    was_training = model.training
+    model.eval()
+    try:
+        if distributed:
+            results = multi_gpu_test(model, val_loader, tmpdir=ev.get("tmpdir"), gpu_collect=ev.get("gpu_collect", True))
+        else:
+            results = single_gpu_test(model, val_loader, on_device=True)[1]
+        metrics = None
+        if rank == 0:
+            metrics = val_loader.dataset.evaluate(results, device=rt.dev, **kw)
+            log(f"Iter(val) [{it}] " + ", ".join(f"{k}: {v:.4f}" if isinstance(v, float) else f"{k}: {v}"
+                                                for k, v in metrics.items() if k != "classwise"))
+            if eval_log is not None:
+                eval_log.append((it, metrics))
+    finally:
+        if was_training:
+            model.train()
+        rt.drop_tape()
+    return metrics
+
+
+def train_detector(model, batches, cfg, max_iters=None, log=print, checkpoint_path=None, val_loader=None, eval_log=None):
     """`batches`: iterable of dict(img=f32[B,3,H,W], gt_bboxes, gt_labels, points_to_gt_index, points_weight)
     (device or host tensors; lists per image).  One process per GPU; gradients are averaged over the
-    `torch.distributed` group if one is initialised.  Returns the list of logged loss triples."""
+    `torch.distributed` group if one is initialised.  Returns the list of logged loss triples.
+    val_loader: a test-mode `build_dataloader`; with it and `cfg.evaluation.interval = n` the detector is evaluated after
+    every n-th iteration (evaluate_during_training; the training trajectory is the same with and without it)."""
     if cfg.get("fp16", None) is not None:        # reference: Fp16OptimizerHook + wrap_fp16_model (apis/train.py:113-117)
         wrap_fp16_model(model)                   # here: bf16 operands, fp32 accumulate / master weights, no loss scaling
     rt = model.train().runtime()
@@ -148,6 +188,7 @@ def train_detector(model, batches, cfg, max_iters=None, log=print, checkpoint_pa
     interval = cfg.get("log_config", {}).get("interval", 50)
     ckpt_every = cfg.get("checkpoint_config", {}).get("interval", 0)
     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    eval_every = int((cfg.get("evaluation", None) or {}).get("interval", 0)) if val_loader is not None else 0
     history, t0 = [], time.time()
     for it, batch in enumerate(batches):
         if it >= max_iters:
@@ -164,4 +205,6 @@ def train_detector(model, batches, cfg, max_iters=None, log=print, checkpoint_pa
                     f"time: {(time.time() - t0) / (it + 1):.4f} s/iter")
         if checkpoint_path and ckpt_every and (it + 1) % ckpt_every == 0 and rank == 0:
             save_checkpoint(model, checkpoint_path.format(iter=it + 1), meta=dict(iter=it + 1), runtime=rt)
+        if eval_every > 0 and (it + 1) % eval_every == 0:
+            evaluate_during_training(model, rt, val_loader, cfg, it + 1, log=log, eval_log=eval_log)
     return history

@@ -340,9 +340,15 @@ class BOPDataset:
         return eval_recalls(gts, pooled, proposal_nums, iou_thrs).mean(axis=1)
 
     def evaluate(self, results, metric="bbox", logger=None, jsonfile_prefix=None, classwise=False,
-                 proposal_nums=(1, 10, 100), iou_thrs=None, metric_items=None):
+                 proposal_nums=(1, 10, 100), iou_thrs=None, metric_items=None, device=None):
         """COCO-protocol evaluation of per-class box lists; returns e.g. {'bbox_mAP': .., 'bbox_mAP_50': .., ...,
-        'bbox_mAP_copypaste': '...'} ('proposal': class-agnostic recall, keys 'AR@1' ...).  An empty result set gives {}."""
+        'bbox_mAP_copypaste': '...'} ('proposal': class-agnostic recall, keys 'AR@1' ...).  An empty result set gives {}.
+        device: None = the host evaluator.  A torch device = `bbox` / `proposal` run on DeviceCOCOeval (the same dict, bit for
+        bit the same tables); `results` may then also be the per-image (dets, labels) device tensors of
+        `single_gpu_test(..., on_device=True)`, and a JSON file is written only when `jsonfile_prefix` is given."""
+        if device is not None:
+            return self._evaluate_on_device(results, metric, logger, jsonfile_prefix, classwise, proposal_nums, iou_thrs,
+                                            metric_items, device)
         metrics, items = self._check_metrics(metric, metric_items)
         if self.bop_submission:
             raise RuntimeError("bop_submission=True formats BOP submission files (scene_id / image_id records); "
@@ -383,6 +389,55 @@ class BOPDataset:
         finally:
             if scratch:
                 scratch.cleanup()
+        return out
+
+    def _evaluate_on_device(self, results, metric, logger, jsonfile_prefix, classwise, proposal_nums, iou_thrs, metric_items,
+                            device):
+        """evaluate() with `bbox` / `proposal` on DeviceCOCOeval: the same messages and the same dict as the host path"""
+        from .cocoeval_device import DeviceCOCOeval, _is_device_results, results_to_lists
+        metrics, items = self._check_metrics(metric, metric_items)
+        if self.bop_submission:
+            raise RuntimeError("bop_submission=True formats BOP submission files (scene_id / image_id records); "
+                               "evaluate with bop_submission=False")
+        if iou_thrs is None:
+            iou_thrs = np.linspace(0.5, 0.95, 10)
+        if not isinstance(results, list):
+            raise AssertionError("results must be a list")
+        if len(results) != len(self):
+            raise AssertionError(f"The length of results is not equal to the dataset len: {len(results)} != {len(self)}")
+        lists = None
+        if _is_device_results(results) and (jsonfile_prefix is not None or "proposal_fast" in metrics):
+            lists = results_to_lists(results, len(self.cat_ids))
+        if jsonfile_prefix is not None and any(m != "proposal_fast" for m in metrics):
+            self.results2json(results if lists is None else lists, jsonfile_prefix)
+        out = {}
+        for m in metrics:
+            _log(("\n" if logger is None else "") + f"Evaluating {m}...", logger)
+            if m == "proposal_fast":
+                ar = self.fast_eval_recall(results if lists is None else lists, proposal_nums, iou_thrs)
+                out.update((f"AR@{n}", ar[i]) for i, n in enumerate(proposal_nums))
+                _log("".join(f"\nAR@{n}\t{ar[i]:.4f}" for i, n in enumerate(proposal_nums)), logger)
+                continue
+            try:
+                ev = DeviceCOCOeval(self.coco, results, self.cat_ids, self.img_ids, device, logger=logger)
+            except IndexError:
+                _log("The testing results of the whole dataset is empty.", logger, logging.ERROR)
+                break
+            ev.params.catIds, ev.params.imgIds = self.cat_ids, self.img_ids
+            ev.params.maxDets, ev.params.iouThrs = list(proposal_nums), iou_thrs
+            ev.params.useCats = 0 if m == "proposal" else ev.params.useCats
+            ev.evaluate()
+            ev.accumulate()
+            ev.summarize()
+            stat = lambda name: float(f"{ev.stats[_STAT_SLOT[name]]:.3f}")  # noqa: E731
+            if m == "proposal":
+                out.update((name, stat(name)) for name in (items or _PROPOSAL_ITEMS))
+                continue
+            if classwise:
+                assert ev.eval["precision"].shape[2] == len(self.cat_ids)
+                out["classwise"] = self._classwise(ev.eval["precision"], logger)
+            out.update((f"{m}_{name}", stat(name)) for name in (items or _STAT_SLOT))
+            out[f"{m}_mAP_copypaste"] = " ".join(f"{v:.3f}" for v in ev.stats[:6])
         return out
 
 

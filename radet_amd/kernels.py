@@ -1564,3 +1564,43 @@ def augment_hsv_noise(src, params2, dst, n, max_px):
 def augment_box(src, params2, dst, n, max_h, max_w):
     _lib.call("radet_augment_box", _ptr(src), _ptr(params2), _ptr(dst), src.numel() * src.element_size(), n, max_h, max_w,
               _stream())
+
+
+# ---------------------------------------------------------------------- COCO-protocol evaluation (csrc/cocoeval.hip)
+COCO_MAX_GT = 512                  # RADET_COCO_MAX_GT of include/radet_hip.h: ground truths per (category, image) segment
+COCO_ERR_OVERSIZE = -3             # RADET_ERR_COCO_OVERSIZE
+
+
+class CocoShapeError(_lib.RadetHipError):
+    """radet_coco_match refused its arguments before launching anything: a segment with more than COCO_MAX_GT ground truths
+    (code -3), or more (area range, threshold) pairs than lanes (code -1).  DeviceCOCOeval falls back to the host evaluator."""
+
+
+def coco_match(dt_xyxy, dt_off, gt_xywh, gt_area, gt_flags, gt_off, nseg, max_seg_gt, iou_thrs, area_rng, dt_match, dt_flag,
+               gt_match, gt_ignore):
+    """see include/radet_hip.h.  The return code is read here, not by _lib.call: the two argument refusals are a result."""
+    T, A = iou_thrs.numel(), area_rng.shape[0]
+    assert dt_match.shape == (dt_xyxy.shape[0], A * T) and dt_flag.shape == dt_match.shape
+    assert gt_match.shape == (gt_xywh.shape[0], A * T) and gt_ignore.shape == (gt_xywh.shape[0], A)
+    assert dt_off.numel() == nseg + 1 and gt_off.numel() == nseg + 1
+    _lib.load()
+    if "radet_coco_match" not in _lib._FN:
+        _lib._FN["radet_coco_match"] = _lib.load().radet_coco_match
+    rc = _lib._FN["radet_coco_match"](_ptr(dt_xyxy), _ptr(dt_off), _ptr(gt_xywh), _ptr(gt_area), _ptr(gt_flags), _ptr(gt_off),
+                                      nseg, int(max_seg_gt), _ptr(iou_thrs), T, _ptr(area_rng), A, _ptr(dt_match),
+                                      _ptr(dt_flag), _ptr(gt_match), _ptr(gt_ignore), _stream())
+    if rc == COCO_ERR_OVERSIZE:
+        raise CocoShapeError(f"a segment holds {max_seg_gt} ground truths, radet_coco_match at most {COCO_MAX_GT}")
+    if rc == -1:
+        raise CocoShapeError(f"radet_coco_match refuses {A} area ranges x {T} IoU thresholds (at most 8 ranges, 64 pairs)")
+    _lib.check(rc, "radet_coco_match")
+
+
+def coco_accumulate(dt_flag_sorted, dt_rank_sorted, dt_score_sorted, dt_cat_off, gt_ignore, gt_cat_off, max_dets, rec_thrs,
+                    T, K, A, precision, recall, scores):
+    R, M = rec_thrs.numel(), max_dets.numel()
+    assert precision.shape == (T, R, K, A, M) and scores.shape == precision.shape and recall.shape == (T, K, A, M)
+    assert dt_cat_off.numel() == K + 1 and gt_cat_off.numel() == K + 1 and dt_flag_sorted.shape[1] == A * T
+    _lib.call("radet_coco_accumulate", _ptr(dt_flag_sorted), _ptr(dt_rank_sorted), _ptr(dt_score_sorted), _ptr(dt_cat_off),
+              _ptr(gt_ignore), _ptr(gt_cat_off), _ptr(max_dets), _ptr(rec_thrs), T, R, K, A, M, _ptr(precision), _ptr(recall),
+              _ptr(scores), _stream())
