@@ -504,6 +504,28 @@ int radet_augment_hsv_noise(const uint8_t* src, const int* params2, uint8_t* dst
 int radet_augment_box(const uint8_t* src, const int* params2, uint8_t* dst, size_t nbytes, int nimg, int max_h, int max_w,
                       void* stream);
 
+/* ---- the mask-free sampler inside the image pipeline (GenerateDistanceMap(with_gt_mask=False), loading.py:596-645): the
+ *      padded box crops cut from the augmented u8 BGR image, and the distance maps pasted for the assigner.
+ *      radet_crop_canvases (csrc/augment.hip): src / lsum / params = what radet_augment_finish reads; a canvas pixel inside
+ *      its box's clipped source rectangle is the u8 BGR value radet_augment_finish normalises (contrast / brightness / color
+ *      blends, the mirrored column of a flipped image), every other canvas pixel the box's fill colour.  desc (device) =
+ *      ncanvas rows of CROP_DESC_INTS ints, coordinates in the (flipped) image:
+ *      {image index, window x0, y0 (image position of canvas pixel (0, 0), may be negative), canvas width, height,
+ *       source rectangle x0, y0, x1, y1 (exclusive; the kernel intersects it with the image), fill b | g << 8 | r << 16,
+ *       output pixel offset, 0};
+ *      dst = the u8 HWC canvases back to back ({offset, h, w} rows of the crop kernels above), total_px pixels (a canvas
+ *      that would leave it is not written); src_bytes = the size of src; src / dst 4-byte aligned; max_px = largest canvas.
+ *      radet_paste_maps (csrc/imgproc.hip): out f32 [nbox, H, W] = per box the map value inside the truncated box rectangle
+ *      (f32 as is, f64 rounded to f32), 1 there for a disabled box, 0 elsewhere; every element is written.  desc (device) =
+ *      nbox rows of PASTE_DESC_INTS ints: {map pixel offset, map height, map width, region x0, y0 inside the map, box x0,
+ *      y0, x1, y1 in the image (exclusive), enabled}; map_px = the size of maps in elements (reads stay inside it). */
+#define CROP_DESC_INTS 12
+#define PASTE_DESC_INTS 10
+int radet_crop_canvases(const uint8_t* src, size_t src_bytes, const unsigned long long* lsum, const int* params, int nimg,
+                        const int* desc, int ncanvas, int max_px, uint8_t* dst, size_t total_px, void* stream);
+int radet_paste_maps(const void* maps, size_t map_px, int is_f64, const int* desc, int nbox, int H, int W, float* out,
+                     void* stream);
+
 /* ---- stand-alone box / loss operators behind the registered classes (used on their own; inside the detector the same
  *      arithmetic runs fused in radet_head_loss / radet_decode_candidates) ------------------------------------------ */
 /* bbox_overlaps / BboxOverlaps2D (radet/core/bbox/iou_calculators/iou2d_calculator.py:43-159): boxes [batch, M, 4] and

@@ -179,6 +179,29 @@ __global__ __launch_bounds__(256) void aug_sharp_kernel(const uint8_t* __restric
     if (threadIdx.x == 0) atomicAdd(lsum + blockIdx.y, part[0] + part[1] + part[2] + part[3]);
 }
 
+// The u8 BGR pixel (y, x) of image n after the last photometric stage and the flip: what the reference's image holds when
+// Normalize (and the mask-free GenerateDistanceMap) read it.  src = the output of sharp (or of box in a mix pipeline).
+__device__ __forceinline__ void aug_final_bgr(const uint8_t* __restrict__ src, const unsigned long long* __restrict__ lsum,
+                                              const AugImg& a, int n, int y, int x, int v[3]) {
+    const int sx = (a.flags & AUG_FLIP) ? a.w - 1 - x : x;
+    const uint8_t* s = src + ((size_t)a.off + (size_t)y * a.w + sx) * 3;
+    v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+    if (a.flags & AUG_CONTRAST) {
+        const int mean = (int)((double)lsum[n] / (double)((long long)a.h * a.w) + 0.5);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = pil_blend(mean, v[c], a.f_contrast);
+    }
+    if (a.flags & AUG_BRIGHT) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = pil_blend(0, v[c], a.f_bright);
+    }
+    if (a.flags & AUG_COLOR) {
+        const int l = pil_luma(v[0], v[1], v[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = pil_blend(l, v[c], a.f_color);
+    }
+}
+
 // grid (ceil(Hp * Wp / 256), nimg): one output pixel (3 planes) per thread
 __global__ __launch_bounds__(256) void aug_finish_kernel(const uint8_t* __restrict__ src, const unsigned long long* __restrict__ lsum,
                                                          const int* __restrict__ params, float* __restrict__ out, int Hp, int Wp,
@@ -193,28 +216,70 @@ __global__ __launch_bounds__(256) void aug_finish_kernel(const uint8_t* __restri
         o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
         return;
     }
-    const int sx = (a.flags & AUG_FLIP) ? a.w - 1 - x : x;
-    const uint8_t* s = src + ((size_t)a.off + (size_t)y * a.w + sx) * 3;
-    int v[3] = {s[0], s[1], s[2]};
-    if (a.flags & AUG_CONTRAST) {
-        const int mean = (int)((double)lsum[blockIdx.y] / (double)((long long)a.h * a.w) + 0.5);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = pil_blend(mean, v[c], a.f_contrast);
-    }
-    if (a.flags & AUG_BRIGHT) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = pil_blend(0, v[c], a.f_bright);
-    }
-    if (a.flags & AUG_COLOR) {
-        const int l = pil_luma(v[0], v[1], v[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = pil_blend(l, v[c], a.f_color);
-    }
+    int v[3];
+    aug_final_bgr(src, lsum, a, blockIdx.y, y, x, v);
     const bool rgb = a.flags & AUG_TO_RGB;
     const float q0 = (float)(rgb ? v[2] : v[0]), q1 = (float)v[1], q2 = (float)(rgb ? v[0] : v[2]);
     o[0] = (q0 - m0) * s0;
     o[plane] = (q1 - m1) * s1;
     o[2 * plane] = (q2 - m2) * s2;
+}
+
+// The padded box crops of the mask-free sampler (GenerateDistanceMap(with_gt_mask=False)): one descriptor row per box
+// (include/radet_hip.h, CROP_DESC_INTS); canvases are packed u8 HWC arrays, back to back.
+struct CropBox { int img, wx, wy, cw, ch, sx0, sy0, sx1, sy1, fill, out; };
+
+__device__ __forceinline__ CropBox load_crop_box(const int* desc, int n) {
+    const int* d = desc + CROP_DESC_INTS * n;
+    CropBox b;
+    b.img = d[0]; b.wx = d[1]; b.wy = d[2]; b.cw = d[3]; b.ch = d[4];
+    b.sx0 = d[5]; b.sy0 = d[6]; b.sx1 = d[7]; b.sy1 = d[8]; b.fill = d[9]; b.out = d[10];
+    return b;
+}
+
+// canvas pixel p as b | g << 8 | r << 16: the image pixel under it inside the source rectangle (already intersected with
+// the image by the caller: no address is formed from a coordinate outside it), the fill colour elsewhere
+__device__ __forceinline__ uint32_t canvas_pixel(const uint8_t* __restrict__ src, const unsigned long long* __restrict__ lsum,
+                                                 const AugImg& a, const CropBox& b, int p) {
+    const int cy = p / b.cw, cx = p - cy * b.cw;
+    const int x = b.wx + cx, y = b.wy + cy;
+    if (x < b.sx0 || x >= b.sx1 || y < b.sy0 || y >= b.sy1) return (uint32_t)b.fill & 0xFFFFFFu;
+    int v[3];
+    aug_final_bgr(src, lsum, a, b.img, y, x, v);
+    return (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16);
+}
+
+// grid (ceil((3 * max_px / 4 + 2) / 256), ncanvas): one aligned dword of the packed output per thread.  A dword holds
+// bytes of at most two pixels; it is stored whole where all four bytes belong to this canvas, byte by byte at the two
+// ends (the neighbouring canvases own the other bytes of those dwords).
+__global__ __launch_bounds__(256) void crop_canvases_kernel(const uint8_t* __restrict__ src, const unsigned long long* __restrict__ lsum,
+                                                            const int* __restrict__ params, int nimg, const int* __restrict__ desc,
+                                                            uint8_t* __restrict__ dst, long long total_px, long long src_bytes) {
+    CropBox b = load_crop_box(desc, blockIdx.y);
+    if (b.img < 0 || b.img >= nimg || b.cw <= 0 || b.ch <= 0 || b.out < 0) return;          // (uniform over the workgroup)
+    const long long npx = (long long)b.cw * b.ch;
+    if ((long long)b.out + npx > total_px) return;
+    const AugImg a = load_img(params, b.img);
+    if (a.off < 0 || a.h <= 0 || a.w <= 0 || 3 * ((long long)a.off + (long long)a.h * a.w) > src_bytes) return;
+    b.sx0 = max(b.sx0, 0); b.sy0 = max(b.sy0, 0); b.sx1 = min(b.sx1, a.w); b.sy1 = min(b.sy1, a.h);
+    const long long gs = 3ll * b.out, ge = gs + 3 * npx;           // this canvas's bytes of dst
+    const long long G = (gs & ~3ll) + 4ll * ((long long)blockIdx.x * 256 + threadIdx.x);
+    if (G >= ge) return;
+    const long long k0 = G - gs;                                   // canvas byte of the dword's first byte (-3 .. at the head)
+    const int p0 = (int)((k0 < 0 ? 0 : k0) / 3);
+    const int r0 = (int)(k0 - 3ll * p0);                           // byte of pixel p0 the dword starts at (negative at the head)
+    // bytes r0 .. r0 + 3 of the 6-byte string (pixel p0, pixel p0 + 1)
+    uint64_t two = canvas_pixel(src, lsum, a, b, p0);
+    if (r0 + 3 > 2 && p0 + 1 < npx) two |= (uint64_t)canvas_pixel(src, lsum, a, b, p0 + 1) << 24;
+    if (r0 >= 0 && G + 4 <= ge) {
+        *(uint32_t*)(dst + G) = (uint32_t)(two >> (8 * r0));
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = r0 + q;                                   // byte of the string
+            if (r >= 0 && G + q < ge) dst[G + q] = (uint8_t)(two >> (8 * r));
+        }
+    }
 }
 
 extern "C" int radet_augment_merge_hblur(const uint8_t* src, const uint8_t* bg, const int* params, uint8_t* dst, int nimg,
@@ -253,6 +318,16 @@ extern "C" int radet_augment_finish(const uint8_t* src, const unsigned long long
     if (nimg == 0 || Hp == 0 || Wp == 0) return RADET_OK;
     hipLaunchKernelGGL(aug_finish_kernel, dim3((Hp * Wp + 255) / 256, nimg), dim3(256), 0, (hipStream_t)stream, src, lsum, params,
                        out, Hp, Wp, m0, m1, m2, s0, s1, s2);
+    return radet_check_launch();
+}
+
+extern "C" int radet_crop_canvases(const uint8_t* src, size_t src_bytes, const unsigned long long* lsum, const int* params, int nimg,
+                                   const int* desc, int ncanvas, int max_px, uint8_t* dst, size_t total_px, void* stream) {
+    if (nimg < 0 || ncanvas < 0 || max_px < 0 || ((uintptr_t)dst & 3)) return RADET_ERR_ARG;
+    if (nimg == 0 || ncanvas == 0 || max_px == 0) return RADET_OK;
+    const long long dwords = (3ll * max_px + 3) / 4 + 1;          // an unaligned canvas touches one dword more
+    hipLaunchKernelGGL(crop_canvases_kernel, dim3((unsigned)((dwords + 255) / 256), ncanvas), dim3(256), 0, (hipStream_t)stream, src,
+                       lsum, params, nimg, desc, dst, (long long)total_px, (long long)src_bytes);
     return radet_check_launch();
 }
 

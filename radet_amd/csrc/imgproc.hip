@@ -199,6 +199,44 @@ __global__ void zero_u32_kernel(unsigned* p, int n) {
     if (i < n) p[i] = 0u;
 }
 
+// The distance maps of the mask-free sampler pasted for the assigner (loading.py:639-644): out[g] is zero except inside
+// box g's truncated rectangle, where it holds the box's region of its map (1 for a box too small to be transformed).
+// One descriptor row per box (include/radet_hip.h, PASTE_DESC_INTS).  grid (ceil(H * ceil(W / 4) / 256), nbox): four
+// neighbouring pixels of a row per thread, one 16-byte store where the row starts are aligned (W a multiple of 4).
+template <class T>
+__global__ __launch_bounds__(256) void paste_maps_kernel(const T* __restrict__ maps, long long map_px, const int* __restrict__ desc,
+                                                         int H, int W, float* __restrict__ out) {
+    const int* d = desc + PASTE_DESC_INTS * blockIdx.y;
+    const int mh = d[1], mw = d[2], rx = d[3], ry = d[4];
+    const int bx0 = max(d[5], 0), by0 = max(d[6], 0), bx1 = min(d[7], W), by1 = min(d[8], H);
+    // a map that does not lie inside `maps` is not read (the box then counts as disabled)
+    const bool enabled = d[9] != 0 && d[0] >= 0 && mh > 0 && mw > 0 && (long long)d[0] + (long long)mh * mw <= map_px;
+    const T* map = maps + (enabled ? d[0] : 0);
+    const int W4 = (W + 3) >> 2;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= H * W4) return;
+    const int y = i / W4, x4 = (i - y * W4) * 4;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (y >= by0 && y < by1) {
+        const int my = ry + (y - d[6]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int x = x4 + q, mx = rx + (x - d[5]);
+            if (x < bx0 || x >= bx1) continue;
+            if (!enabled) v[q] = 1.f;
+            else if (my >= 0 && my < mh && mx >= 0 && mx < mw) v[q] = (float)map[(size_t)my * mw + mx];
+        }
+    }
+    float* o = out + ((size_t)blockIdx.y * H + y) * W + x4;
+    if ((W & 3) == 0) {
+        *(float4*)o = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (x4 + q < W) o[q] = v[q];
+    }
+}
+
 static inline dim3 crop_grid(int max_px, int n) { return dim3((max_px + 255) / 256, n); }
 
 extern "C" int radet_resize_linear_u8(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* dst_desc, int ncrop,
@@ -245,5 +283,21 @@ extern "C" int radet_sobel_edge(const uint8_t* src, const int* desc, float* edge
     hipLaunchKernelGGL(blur3_gray_kernel, crop_grid(max_px, ncrop), dim3(256), 0, st, src, desc, gray_ws);
     hipLaunchKernelGGL(sobel_kernel, crop_grid(max_px, ncrop), dim3(256), 0, st, gray_ws, desc, edge, max_ws);
     hipLaunchKernelGGL(edge_norm_kernel, crop_grid(max_px, ncrop), dim3(256), 0, st, edge, desc, max_ws);
+    return radet_check_launch();
+}
+
+extern "C" int radet_paste_maps(const void* maps, size_t map_px, int is_f64, const int* desc, int nbox, int H, int W, float* out,
+                                void* stream) {
+    if (nbox < 0 || H < 0 || W < 0 || ((uintptr_t)out & 15)) return RADET_ERR_ARG;
+    if (nbox == 0 || H == 0 || W == 0) return RADET_OK;
+    const long long threads = (long long)H * ((W + 3) / 4);
+    if (threads > 0x7FFFFFFFll) return RADET_ERR_ARG;
+    const dim3 grid((unsigned)((threads + 255) / 256), nbox);
+    if (is_f64)
+        hipLaunchKernelGGL(paste_maps_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (const double*)maps, (long long)map_px,
+                           desc, H, W, out);
+    else
+        hipLaunchKernelGGL(paste_maps_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)maps, (long long)map_px,
+                           desc, H, W, out);
     return radet_check_launch();
 }

@@ -7,7 +7,9 @@ sample's own generators (`rnd`: a random.Random or the `random` module, `nprnd`:
 touches no device, so the loader runs it on host threads.  `ImagePipeline.run(planned)` then does the device part of a
 whole batch on the calling thread and stream: the resize of images and backgrounds (radet_resize_linear_u8), mask
 normalisation / resize / flip (radet_mask_transform), the four augmentation launches of csrc/augment.hip (a mixpbr
-pipeline: merge, hsv_noise, box, finish) and the label assigner -- a fixed number of launches whatever the batch size.  A single sample (`BOPDataset.__getitem__`) is a batch
+pipeline: merge, hsv_noise, box, finish), the box crops / distance maps of a mask-free GenerateDistanceMap
+(radet_crop_canvases, the ops' packed GDT / MBD chain, radet_paste_maps) and the label assigner -- a fixed number of
+launches whatever the batch size.  A single sample (`BOPDataset.__getitem__`) is a batch
 of one.  Options the RADet configs do not use raise NotImplementedError."""
 import glob
 import math
@@ -415,17 +417,19 @@ class ImagePipeline:
                 _refuse(f"an image pipeline without {need}")
         self.assigner = next((t for t in flat if isinstance(t, LabelAssignment)), None)
         dm = next((t for t in flat if isinstance(t, GenerateDistanceMap)), None)
-        if dm is not None and not dm.with_gt_mask:
-            _refuse("GenerateDistanceMap(with_gt_mask=False) in an image pipeline")
         if self.assigner is not None and dm is None:
             raise ValueError("LabelAssignment needs GenerateDistanceMap before it")
+        # the mask-free sampler: box crops of the augmented image -> GDT / MBD maps (Sobel and MBD are the device paths)
+        self.mask_free = dm if dm is not None and not dm.with_gt_mask else None
+        if self.mask_free is not None and getattr(dm.distance_transform, "extract_edge_func", None) is not None:
+            _refuse("GenerateDistanceMap(extract_edge_func=...) in an image pipeline (a host callback)")
         self.tta = any(isinstance(t, MultiScaleFlipAug) for t in self.transforms)
 
     def plan(self, results, rnd, nprnd):
         """host part of one sample (thread-safe for distinct generators): decoding, boxes, random draws"""
         s = dict(results)
         for t in self.transforms:
-            if not isinstance(t, (GenerateDistanceMap, LabelAssignment)):     # (device-only: run() does them)
+            if not isinstance(t, LabelAssignment):     # (device-only: run() does it; GenerateDistanceMap plans its crops)
                 t.plan(s, rnd, nprnd)
         s["_nprnd"] = nprnd
         return s
@@ -531,13 +535,63 @@ class ImagePipeline:
         p2g = pw = None
         if self.assigner is not None:
             p2g, pw = [None] * B, [None] * B
+            # (t1 / lsum / params: what augment_finish has just read -- the augmented u8 image exists nowhere else)
+            maps = flipped_masks if self.mask_free is None else self._distance_maps(planned, hw, t1, lsum, params, dev)
             for shape in sorted(set(hw)):
                 idx = [i for i in range(B) if hw[i] == shape]
-                a, b = self.assigner.assign_batch([planned[i]["gt_bboxes"] for i in idx], [flipped_masks[i] for i in idx], shape,
+                a, b = self.assigner.assign_batch([planned[i]["gt_bboxes"] for i in idx], [maps[i] for i in idx], shape,
                                                   rngs=[planned[i]["_nprnd"] for i in idx], device=dev)
                 for j, i in enumerate(idx):
                     p2g[i], pw[i] = a[j], b[j]
         return self._collect(planned, out, p2g, pw, collate)
+
+    def _distance_maps(self, planned, hw, img, lsum, params, dev):
+        """The mask-free sampler's maps of a batch, f32 [G_i, h, w] per sample: every box's padded crop cut from the
+        augmented image (one launch), the GDT / MBD chain over all crops (ops.*_box2distance.packed_maps), one paste launch
+        per image size.  All descriptors come from the planned box geometry; nothing is read back from the device."""
+        from ..ops import _Packed, _upload
+        boxes = [(i, k) for i, s in enumerate(planned) for k in range(len(s["_crop_plan"][0].corners))]
+        maps = [torch.zeros(0, *hw[i], dtype=torch.float32, device=dev) for i in range(len(planned))]
+        if not boxes:
+            return maps
+        # canvases only for the boxes that are transformed (a box below small_object_size pastes ones)
+        large = [n for n, (i, k) in enumerate(boxes) if planned[i]["_crop_plan"][0].large[k]]
+        D = np.zeros((len(large), K.CROP_DESC_INTS), np.int32)
+        sizes, o = [], 0
+        for row, n in zip(D, large):
+            i, k = boxes[n]
+            g, fill = planned[i]["_crop_plan"]
+            (cw, ch), b = g.canvas_wh[k], fill[k].astype(np.int64)
+            if cw < 2 or ch < 2:
+                raise ValueError(f"a gt box of sample {i} truncates to a canvas of {ch} x {cw} pixels (the transforms need 2 x 2)")
+            row[:] = [i, *g.win_lo[k], cw, ch, *g.src_lo[k], *g.src_hi[k], b[0] | b[1] << 8 | b[2] << 16, o, 0]
+            sizes.append((int(ch), int(cw)))
+            o += int(cw) * int(ch)
+        where = {}
+        if large:
+            canvases = torch.empty(o * 3, dtype=torch.uint8, device=dev)
+            K.crop_canvases(img, lsum, params, len(planned), _upload(D, dev), len(large), max(h * w for h, w in sizes), canvases)
+            dmaps, _ = self.mask_free.distance_transform.packed_maps(_Packed(canvases, sizes, 3), [True] * len(large))
+            where = dict(zip(large, zip(dmaps.offs, dmaps.hw)))
+        for shape in sorted(set(hw)):
+            rows = [n for n, (i, k) in enumerate(boxes) if hw[i] == shape]
+            if not rows:
+                continue
+            P = np.zeros((len(rows), K.PASTE_DESC_INTS), np.int32)
+            for prow, n in zip(P, rows):
+                i, k = boxes[n]
+                g = planned[i]["_crop_plan"][0]
+                off, (mh, mw) = where.get(n, (0, (0, 0)))
+                prow[:] = [off, mh, mw, g.regions[k, 0], g.regions[k, 1], *g.corners[k], n in where]
+            pasted = torch.empty(len(rows), *shape, dtype=torch.float32, device=dev)
+            K.paste_maps(dmaps.data if large else pasted, _upload(P, dev), len(rows), shape[0], shape[1], pasted)
+            o = 0
+            for i in range(len(planned)):
+                if hw[i] == shape:
+                    c = len(planned[i]["_crop_plan"][0].corners)
+                    maps[i] = pasted[o:o + c]
+                    o += c
+        return maps
 
     @staticmethod
     def _params2(planned, offs, hw):

@@ -2,6 +2,7 @@
 (radet/datasets/pipelines/label_assignment.py:15-201) on the GPU, batched over images, and GenerateDistanceMap
 (loading.py:543-650): the pass-through of the visible masks and the mask-free variant built on the GPU box-to-distance
 transforms."""
+import collections
 import ctypes as C
 import math
 
@@ -17,6 +18,36 @@ INF = 1e8
 
 def build_pipeline(cfg):
     return build_from_cfg(cfg, PIPELINES)
+
+
+CropGeometry = collections.namedtuple("CropGeometry", "corners canvas_wh win_lo src_lo src_hi dst_lo dst_hi regions large")
+
+
+def crop_geometry(gt_bboxes, img_shape, pad_ratio, small_object_size):
+    """The box arithmetic of loading.py:595-628 for all G boxes at once (int arrays [G, 2] as (x, y) unless noted):
+    corners [G, 4] = the truncated boxes; canvas_wh = the box grown by ceil(pad_ratio * side) on every side; win_lo = the
+    image position of canvas pixel (0, 0); src_lo / src_hi = the grown window clipped to the last valid pixel (used as an
+    exclusive slice end, like the reference: the last row / column of the image never reaches a canvas); dst_lo / dst_hi =
+    where that part sits on the canvas; regions [G, 4] = the box's own rectangle inside its canvas; large bool [G] = boxes
+    above small_object_size (the others are not transformed)."""
+    gt_bboxes = np.asarray(gt_bboxes).reshape(-1, 4)
+    bounds = np.array([img_shape[1] - 1, img_shape[0] - 1], dtype=np.int_)        # last valid (x, y)
+    side = gt_bboxes[:, 2:4] - gt_bboxes[:, 0:2]
+    large = (side + 1).prod(axis=1) > small_object_size
+    corners = gt_bboxes.astype(np.int_)                                             # truncation
+    lo, hi = corners[:, 0:2], corners[:, 2:4]
+    grow = np.ceil((hi - lo) * pad_ratio).astype(np.int_)
+    canvas_wh = hi - lo + 2 * grow
+    win_lo, win_hi = lo - grow, hi + grow                                           # grown window, image coordinates
+    src_lo, src_hi = np.clip(win_lo, 0, bounds), np.clip(win_hi, 0, bounds)         # its part inside the image
+    dst_lo, dst_hi = src_lo - win_lo, canvas_wh - (win_hi - src_hi)                 # where that part sits on the canvas
+    regions = np.concatenate([grow, canvas_wh - grow], axis=1)
+    return CropGeometry(corners, canvas_wh, win_lo, src_lo, src_hi, dst_lo, dst_hi, regions, large)
+
+
+def draw_fill_colours(rnd, n):
+    """three randint(0, 255) per box, box after box (loading.py:608), on `rnd` (a random.Random or the random module)"""
+    return np.array([rnd.randint(0, 255) for _ in range(3 * n)], dtype=np.uint8).reshape(-1, 3)
 
 
 @PIPELINES.register_module()
@@ -49,25 +80,25 @@ class GenerateDistanceMap:
         window covers; the box's own rectangle inside its canvas; and which boxes exceed `small_object_size`.
         Returns (list of u8 [h, w, 3] canvases, bool [G], int [G, 4] regions)."""
         import random
-        bounds = np.array([img_shape[1] - 1, img_shape[0] - 1], dtype=np.int_)        # last valid (x, y)
-        side = gt_bboxes[:, 2:4] - gt_bboxes[:, 0:2]
-        large = (side + 1).prod(axis=1) > self.small_object_size
-        corners = gt_bboxes.astype(np.int_)                                             # truncation
-        lo, hi = corners[:, 0:2], corners[:, 2:4]
-        grow = np.ceil((hi - lo) * self.pad_ratio).astype(np.int_)
-        canvas_wh = hi - lo + 2 * grow
-        win_lo, win_hi = lo - grow, hi + grow                                           # grown window, image coordinates
-        src_lo, src_hi = np.clip(win_lo, 0, bounds), np.clip(win_hi, 0, bounds)         # its part inside the image
-        dst_lo, dst_hi = src_lo - win_lo, canvas_wh - (win_hi - src_hi)                 # where that part sits on the canvas
-        regions = np.concatenate([grow, canvas_wh - grow], axis=1)
-        fill = np.array([random.randint(0, 255) for _ in range(3 * len(corners))], dtype=np.uint8).reshape(-1, 3)
+        g = crop_geometry(gt_bboxes, img_shape, self.pad_ratio, self.small_object_size)
+        fill = draw_fill_colours(random, len(g.corners))
         canvases = []
-        for g, (w, h) in enumerate(canvas_wh):
+        for k, (w, h) in enumerate(g.canvas_wh):
             canvas = np.empty((h, w, 3), dtype=np.uint8)
-            canvas[...] = fill[g]
-            canvas[dst_lo[g, 1]:dst_hi[g, 1], dst_lo[g, 0]:dst_hi[g, 0]] = img[src_lo[g, 1]:src_hi[g, 1], src_lo[g, 0]:src_hi[g, 0]]
+            canvas[...] = fill[k]
+            canvas[g.dst_lo[k, 1]:g.dst_hi[k, 1], g.dst_lo[k, 0]:g.dst_hi[k, 0]] = \
+                img[g.src_lo[k, 1]:g.src_hi[k, 1], g.src_lo[k, 0]:g.src_hi[k, 0]]
             canvases.append(canvas)
-        return canvases, large, regions
+        return canvases, g.large, g.regions
+
+    def plan(self, s, rnd, nprnd):
+        """host part inside an image pipeline (after RandomFlip): the crop geometry of the sample's resized / flipped boxes
+        and the fill colours, drawn from the sample's `random` stream where the reference's random.randint calls fall.
+        The device part (ImagePipeline.run) cuts the canvases from the augmented image."""
+        if self.with_gt_mask:
+            return
+        g = crop_geometry(s["gt_bboxes"], s["img_shape"][:2], self.pad_ratio, self.small_object_size)
+        s["_crop_plan"] = (g, draw_fill_colours(rnd, len(g.corners)))
 
     def forward_wo_gt_mask(self, results):
         """loading.py:586-645: distance maps of the padded box crops, pasted back at the (truncated) box positions of

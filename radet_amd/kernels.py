@@ -1566,6 +1566,25 @@ def augment_box(src, params2, dst, n, max_h, max_w):
               _stream())
 
 
+# ---------------------------------------------------------------------- mask-free sampler inside the image pipeline
+CROP_DESC_INTS = 12
+PASTE_DESC_INTS = 10
+
+
+def crop_canvases(src, lsum, params, nimg, desc, n, max_px, dst):
+    """the padded box crops of a batch cut from the augmented image (src / lsum / params: what augment_finish reads);
+    desc i32 [n, CROP_DESC_INTS]; dst u8 [sum h * w * 3], the canvases back to back"""
+    _lib.call("radet_crop_canvases", _ptr(src), C.c_size_t(src.numel()), _ptr(lsum), _ptr(params), nimg, _ptr(desc), n, max_px,
+              _ptr(dst), C.c_size_t(dst.numel() // 3), _stream())
+
+
+def paste_maps(maps, desc, n, H, W, out):
+    """packed f32 / f64 distance maps -> out f32 [n, H, W] (zero fill and paste in one pass); desc i32 [n, PASTE_DESC_INTS]"""
+    assert maps.dtype in (torch.float32, torch.float64) and out.dtype == torch.float32 and out.numel() == n * H * W
+    _lib.call("radet_paste_maps", _ptr(maps), C.c_size_t(maps.numel()), 1 if maps.dtype == torch.float64 else 0, _ptr(desc), n,
+              H, W, _ptr(out), _stream())
+
+
 # ---------------------------------------------------------------------- COCO-protocol evaluation (csrc/cocoeval.hip)
 COCO_MAX_GT = 512                  # RADET_COCO_MAX_GT of include/radet_hip.h: ground truths per (category, image) segment
 COCO_ERR_OVERSIZE = -3             # RADET_ERR_COCO_OVERSIZE

@@ -1,6 +1,8 @@
 """radet.ops-compatible entry points (radet/ops/__init__.py:1-11 of the reference), executed by the
 HIP NMS kernel (radet_amd/csrc/decode_nms.hip).  Inputs may be CPU / GPU tensors or ndarrays; results come
 back on the input's device, same shapes / dtypes / ordering as the reference's C++ ops."""
+import functools
+
 import numpy as np
 import torch
 
@@ -125,23 +127,53 @@ def border_seeds(h, w, interval=3):
     return sx, sy
 
 
-def _pack_crops(items, seeds, dtype, chans):
-    """items: list of [h, w(, 3)] arrays/tensors; seeds: list of (sx, sy). -> packed device buffers + descriptor"""
-    dev = _dev()
-    desc, px, so = [], 0, 0
-    flat, sxs, sys_ = [], [], []
-    for it, (sx, sy) in zip(items, seeds):
-        t = torch.as_tensor(it)
-        h, w = int(t.shape[0]), int(t.shape[1])
-        assert h >= 2 and w >= 2 and (t.dim() == 3 and t.shape[2] == 3 if chans == 3 else t.dim() == 2)
-        sx, sy = torch.as_tensor(sx).reshape(-1).to(torch.int32), torch.as_tensor(sy).reshape(-1).to(torch.int32)
-        desc += [px, h, w, so, int(sx.numel())]
-        flat.append(t.to(dtype).reshape(-1))
+def _upload(array, dev):
+    """host ndarray -> device tensor through pinned memory, without blocking the host (the device chain of the mask-free
+    sampler reads nothing back and waits for nothing)"""
+    t = torch.from_numpy(np.ascontiguousarray(array))
+    if not t.numel():
+        return torch.empty(t.shape, dtype=t.dtype, device=dev)
+    return t.pin_memory().to(dev, non_blocking=True)
+
+
+@functools.lru_cache(maxsize=4096)
+def _border_seeds_np(h, w, interval):
+    sx, sy = border_seeds(h, w, interval)
+    return sx.numpy().astype(np.int32), sy.numpy().astype(np.int32)
+
+
+def _seed_desc(p, seeds):
+    """distance-kernel descriptor rows (pixel offset, h, w, first seed, seeds) of a _Packed and its per-crop seeds"""
+    sxs, sys_, desc, so = [], [], [], 0
+    for o, (h, w), (sx, sy) in zip(p.offs, p.hw, seeds):
+        assert h >= 2 and w >= 2
+        sx = (sx.cpu().numpy() if isinstance(sx, torch.Tensor) else np.asarray(sx)).reshape(-1).astype(np.int32)
+        sy = (sy.cpu().numpy() if isinstance(sy, torch.Tensor) else np.asarray(sy)).reshape(-1).astype(np.int32)
+        desc.append((o, h, w, so, sx.size))
         sxs.append(sx); sys_.append(sy)
-        px += h * w
-        so += int(sx.numel())
-    return (torch.cat(flat).to(dev), torch.tensor(desc, dtype=torch.int32).to(dev), torch.cat(sxs).to(dev),
-            torch.cat(sys_).to(dev), px, [(d[1], d[2]) for d in zip(*[iter(desc)] * 5)])
+        so += sx.size
+    dev = p.data.device
+    return (_upload(np.array(desc, np.int32), dev), _upload(np.concatenate(sxs), dev), _upload(np.concatenate(sys_), dev))
+
+
+def _mbd_packed(p, seeds, alpha=0.1, niter=4, base_size=300):
+    """u8 HWC crops (_Packed) -> f64 maps packed at the same offsets"""
+    out = p.empty_like(dtype=torch.float64, channels=1)
+    if len(p.hw):
+        desc, sx, sy = _seed_desc(p, seeds)
+        ws = torch.empty(K.mbd_ws_bytes(p.px), dtype=torch.uint8, device=p.data.device)
+        K.mbd(p.data, desc, len(p.hw), sx, sy, float(alpha), int(niter), int(base_size), out.data, p.px, ws)
+    return out
+
+
+def _gdt_packed(p, seeds):
+    """f32 cost maps (_Packed) -> f32 distances packed at the same offsets"""
+    out = p.empty_like()
+    if len(p.hw):
+        desc, sx, sy = _seed_desc(p, seeds)
+        ws = torch.empty(p.px, dtype=torch.int32, device=p.data.device)
+        K.gdt(p.data, desc, len(p.hw), sx, sy, out.data, ws)
+    return out
 
 
 def mbd_batch(images, seeds, alpha=0.1, niter=4, base_size=300):
@@ -149,30 +181,14 @@ def mbd_batch(images, seeds, alpha=0.1, niter=4, base_size=300):
     Returns a list of f64 [h, w] device tensors == bbox2distance_ext.MBD per crop (bit-identical)."""
     if not len(images):
         return []
-    img, desc, sx, sy, px, hw = _pack_crops(images, seeds, torch.uint8, 3)
-    dmap = torch.empty(px, dtype=torch.float64, device=img.device)
-    ws = torch.empty(K.mbd_ws_bytes(px), dtype=torch.uint8, device=img.device)
-    K.mbd(img, desc, len(images), sx, sy, float(alpha), int(niter), int(base_size), dmap, px, ws)
-    out, o = [], 0
-    for h, w in hw:
-        out.append(dmap[o:o + h * w].view(h, w))
-        o += h * w
-    return out
+    return _mbd_packed(_Packed.pack(images, torch.uint8, 3), seeds, alpha, niter, base_size).unpack()
 
 
 def gdt_batch(costs, seeds):
     """Geodesic distance transforms of a list of f32 [h, w] cost maps; == bbox2distance_ext.GDT per map."""
     if not len(costs):
         return []
-    cost, desc, sx, sy, px, hw = _pack_crops(costs, seeds, torch.float32, 1)
-    dist = torch.empty(px, dtype=torch.float32, device=cost.device)
-    ws = torch.empty(px, dtype=torch.int32, device=cost.device)
-    K.gdt(cost, desc, len(costs), sx, sy, dist, ws)
-    out, o = [], 0
-    for h, w in hw:
-        out.append(dist[o:o + h * w].view(h, w))
-        o += h * w
-    return out
+    return _gdt_packed(_Packed.pack(costs, torch.float32, 1), seeds).unpack()
 
 
 def MBD(image, seeds_x, seeds_y, alpha, niter, base_size):
@@ -187,17 +203,20 @@ def GDT(costmap, seeds_x, seeds_y):
 
 # ---------------------------------------------------------------------------------------------- image processing (packed crops)
 class _Packed:
-    """box crops of one call packed back to back on the device: data [sum h*w (* c)], desc i32 [n, 3] = (pixel offset, h, w)"""
+    """box crops of one call packed on the device: data [px (* c)], desc i32 [n, 3] = (pixel offset, h, w).  Crops lie back
+    to back unless `offs` says where they start (a selection out of a larger pack shares its data)."""
 
-    def __init__(self, data, hw, channels):
+    def __init__(self, data, hw, channels, offs=None, desc=None):
         self.data, self.hw, self.c = data, [(int(h), int(w)) for h, w in hw], channels
-        offs, o = [], 0
-        for h, w in self.hw:
-            offs.append(o)
-            o += h * w
-        self.offs, self.px = offs, o
-        self.desc = torch.tensor([[o_, h, w] for o_, (h, w) in zip(offs, self.hw)], dtype=torch.int32,
-                                 device=data.device).reshape(-1, 3).contiguous()
+        if offs is None:
+            offs, o = [], 0
+            for h, w in self.hw:
+                offs.append(o)
+                o += h * w
+        self.offs = [int(o) for o in offs]
+        self.px = max([o + h * w for o, (h, w) in zip(self.offs, self.hw)], default=0)      # pixels the crops span
+        self.desc = desc if desc is not None else _upload(
+            np.array([[o_, h, w] for o_, (h, w) in zip(self.offs, self.hw)], np.int32).reshape(-1, 3), data.device)
         self.max_px = max([h * w for h, w in self.hw], default=0)
 
     @staticmethod
@@ -209,9 +228,16 @@ class _Packed:
         flat = torch.cat([t.reshape(-1) for t in ts]) if ts else torch.empty(0, dtype=dtype, device=dev)
         return _Packed(flat.contiguous(), [t.shape[:2] for t in ts], channels)
 
+    def select(self, idx):
+        """the crops idx of this pack, in place"""
+        return _Packed(self.data, [self.hw[i] for i in idx], self.c, offs=[self.offs[i] for i in idx])
+
     def empty_like(self, hw=None, dtype=None, channels=None):
-        hw = self.hw if hw is None else hw
+        """uninitialised pack of other sizes (back to back), or of the same crops at the same offsets"""
         c = self.c if channels is None else channels
+        if hw is None:
+            return _Packed(torch.empty(self.px * c, dtype=dtype or self.data.dtype, device=self.data.device), self.hw, c,
+                           offs=self.offs, desc=self.desc)
         n = sum(int(h) * int(w) for h, w in hw) * c
         return _Packed(torch.empty(n, dtype=dtype or self.data.dtype, device=self.data.device), hw, c)
 
@@ -271,16 +297,25 @@ def sobel_edge_batch(images):
     return _sobel(_Packed.pack(images, torch.uint8, 3)).unpack()
 
 
-def _center_prepare(box_images, idx, size):
-    """mode='center': short edge -> `size` pixels (cv2.resize), then the 9x9 Gaussian (wrapper.py:80-88 / 170-177)"""
+def _center_prepare(p, size):
+    """mode='center': short edge -> `size` pixels (cv2.resize), then the 9x9 Gaussian (wrapper.py:80-88 / 170-177);
+    p: _Packed u8 HWC crops.  Returns (blurred _Packed, the crops' own (w, h))"""
     orig, dsz = [], []
-    for i in idx:
-        h, w = box_images[i].shape[:2]
+    for h, w in p.hw:
         ratio = size / min(w, h)
         dsz.append((int(w * ratio), int(h * ratio)))
         orig.append((w, h))
-    p = _Packed.pack([box_images[i] for i in idx], torch.uint8, 3)
     return _blur9(_resize(p, dsz)), orig
+
+
+def _cropped(box_images, mask_enable, bbox_images_xy, maps, idx, ones_dtype):
+    """the wrappers' return value: per box its region of its map, ones for a disabled box"""
+    maps = dict(zip(idx, maps.unpack()))
+    out = []
+    for i, (img, xy) in enumerate(zip(box_images, bbox_images_xy)):
+        d = maps[i] if i in maps else torch.ones(tuple(img.shape[:2]), dtype=ones_dtype, device=_dev())
+        out.append(d[xy[1]:xy[-1], xy[0]:xy[2]])
+    return out
 
 
 class MBD_box2distance:
@@ -297,24 +332,22 @@ class MBD_box2distance:
         h, w = image.shape[:2]
         return MBD(image, *border_seeds(h, w, self.interval), self.alpha, self.niter, self.base_size)
 
-    def __call__(self, box_images, mask_enable, bbox_images_xy):
+    def packed_maps(self, canvases, mask_enable):
+        """canvases: _Packed of u8 HWC crops on the device -> (_Packed of the enabled crops' f64 maps, each of its crop's
+        size, and their indices).  Every size and seed follows from the crops' shapes: nothing is read back."""
         idx = [i for i, e in enumerate(mask_enable) if e]
+        p = canvases.select(idx)
         if self.mode == "center" and idx:
-            blurred, orig = _center_prepare(box_images, idx, self.size)
-            crops = blurred.unpack()
-            maps = mbd_batch(crops, [border_seeds(h, w, self.interval) for h, w in blurred.hw], self.alpha, self.niter,
-                             self.base_size)
-            maps = _resize(_Packed.pack(maps, torch.float64, 1), orig).unpack()
-        else:
-            maps = mbd_batch([box_images[i] for i in idx],
-                             [border_seeds(*box_images[i].shape[:2], self.interval) for i in idx], self.alpha, self.niter,
-                             self.base_size)
-        maps = dict(zip(idx, maps))
-        out = []
-        for i, (img, xy) in enumerate(zip(box_images, bbox_images_xy)):
-            d = maps[i] if i in maps else torch.ones(img.shape[:2], dtype=torch.uint8, device=_dev())
-            out.append(d[xy[1]:xy[-1], xy[0]:xy[2]])
-        return out
+            p, orig = _center_prepare(p, self.size)
+        maps = _mbd_packed(p, [_border_seeds_np(h, w, self.interval) for h, w in p.hw], self.alpha, self.niter, self.base_size)
+        if self.mode == "center" and idx:
+            maps = _resize(maps, orig)
+        return maps, idx
+
+    def __call__(self, box_images, mask_enable, bbox_images_xy):
+        idx = [i for i, e in enumerate(mask_enable) if e]          # (disabled crops never leave the host)
+        maps, _ = self.packed_maps(_Packed.pack([box_images[i] for i in idx], torch.uint8, 3), [True] * len(idx))
+        return _cropped(box_images, mask_enable, bbox_images_xy, maps, idx, torch.uint8)
 
 
 class GDT_box2distance:
@@ -333,27 +366,33 @@ class GDT_box2distance:
     def sobel_extract_edge(self, image):
         return sobel_edge_batch([image])[0]
 
-    def _edges(self, crops):
-        if self.extract_edge_func is not None:
-            return [torch.as_tensor(self.extract_edge_func(c.cpu().numpy() if isinstance(c, torch.Tensor) else c)) for c in crops]
-        return sobel_edge_batch(crops)
+    def _edges(self, p):
+        """_Packed u8 crops -> _Packed f32 cost maps at the same offsets (a host callback reads the crops back)"""
+        if self.extract_edge_func is None:
+            return _sobel(p)
+        out = p.empty_like(dtype=torch.float32, channels=1)
+        for o, (h, w), c in zip(p.offs, p.hw, p.unpack()):
+            out.data[o:o + h * w] = torch.as_tensor(self.extract_edge_func(c.cpu().numpy())).to(out.data.device, torch.float32).reshape(-1)
+        return out
 
     def cal_dmap_single_scale(self, box_image):
         h, w = box_image.shape[:2]
-        return GDT(self._edges([box_image])[0], *border_seeds(h, w, self.interval))
+        cost = self._edges(_Packed.pack([box_image], torch.uint8, 3)).unpack()[0]
+        return GDT(cost, *border_seeds(h, w, self.interval))
+
+    def packed_maps(self, canvases, mask_enable):
+        """canvases: _Packed of u8 HWC crops on the device -> (_Packed of the enabled crops' f32 maps, their indices); with
+        the Sobel extractor nothing is read back"""
+        idx = [i for i, e in enumerate(mask_enable) if e]
+        p = canvases.select(idx)
+        if self.mode == "center" and idx:
+            p, orig = _center_prepare(p, self.size)
+        maps = _gdt_packed(self._edges(p), [_border_seeds_np(h, w, self.interval) for h, w in p.hw])
+        if self.mode == "center" and idx:
+            maps = _resize(maps, orig)
+        return maps, idx
 
     def __call__(self, box_images, mask_enable, bbox_images_xy):
-        idx = [i for i, e in enumerate(mask_enable) if e]
-        if self.mode == "center" and idx:
-            blurred, orig = _center_prepare(box_images, idx, self.size)
-            maps = gdt_batch(self._edges(blurred.unpack()), [border_seeds(h, w, self.interval) for h, w in blurred.hw])
-            maps = _resize(_Packed.pack(maps, torch.float32, 1), orig).unpack()
-        else:
-            maps = gdt_batch(self._edges([box_images[i] for i in idx]),
-                             [border_seeds(*box_images[i].shape[:2], self.interval) for i in idx])
-        maps = dict(zip(idx, maps))
-        out = []
-        for i, (img, xy) in enumerate(zip(box_images, bbox_images_xy)):
-            d = maps[i] if i in maps else torch.ones(img.shape[:2], dtype=torch.float32, device=_dev())
-            out.append(d[xy[1]:xy[-1], xy[0]:xy[2]])
-        return out
+        idx = [i for i, e in enumerate(mask_enable) if e]          # (disabled crops never leave the host)
+        maps, _ = self.packed_maps(_Packed.pack([box_images[i] for i in idx], torch.uint8, 3), [True] * len(idx))
+        return _cropped(box_images, mask_enable, bbox_images_xy, maps, idx, torch.float32)

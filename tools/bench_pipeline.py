@@ -4,6 +4,11 @@
                                                                    # (run it under `rocprofv3 --kernel-trace --stats`)
     python tools/bench_pipeline.py --part decode                   # host planning (decode + draws) per thread count
     python tools/bench_pipeline.py --part train [--steps 60]       # r50_ycbv_pbr fp32 bs 16: loader-fed vs one prebuilt batch
+    python tools/bench_pipeline.py --part maskfree [--iters 7]     # GenerateDistanceMap(with_gt_mask=False), gdt-sobel and mbd:
+                                                                   # the batched device chain vs per-sample host calls vs masks
+                                                                   # (one GPU step: run it under its own time limit,
+                                                                   #  timeout -k 10 400 python tools/bench_pipeline.py --part
+                                                                   #  maskfree --out profiles/bench_pipeline_maskfree.json)
 `--pipeline mix` runs the mixpbr train pipeline instead (RandomHSV / RandomNoise / RandomSmooth in place of CosyPoseAug,
 the training set a MixDataset of the tree twice, ratios 2 and 1).
 Each part prints one JSON line (and writes it to --out if given)."""
@@ -137,9 +142,113 @@ def part_train(args, root):
                 replays=(rt.tape_stats() or {}).get("replays"))
 
 
+MASK_FREE = dict(gdt=dict(type="GenerateDistanceMap", with_gt_mask=False, distance_transform="gdt", edge_mode="sobel"),
+                 mbd=dict(type="GenerateDistanceMap", with_gt_mask=False, distance_transform="mbd"))
+
+
+def _median_ms(fn, iters):
+    import torch
+    fn()                                                    # warm-up (allocator, pinned staging, code objects)
+    fn()
+    times = []
+    for _ in range(iters):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(times)), times
+
+
+def part_maskfree(args, root):
+    """bs 16, 640 x 480, 6 boxes per image.  Per transform: (a) the batched chain crop -> pasted maps
+    (ImagePipeline._distance_maps), (b) GenerateDistanceMap.__call__ per sample on host copies of the same augmented
+    images (the only way to these maps before the chain existed), (c) the mask pipeline's whole batch; and the chain's
+    time per entry point, each launch timed between two device synchronisations."""
+    import torch
+    from radet_amd import _lib, kernels as K
+    from radet_amd.datasets import PIPELINES, build_dataset
+    from radet_amd.datasets.loader import sample_generators
+    from radet_amd.utils import build_from_cfg
+    tree = write_tree(root, n_frames=16, objects=(6, 6), seed=0)
+    train, _ = pipelines(tree["background_dir"])
+    at = [t["type"] for t in train].index("GenerateDistanceMap")
+    if args.pipeline == "mix":
+        train = train[:4] + MIX_STAGES + train[5:]
+        at = [t["type"] for t in train].index("GenerateDistanceMap")
+
+    def build(dm):
+        return build_dataset(dict(type="BOPDataset", ann_file=tree["ann_file"], img_prefix=tree["img_prefix"],
+                                  seg_prefix=tree["seg_prefix"], pipeline=train[:at] + [dm] + train[at + 1:]))
+
+    def plan(ds):
+        return [ds.plan_sample(i, *sample_generators(0, 0, i)) for i in range(16)]
+    mask_ds = build(dict(type="GenerateDistanceMap"))
+    mask_plan = plan(mask_ds)
+    mask_ms, _ = _median_ms(lambda: mask_ds.pipeline.run(_fresh(mask_plan), collate=True), args.iters)
+    res = dict(part="maskfree", pipeline=args.pipeline, batch=16, iters=args.iters, mask_pipeline_ms=mask_ms)
+    for name, dm in MASK_FREE.items():
+        ds = build(dm)
+        pipe, planned = ds.pipeline, plan(ds)
+        nbox = sum(len(s["gt_bboxes"]) for s in planned)
+        grabbed, inner = [], pipe._distance_maps
+        pipe._distance_maps = lambda *a: grabbed.append(a) or inner(*a)
+        pipe.run(_fresh(planned), collate=True)
+        del pipe._distance_maps
+        chain_args = grabbed[0]
+        chain_ms, _ = _median_ms(lambda: pipe._distance_maps(*chain_args), args.iters)
+        run_ms, _ = _median_ms(lambda: pipe.run(_fresh(planned), collate=True), args.iters)
+        # host copies of the augmented images: one canvas per image that covers it
+        _, hw, img, lsum, params, dev = chain_args
+        D = np.zeros((16, K.CROP_DESC_INTS), np.int32)
+        o = 0
+        for i, (h, w) in enumerate(hw):
+            D[i] = [i, 0, 0, w, h, 0, 0, w, h, 0, o, 0]
+            o += h * w
+        full = torch.empty(o * 3, dtype=torch.uint8, device=dev)
+        K.crop_canvases(img, lsum, params, 16, torch.from_numpy(D).to(dev), 16, max(h * w for h, w in hw), full)
+        host, o = [], 0
+        for h, w in hw:
+            host.append(full[o * 3:(o + h * w) * 3].view(h, w, 3).cpu().numpy())
+            o += h * w
+        gdm = build_from_cfg(dm, PIPELINES)
+
+        def per_sample():
+            return [gdm(dict(img=im, img_shape=im.shape, gt_bboxes=s["gt_bboxes"]))["distance_maps"] for im, s in zip(host, planned)]
+        host_ms, _ = _median_ms(per_sample, args.iters)
+        # the chain's entry points one by one (synchronised: the sum exceeds the chain's own time by the lost overlap)
+        by_name, call = {}, _lib.call
+
+        def timed(fn_name, *a):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = call(fn_name, *a)
+            torch.cuda.synchronize()
+            by_name.setdefault(fn_name, []).append((time.perf_counter() - t0) * 1e3)
+            return out
+        pipe._distance_maps(*chain_args)
+        _lib.call = timed
+        try:
+            for _ in range(args.iters):
+                pipe._distance_maps(*chain_args)
+        finally:
+            _lib.call = call
+        launches = {k: dict(calls_per_batch=len(v) // args.iters, ms_per_batch=float(np.sum(v) / args.iters)) for k, v in by_name.items()}
+        res[name] = dict(boxes=nbox, transformed=int(sum(s["_crop_plan"][0].large.sum() for s in planned)),
+                         chain_ms=chain_ms, per_sample_host_ms=host_ms, chain_over_per_sample=chain_ms / host_ms,
+                         chain_share_of_mask_pipeline=chain_ms / mask_ms, maskfree_pipeline_ms=run_ms, entry_points=launches)
+    return res
+
+
+def _fresh(planned):
+    """the planned samples with copies of their RandomStates (the assigner advances them)"""
+    import copy
+    return [dict(s, _nprnd=copy.deepcopy(s["_nprnd"])) for s in planned]
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("kernels", "decode", "train"), required=True)
+    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree"), required=True)
     ap.add_argument("--pipeline", choices=("pbr", "mix"), default="pbr")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=60)
@@ -149,7 +258,7 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as root:
-        res = dict(kernels=part_kernels, decode=part_decode, train=part_train)[args.part](args, root)
+        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree)[args.part](args, root)
     line = json.dumps(res)
     print(line)
     if args.out:

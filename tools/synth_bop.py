@@ -24,19 +24,23 @@ def _image(rng, h, w):
     return np.clip(base + rng.normal(0, 12, base.shape), 0, 255).astype(np.uint8)
 
 
-def write_tree(root, n_frames=8, objects=(3, 6), size=(640, 480), n_backgrounds=3, seed=0, quality=90):
+def write_tree(root, n_frames=8, objects=(3, 6), size=(640, 480), n_backgrounds=3, seed=0, quality=90, sizes=None,
+               empty_frames=(), small_frames=()):
+    """sizes: (w, h) per frame, cycled (default: `size` for all); empty_frames: frames without objects; small_frames: frames
+    whose objects are 8 .. 20 pixels wide and high (below GenerateDistanceMap's small_object_size)"""
     from PIL import Image
     rng = np.random.RandomState(seed)
-    w, h = size
     scene = os.path.join(root, "train_pbr", "000000")
     os.makedirs(os.path.join(scene, "rgb"), exist_ok=True)
     os.makedirs(os.path.join(scene, "mask_visib"), exist_ok=True)
     images, anns = [], []
     for f in range(n_frames):
+        w, h = sizes[f % len(sizes)] if sizes else size
         Image.fromarray(_image(rng, h, w)).save(os.path.join(scene, "rgb", f"{f:06d}.jpg"), quality=quality)
         images.append(dict(id=f + 1, file_name=f"000000/rgb/{f:06d}.jpg", width=w, height=h))
-        for i in range(rng.randint(objects[0], objects[1] + 1)):
-            bw, bh = rng.randint(w // 10, w // 3), rng.randint(h // 10, h // 3)
+        for i in range(0 if f in empty_frames else rng.randint(objects[0], objects[1] + 1)):
+            bw, bh = (rng.randint(8, 21), rng.randint(8, 21)) if f in small_frames else \
+                (rng.randint(w // 10, w // 3), rng.randint(h // 10, h // 3))
             x0, y0 = rng.randint(0, w - bw), rng.randint(0, h - bh)
             yy, xx = np.mgrid[0:h, 0:w]
             inside = ((xx - x0 - bw / 2) / (bw / 2)) ** 2 + ((yy - y0 - bh / 2) / (bh / 2)) ** 2 <= 1.0
