@@ -474,6 +474,22 @@ int radet_mask_max(const uint8_t* masks, uint32_t* maxes /* [G] */, int G, size_
 int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, int G, int Hs, int Ws, int Hr, int Wr,
                          int Hd, int Wd, int flip, int pad_val, void* stream);
 
+/* ---- the same masks from run-length annotations (COCO RLE / rasterised polygons, radet/datasets/pipelines/loading.py:313-380
+ *      `_poly2mask`), without a bitmap on the host or in HBM: one launch per group of masks of one destination geometry.
+ *      A mask is the union of its parts; a part is a COCO run list over the source image in column-major order (first run
+ *      zeros).  run_ends u32 [n_ends]: the inclusive prefix sums of every part's counts, part after part (a part's last
+ *      entry is Hs * Ws < 2^32).  part_desc i32 [n_parts][RLE_PART_INTS] = {offset into run_ends, runs};
+ *      mask_desc i32 [G][RLE_MASK_INTS] = {first part, parts, Hs, Ws, flip (bit 0: horizontal)}.
+ *      dst u8 [G,Hd,Wd]: what radet_mask_transform writes for the decoded 0 / 1 bitmap with the mask's own flip:
+ *      dst[g][y][x] = y < Hr && x < Wr ? OR over parts of (index of the run that holds nn(flip_x(x)) * Hs + nn(y)) & 1 : pad_val.
+ *      dst_plain (may be NULL) u8 [G,Hd,Wd]: the unflipped mask, written ONLY for masks whose flip bit is set (for the
+ *      others dst already is that mask): both orientations from one lookup.  Rows that point outside the tables decode as
+ *      empty.  Wd <= 8192, G <= 65535. */
+#define RLE_MASK_INTS 5
+#define RLE_PART_INTS 2
+int radet_rle_masks(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc, int G,
+                    uint8_t* dst, uint8_t* dst_plain, int Hr, int Wr, int Hd, int Wd, int pad_val, void* stream);
+
 /* ---- BOP training-image augmentation (csrc/augment.hip): RandomBackground merge, CosyPoseAug's PillowBlur /
  *      PillowSharpness / PillowContrast / PillowBrightness / PillowColor, RandomFlip, Normalize, Pad, batched over packed
  *      u8 HWC BGR images (every buffer packed alike).  params (device) = nimg rows of AUG_PARAM_INTS ints:

@@ -39,6 +39,34 @@ class BitmapMasks:
             m = torch.from_numpy(np.ascontiguousarray(arr.astype(np.uint8))).to(dev)
         self.masks = m.reshape(-1, self.height, self.width).contiguous()
 
+    @classmethod
+    def from_rle(cls, parts_per_mask, height, width, resized_hw=None, flip=None, out_hw=None, pad_val=0, device=None):
+        """Masks given as run lists (per mask a list of parts, each a COCO counts array over height x width; the parts of a
+        mask are united), decoded on the device straight to the resized -> flipped -> padded bitmaps of `transform`:
+        one launch, no bitmap on the host.  flip: None / 'horizontal', or one bool per mask."""
+        from . import rle
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        G = len(parts_per_mask)
+        if isinstance(flip, str) or flip is None:
+            if flip not in (None, "none", "horizontal"):
+                raise NotImplementedError(f"BitmapMasks.from_rle(flip={flip!r}): run-length masks flip horizontally")
+            flip = [flip == "horizontal"] * G
+        Hr, Wr = resized_hw or (int(height), int(width))
+        Hd, Wd = out_hw or (Hr, Wr)
+        if Wd > K.RLE_MAX_W or Hd < Hr or Wd < Wr:
+            raise ValueError(f"BitmapMasks.from_rle: destination {Hd} x {Wd} for a resized mask of {Hr} x {Wr} "
+                             f"(width up to {K.RLE_MAX_W})")
+        ends, prows, mrows = rle.pack_runs(parts_per_mask, height, width, flip)
+        packed = np.concatenate([ends.view(np.int32), prows.reshape(-1), mrows.reshape(-1)])
+        if packed.size:
+            packed = torch.from_numpy(packed).pin_memory().to(dev, non_blocking=True)
+        else:
+            packed = torch.empty(0, dtype=torch.int32, device=dev)
+        a, b = ends.size, ends.size + prows.size
+        out = K.rle_masks(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:].view(-1, K.RLE_MASK_INTS), (Hd, Wd),
+                          (Hr, Wr), pad_val)
+        return cls(out, Hd, Wd, device=dev)
+
     def __len__(self):
         return self.masks.shape[0]
 

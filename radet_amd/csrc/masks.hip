@@ -4,6 +4,7 @@
 // (cv2.INTER_NEAREST) / np.flip / np.pad per mask on the host) and radet/datasets/pipelines/loading.py:419-422.
 // HBM-bound byte work: every output byte is written once (4 per thread, one 32-bit store when the row allows),
 // every source byte is read at most ~once (rows are walked contiguously).
+// radet_rle_masks produces the same bytes from run-length annotations: no bitmap is uploaded, no maximum is taken.
 #include "common.h"
 #include "radet_hip.h"
 
@@ -57,6 +58,96 @@ __global__ __launch_bounds__(256) void mask_transform_kernel(const uint8_t* __re
     }
 }
 
+// Number of run ends <= p among ends[lo, n) (ends ascending): the index of the run that holds position p.
+__device__ __forceinline__ int rle_run_of(const uint32_t* __restrict__ ends, int lo, int n, uint32_t p) {
+    int hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (ends[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One workgroup per destination row of one mask.  A thread owns 4 adjacent pixels: their source positions sx * Hs + sy
+// ascend with x, so each part is searched once (binary, over its run ends) and the search for the next pixel starts at the
+// run found last -- one compare when it is the same run.  The packed row goes to LDS; from there the mirrored copy is
+// composed, so both orientations leave as aligned 32-bit stores and the runs are looked up once.
+#define RLE_MAX_W 8192
+__global__ __launch_bounds__(256) void rle_masks_kernel(const uint32_t* __restrict__ run_ends, int n_ends,
+                                                        const int* __restrict__ part_desc, int n_parts,
+                                                        const int* __restrict__ mask_desc, uint8_t* __restrict__ dst,
+                                                        uint8_t* __restrict__ dst_plain, int Hr, int Wr, int Hd, int Wd,
+                                                        int pad_val) {
+    __shared__ unsigned row[RLE_MAX_W / 4 + 1];
+    const int g = blockIdx.y, y = blockIdx.x;
+    const int* md = mask_desc + (size_t)g * RLE_MASK_INTS;
+    const int first = md[0], Hs = md[2], Ws = md[3], flip = md[4] & 1;
+    int np = md[1];
+    if (first < 0 || np < 0 || first > n_parts - np || Hs <= 0 || Ws <= 0) np = 0;         // (a row that points outside the part table: no parts)
+    // OpenCV computes inv_scale = dsize / ssize and then 1. / inv_scale (not ssize / dsize)
+    const double ify = 1.0 / ((double)Hr / (double)Hs), ifx = 1.0 / ((double)Wr / (double)Ws);
+    const unsigned pad = (unsigned)pad_val & 0xFFu;
+    const int nwords = (Wd + 3) >> 2;
+    const bool inside = y < Hr;
+    const uint32_t sy = inside ? (uint32_t)nn_src(y, ify, Hs) : 0u;
+    for (int wd = threadIdx.x; wd < nwords; wd += blockDim.x) {
+        const int x0 = wd * 4;
+        unsigned out[4] = {pad, pad, pad, pad};
+        if (inside && x0 < Wr) {
+            uint32_t pos[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                out[j] = x0 + j < Wr ? 0u : pad;
+                pos[j] = (uint32_t)nn_src(min(x0 + j, Wr - 1), ifx, Ws) * (uint32_t)Hs + sy;
+            }
+            for (int k = 0; k < np; ++k) {
+                const int off = part_desc[(size_t)(first + k) * RLE_PART_INTS], n = part_desc[(size_t)(first + k) * RLE_PART_INTS + 1];
+                if (off < 0 || n <= 0 || off > n_ends - n) continue;
+                const uint32_t* e = run_ends + off;
+                int r = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (r < n && e[r] <= pos[j]) r = rle_run_of(e, r + 1, n, pos[j]);
+                    if (x0 + j < Wr) out[j] |= (unsigned)r & 1u;
+                }
+            }
+        }
+        row[wd] = out[0] | (out[1] << 8) | (out[2] << 16) | (out[3] << 24);
+    }
+    __syncthreads();
+    const uint8_t* rb = reinterpret_cast<const uint8_t*>(row);
+    uint8_t* dp = dst + ((size_t)g * Hd + y) * Wd;
+    uint8_t* pp = (dst_plain && flip) ? dst_plain + ((size_t)g * Hd + y) * Wd : nullptr;
+    for (int wd = threadIdx.x; wd < nwords; wd += blockDim.x) {
+        const int x0 = wd * 4;
+        unsigned v = row[wd];
+        if (pp) {
+            if ((Wd & 3) == 0) {
+                *reinterpret_cast<unsigned*>(pp + x0) = v;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (x0 + j < Wd) pp[x0 + j] = (uint8_t)(v >> (8 * j));
+            }
+        }
+        if (flip && inside) {                                        // flip acts on the resized image; the pad stays right
+            v = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = x0 + j;
+                v |= (unsigned)(x < Wr ? rb[Wr - 1 - x] : (uint8_t)pad) << (8 * j);
+            }
+        }
+        if ((Wd & 3) == 0) {
+            *reinterpret_cast<unsigned*>(dp + x0) = v;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < Wd) dp[x0 + j] = (uint8_t)(v >> (8 * j));
+        }
+    }
+}
+
 extern "C" int radet_mask_max(const uint8_t* masks, uint32_t* maxes, int G, size_t hw, void* stream) {
     if (G <= 0 || hw == 0) return RADET_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -75,5 +166,17 @@ extern "C" int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint
     const double ify = 1.0 / ((double)Hr / (double)Hs), ifx = 1.0 / ((double)Wr / (double)Ws);
     hipLaunchKernelGGL(mask_transform_kernel, dim3((Wd + 1023) / 1024, Hd, G), dim3(256), 0, (hipStream_t)stream, src, dst,
                        norm_max, Hs, Ws, Hr, Wr, Hd, Wd, ify, ifx, flip, pad_val);
+    return radet_check_launch();
+}
+
+extern "C" int radet_rle_masks(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc,
+                               int G, uint8_t* dst, uint8_t* dst_plain, int Hr, int Wr, int Hd, int Wd, int pad_val,
+                               void* stream) {
+    if (G <= 0 || G > 65535 || n_ends < 0 || n_parts < 0 || Hr <= 0 || Wr <= 0 || Hd < Hr || Wd < Wr || Wd > RLE_MAX_W)
+        return RADET_ERR_ARG;
+    const int nwords = (Wd + 3) / 4;
+    const int threads = nwords >= 256 ? 256 : ((nwords + 63) / 64) * 64;
+    hipLaunchKernelGGL(rle_masks_kernel, dim3(Hd, G), dim3(threads), 0, (hipStream_t)stream, run_ends, n_ends, part_desc, n_parts,
+                       mask_desc, dst, dst_plain, Hr, Wr, Hd, Wd, pad_val);
     return radet_check_launch();
 }

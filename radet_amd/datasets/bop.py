@@ -122,7 +122,13 @@ class BOPDataset:
     mask_path_template = "{:06d}/mask_visib/{:06}_{:06}.png"
 
     def __init__(self, ann_file, pipeline, classes=None, data_root=None, img_prefix="", bop_submission=False,
-                 seg_prefix=None, proposal_file=None, test_mode=False, min_visib_frac=0., filter_empty_gt=True):
+                 seg_prefix=None, proposal_file=None, test_mode=False, min_visib_frac=0., filter_empty_gt=True,
+                 mask_source="file"):
+        """mask_source: 'file' = one visible-mask PNG per object under seg_prefix (LoadAnnotations(with_bop_mask=True));
+        'annotation' = the records' `segmentation` objects (LoadAnnotations(with_mask=True))"""
+        if mask_source not in ("file", "annotation"):
+            raise ValueError(f"mask_source is 'file' or 'annotation', got {mask_source!r}")
+        self.mask_source = mask_source
         self.data_root, self.test_mode, self.filter_empty_gt = data_root, test_mode, filter_empty_gt
         self.ann_file = _under(data_root, ann_file)
         self.img_prefix = _under(data_root, img_prefix)
@@ -232,7 +238,8 @@ class BOPDataset:
         seg_map).  Dropped: `ignore` records, boxes outside the image, degenerate boxes (area <= 0 or a side < 1 px),
         unwanted classes.  Objects whose visible fraction is below `min_visib_frac` become ignore boxes.  The mask of the
         i-th record of the frame is '<scene>/mask_visib/<frame>_<i>.png' (i counts ALL records: the BOP file layout)."""
-        scene, frame = _bop_frame(img_info["filename"])
+        from_file = self.mask_source == "file"
+        scene, frame = _bop_frame(img_info["filename"]) if from_file else (None, None)
         n = len(ann_info)
         box = np.array([a["bbox"] for a in ann_info], dtype=np.float64).reshape(n, 4)
         x1, y1, w, h = box.T
@@ -248,7 +255,9 @@ class BOPDataset:
         return dict(bboxes=xyxy[pos].reshape(-1, 4),
                     labels=np.array([self.cat2label[ann_info[i]["category_id"]] for i in pos], dtype=np.int64),
                     bboxes_ignore=xyxy[usable & ~visible].reshape(-1, 4),
-                    masks=[self.mask_path_template.format(int(scene), frame, int(i)) for i in pos],
+                    masks=([self.mask_path_template.format(int(scene), frame, int(i)) for i in pos] if from_file
+                           else [ann_info[i].get("segmentation") for i in pos]),
+                    ann_ids=[ann_info[i].get("id", int(i)) for i in pos],
                     seg_map=img_info["filename"].replace("jpg", "png"))
 
     # ------------------------------------------------------------------ detections -> result files
@@ -439,6 +448,51 @@ class BOPDataset:
             out.update((f"{m}_{name}", stat(name)) for name in (items or _STAT_SLOT))
             out[f"{m}_mAP_copypaste"] = " ".join(f"{v:.3f}" for v in ev.stats[:6])
         return out
+
+
+COCO_CLASSES = ("person", "bicycle", "car", "motorcycle", "airplane", "bus", "train", "truck", "boat", "traffic light",
+                "fire hydrant", "stop sign", "parking meter", "bench", "bird", "cat", "dog", "horse", "sheep", "cow", "elephant",
+                "bear", "zebra", "giraffe", "backpack", "umbrella", "handbag", "tie", "suitcase", "frisbee", "skis", "snowboard",
+                "sports ball", "kite", "baseball bat", "baseball glove", "skateboard", "surfboard", "tennis racket", "bottle",
+                "wine glass", "cup", "fork", "knife", "spoon", "bowl", "banana", "apple", "sandwich", "orange", "broccoli",
+                "carrot", "hot dog", "pizza", "donut", "cake", "chair", "couch", "potted plant", "bed", "dining table", "toilet",
+                "tv", "laptop", "mouse", "remote", "keyboard", "cell phone", "microwave", "oven", "toaster", "sink",
+                "refrigerator", "book", "clock", "vase", "scissors", "teddy bear", "hair drier", "toothbrush")
+
+
+@DATASETS.register_module()
+class CocoDataset(BOPDataset):
+    """The reference's `CocoDataset` (radet/datasets/coco.py): any COCO-format detection file.  Loading, filtering, result
+    files and evaluation are BOPDataset's; the annotation parsing is coco.py:120-178 -- no BOP file layout, no visible
+    fraction: `iscrowd` records become ignore boxes, and `masks` are the `segmentation` objects of the kept records
+    (polygons, run lists or compressed run lists: LoadAnnotations(with_mask=True))."""
+    CLASSES = COCO_CLASSES
+
+    def __init__(self, ann_file, pipeline, classes=None, data_root=None, img_prefix="", seg_prefix=None, proposal_file=None,
+                 test_mode=False, filter_empty_gt=True):
+        super().__init__(ann_file, pipeline, classes=classes, data_root=data_root, img_prefix=img_prefix, seg_prefix=seg_prefix,
+                         proposal_file=proposal_file, test_mode=test_mode, filter_empty_gt=filter_empty_gt,
+                         mask_source="annotation")
+
+    def _parse_ann_info(self, img_info, ann_info):
+        n = len(ann_info)
+        box = np.array([a["bbox"] for a in ann_info], dtype=np.float64).reshape(n, 4)
+        x1, y1, w, h = box.T
+        x2, y2 = x1 + w, y1 + h
+        inside = (np.minimum(x2, img_info["width"]) - np.maximum(x1, 0)).clip(min=0) * \
+                 (np.minimum(y2, img_info["height"]) - np.maximum(y1, 0)).clip(min=0)
+        usable = np.array([not a.get("ignore", False) and a["area"] > 0 and a["category_id"] in self.cat2label
+                           for a in ann_info], dtype=bool).reshape(n)
+        usable &= (inside != 0) & (w >= 1) & (h >= 1)
+        crowd = np.array([bool(a.get("iscrowd", False)) for a in ann_info], dtype=bool).reshape(n)
+        xyxy = np.stack([x1, y1, x2, y2], axis=1).astype(np.float32)
+        pos = np.flatnonzero(usable & ~crowd)
+        return dict(bboxes=xyxy[pos].reshape(-1, 4),
+                    labels=np.array([self.cat2label[ann_info[i]["category_id"]] for i in pos], dtype=np.int64),
+                    bboxes_ignore=xyxy[usable & crowd].reshape(-1, 4),
+                    masks=[ann_info[i].get("segmentation") for i in pos],
+                    ann_ids=[ann_info[i].get("id", int(i)) for i in pos],
+                    seg_map=img_info["filename"].replace("jpg", "png"))
 
 
 @DATASETS.register_module()

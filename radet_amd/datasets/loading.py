@@ -6,7 +6,7 @@ arithmetic (NumPy, mmdet 2.x Resize / RandomFlip.bbox_flip) and every random dra
 sample's own generators (`rnd`: a random.Random or the `random` module, `nprnd`: a RandomState or `np.random`).  Planning
 touches no device, so the loader runs it on host threads.  `ImagePipeline.run(planned)` then does the device part of a
 whole batch on the calling thread and stream: the resize of images and backgrounds (radet_resize_linear_u8), mask
-normalisation / resize / flip (radet_mask_transform), the four augmentation launches of csrc/augment.hip (a mixpbr
+normalisation / resize / flip (radet_mask_transform; radet_rle_masks for masks annotated as run lists or polygons), the four augmentation launches of csrc/augment.hip (a mixpbr
 pipeline: merge, hsv_noise, box, finish), the box crops / distance maps of a mask-free GenerateDistanceMap
 (radet_crop_canvases, the ops' packed GDT / MBD chain, radet_paste_maps) and the label assigner -- a fixed number of
 launches whatever the batch size.  A single sample (`BOPDataset.__getitem__`) is a batch
@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from ..core import rle
 from ..core.mask import rescale_size
 from ..utils import build_from_cfg
 from .pipelines import PIPELINES, GenerateDistanceMap, LabelAssignment
@@ -100,9 +101,13 @@ class LoadImageFromFile:
 class LoadAnnotations:
     def __init__(self, with_bbox=True, with_label=True, with_mask=False, with_seg=False, with_bop_mask=False, poly2mask=True,
                  file_client_args=None):
-        if with_mask or with_seg:
-            _refuse("LoadAnnotations(with_mask / with_seg)")
-        self.with_bbox, self.with_label, self.with_bop_mask = with_bbox, with_label, with_bop_mask
+        if with_seg:
+            _refuse("LoadAnnotations(with_seg)")
+        if with_mask and not poly2mask:
+            _refuse("LoadAnnotations(with_mask=True, poly2mask=False) (PolygonMasks)")
+        if with_mask and with_bop_mask:
+            _refuse("LoadAnnotations(with_mask=True, with_bop_mask=True) (two sources for gt_masks)")
+        self.with_bbox, self.with_label, self.with_bop_mask, self.with_mask = with_bbox, with_label, with_bop_mask, with_mask
 
     def plan(self, s, rnd, nprnd):
         ann = s["ann_info"]
@@ -121,6 +126,15 @@ class LoadAnnotations:
                 if m.shape != (h, w):
                     raise ValueError(f"mask of shape {m.shape} for an image of {h} x {w}")
             s["gt_masks"] = np.stack(masks) if masks else np.zeros((0, h, w), np.uint8)
+            s["mask_fields"].append("gt_masks")
+        if self.with_mask:
+            # the `segmentation` objects of the annotation file (polygons, run lists, compressed run lists) as run lists:
+            # nothing is decoded to pixels here, radet_rle_masks does that for the whole batch (ImagePipeline._masks)
+            h, w = s["img_info"]["height"], s["img_info"]["width"]
+            ids = ann.get("ann_ids") or range(len(ann["masks"]))
+            name = s["img_info"].get("filename", s["img_info"].get("file_name"))
+            s["gt_masks_rle"] = ([rle.parts_from_segmentation(seg, h, w, f"{name}, record {k}") for seg, k in zip(ann["masks"], ids)],
+                                 (h, w))
             s["mask_fields"].append("gt_masks")
 
 
@@ -638,7 +652,40 @@ class ImagePipeline:
                 masks[i] = res[o:o + c]
                 flipped[i] = fl[o:o + c] if planned[i].get("flip") else masks[i]
                 o += c
+        self._rle_masks(planned, hw, dev, masks, flipped)
         return masks, flipped
+
+    @staticmethod
+    def _rle_masks(planned, hw, dev, masks, flipped):
+        """the same two lists for the samples whose masks arrive as run lists (LoadAnnotations(with_mask=True)): per group
+        of equal sizes one pinned upload of the run arrays and one radet_rle_masks launch that writes both orientations;
+        nothing waits for the device"""
+        groups = {}
+        for i, s in enumerate(planned):
+            if "gt_masks_rle" in s:
+                if "gt_masks" in s:
+                    raise ValueError("a sample carries both gt_masks and gt_masks_rle")
+                groups.setdefault((tuple(s["gt_masks_rle"][1]), hw[i]), []).append(i)
+        for (src_hw, dst_hw), idx in groups.items():
+            per_mask = [m for i in idx for m in planned[i]["gt_masks_rle"][0]]
+            counts = [len(planned[i]["gt_masks_rle"][0]) for i in idx]
+            if not per_mask:
+                for i in idx:
+                    masks[i] = flipped[i] = torch.zeros(0, *dst_hw, dtype=torch.uint8, device=dev)
+                continue
+            flips = np.repeat([bool(planned[i].get("flip")) for i in idx], counts)
+            ends, prows, mrows = rle.pack_runs(per_mask, *src_hw, flips)
+            packed = torch.from_numpy(np.concatenate([ends.view(np.int32), prows.reshape(-1), mrows.reshape(-1)]))
+            packed = packed.pin_memory().to(dev, non_blocking=True)
+            a, b = ends.size, ends.size + prows.size
+            res = K.rle_masks(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:].view(-1, K.RLE_MASK_INTS), dst_hw,
+                              with_plain=bool(flips.any()))
+            out, plain = res if flips.any() else (res, None)
+            o = 0
+            for i, c in zip(idx, counts):
+                flipped[i] = out[o:o + c]
+                masks[i] = plain[o:o + c] if planned[i].get("flip") else flipped[i]
+                o += c
 
     def _collect(self, planned, out, p2g, pw, collate):
         samples = []

@@ -1490,6 +1490,27 @@ def mask_transform(src, out_hw=None, resized_hw=None, flip=None, pad_val=0, norm
     return dst
 
 
+RLE_MASK_INTS, RLE_PART_INTS = 5, 2       # include/radet_hip.h
+RLE_MAX_W = 8192
+
+
+def rle_masks(run_ends, part_desc, mask_desc, out_hw, resized_hw=None, pad_val=0, with_plain=False):
+    """Run-length masks -> u8[G,Hd,Wd] in one launch (radet_amd.core.rle.pack_runs makes the three arrays): what
+    mask_transform(normalize=True) gives for the decoded bitmaps, each mask with the flip of its descriptor row.
+    run_ends: int32 / uint32 bit patterns [R]; part_desc i32 [P, 2]; mask_desc i32 [G, 5], all on the device.
+    with_plain: also returns the unflipped masks -- defined only for masks whose flip bit is set (the others are
+    unflipped in the first result)."""
+    G = mask_desc.shape[0]
+    Hd, Wd = out_hw
+    Hr, Wr = resized_hw or (Hd, Wd)
+    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=mask_desc.device)
+    plain = torch.empty_like(dst) if with_plain else None
+    if G:
+        _lib.call("radet_rle_masks", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc), G,
+                  _ptr(dst), _ptr(plain), Hr, Wr, Hd, Wd, int(pad_val), _stream())
+    return (dst, plain) if with_plain else dst
+
+
 def assign_points(gt_boxes, gt_off, masks, H, W, rng_words, U, ldesc, ranges, nlvl, B, positive_num, neg_thr, p2g, pw, used,
                   ws, flags=1):
     """masks: u8 [sumG, H, W] visible masks, or f32 per-box distance maps (mask-free sampler); rng_words: int32 / uint32 bit

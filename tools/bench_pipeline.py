@@ -9,6 +9,10 @@
                                                                    # (one GPU step: run it under its own time limit,
                                                                    #  timeout -k 10 400 python tools/bench_pipeline.py --part
                                                                    #  maskfree --out profiles/bench_pipeline_maskfree.json)
+    python tools/bench_pipeline.py --part rle [--iters 20]          # the same frames under PNG-path and RLE annotations:
+                                                                   # host plan, device mask stage, loader-fed training
+                                                                   # (timeout -k 10 500 python tools/bench_pipeline.py --part rle
+                                                                   #  --out profiles/bench_pipeline_rle.json)
 `--pipeline mix` runs the mixpbr train pipeline instead (RandomHSV / RandomNoise / RandomSmooth in place of CosyPoseAug,
 the training set a MixDataset of the tree twice, ratios 2 and 1).
 Each part prints one JSON line (and writes it to --out if given)."""
@@ -240,6 +244,138 @@ def part_maskfree(args, root):
     return res
 
 
+def _scatter(times):
+    t = np.asarray(times, np.float64)
+    return dict(median=float(np.median(t)), min=float(t.min()), max=float(t.max()), p25=float(np.percentile(t, 25)),
+                p75=float(np.percentile(t, 75)), n=int(t.size))
+
+
+def part_rle(args, root):
+    """bs 16, 640 x 480, 6 objects per image; one tree annotated twice (visible-mask PNG paths / run lists in the json).
+    (a) host plan per sample and images/s at 1 / 12 / 16 threads; (b) the device mask stage of one batch
+    (ImagePipeline._masks: upload + mask_max + mask_transform + flip, against upload + rle_masks), each call between two
+    device synchronisations, and the same with a device event pair; (c) loader-fed training images/s, as in --part train."""
+    import copy
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    from radet_amd.datasets import build_dataloader, build_dataset
+    from radet_amd.datasets.bop_convert import add_segmentation
+    from radet_amd.datasets.loader import sample_generators
+    tree = write_tree(root, n_frames=64, objects=(6, 6), seed=0)
+    ann = os.path.join(root, "train_pbr_rle.json")
+    with open(tree["ann_file"]) as f:
+        coco = add_segmentation(json.load(f), tree["seg_prefix"], "rle")
+    with open(ann, "w") as f:
+        json.dump(coco, f)
+    train, _ = pipelines(tree["background_dir"])
+    rle_train = copy.deepcopy(train)
+    rle_train[1] = dict(type="LoadAnnotations", with_bbox=True, with_mask=True)
+    ds = dict(png=build_dataset(dict(type="BOPDataset", ann_file=tree["ann_file"], img_prefix=tree["img_prefix"],
+                                     seg_prefix=tree["seg_prefix"], pipeline=train)),
+              rle=build_dataset(dict(type="BOPDataset", ann_file=ann, img_prefix=tree["img_prefix"], mask_source="annotation",
+                                     pipeline=rle_train)))
+    res = dict(part="rle", batch=16, iters=args.iters, frames=len(ds["png"]), masks_per_batch=96,
+               ann_file_bytes=dict(png=os.path.getsize(tree["ann_file"]), rle=os.path.getsize(ann)))
+    # (a) host planning
+    host = {}
+    for name, d in ds.items():
+        d.plan_sample(0, *sample_generators(0, 0, 0))
+        per = []
+        for i in range(len(d)):
+            t0 = time.perf_counter()
+            d.plan_sample(i, *sample_generators(0, 0, i))
+            per.append((time.perf_counter() - t0) * 1e3)
+        # the mask share alone: LoadAnnotations.plan on a sample whose image is already decoded
+        stage, only = d.pipeline.transforms[1], []
+        for i in range(len(d)):
+            s = d._results(i, True)
+            t0 = time.perf_counter()
+            stage.plan(s, None, None)
+            only.append((time.perf_counter() - t0) * 1e3)
+        rate = {}
+        for threads in (1, 12, 16):
+            with ThreadPoolExecutor(threads) as pool:
+                list(pool.map(lambda i: d.plan_sample(i, *sample_generators(0, 0, i)), range(threads)))
+                runs = []
+                for rep in range(3):
+                    t0 = time.perf_counter()
+                    list(pool.map(lambda i: d.plan_sample(i, *sample_generators(0, rep, i)), range(len(d))))
+                    runs.append(len(d) / (time.perf_counter() - t0))
+                rate[threads] = dict(median=float(np.median(runs)), runs=runs)
+        host[name] = dict(plan_ms_per_sample=_scatter(per), load_annotations_ms_per_sample=_scatter(only), images_per_s_by_threads=rate)
+    res["host"] = host
+    # (b) the device mask stage of one batch
+    dev_res = {}
+    for name, d in ds.items():
+        planned = [d.plan_sample(i, *sample_generators(0, 0, i)) for i in range(16)]
+        assert sum(len(s["gt_bboxes"]) for s in planned) == 96 and any(s["flip"] for s in planned)
+        hw = [tuple(s["resize_hw"]) for s in planned]
+        dev = d.pipeline._dev()
+        wall, evt = [], []
+        for it in range(args.iters + 3):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            d.pipeline._masks(planned, hw, dev)
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= 3:
+                wall.append((time.perf_counter() - t0) * 1e3)
+                evt.append(e0.elapsed_time(e1))
+        up = (sum(s["gt_masks"].nbytes for s in planned) if name == "png" else
+              4 * sum(c.size for s in planned for m in s["gt_masks_rle"][0] for c in m))
+        dev_res[name] = dict(wall_ms=_scatter(wall), event_ms=_scatter(evt), upload_bytes=int(up))
+    res["device_mask_stage"] = dev_res
+    # (c) loader-fed training
+    if args.steps > 0:
+        from oracle import synth
+        from radet_amd.models import build_detector
+        from radet_amd.utils import Config
+        cfg = Config.fromfile(os.path.join(ROOT, "configs", "bop", "r50_ycbv_pbr.py"))
+        cfg.model["pretrained"] = None
+        torch.manual_seed(0)
+        det = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
+        synth.fill_state_dict(det.state_dict(), seed=0)
+        det = det.cuda().train()
+        rt = det.runtime()
+        rt.init_optimizer(lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=35.0)
+        rt.set_loss_from_head(det.bbox_head)
+
+        def step(b):
+            tg = rt.pack_targets(b["gt_bboxes"], b["gt_labels"], b["points_to_gt_index"], b["points_weight"])
+            rt.train_step(b["img"], tg, lr=1e-4)
+        loaders = {k: build_dataloader(d, samples_per_gpu=16, workers=args.workers, seed=0) for k, d in ds.items()}
+
+        def stream(loader):
+            epoch = 0
+            while True:
+                loader.set_epoch(epoch)
+                yield from loader
+                epoch += 1
+        its = {k: stream(v) for k, v in loaders.items()}
+        fixed = next(its["png"])
+        for _ in range(args.warmup):
+            step(fixed)
+            step(next(its["png"]))
+            step(next(its["rle"]))
+        torch.cuda.synchronize()
+        rates = dict(prebuilt=[], png=[], rle=[])
+        for rnd in range(args.rounds):
+            for name in rates:
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    step(fixed if name == "prebuilt" else next(its[name]))
+                torch.cuda.synchronize()
+                rates[name].append(16 * args.steps / (time.perf_counter() - t0))
+        for v in loaders.values():
+            v.close()
+        med = {k: float(np.median(v)) for k, v in rates.items()}
+        res["train"] = dict(steps=args.steps, rounds=args.rounds, workers=args.workers, images_per_s=rates, median=med,
+                            png_over_prebuilt=med["png"] / med["prebuilt"], rle_over_prebuilt=med["rle"] / med["prebuilt"])
+    return res
+
+
 def _fresh(planned):
     """the planned samples with copies of their RandomStates (the assigner advances them)"""
     import copy
@@ -248,7 +384,7 @@ def _fresh(planned):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree"), required=True)
+    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree", "rle"), required=True)
     ap.add_argument("--pipeline", choices=("pbr", "mix"), default="pbr")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=60)
@@ -258,7 +394,7 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as root:
-        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree)[args.part](args, root)
+        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree, rle=part_rle)[args.part](args, root)
     line = json.dumps(res)
     print(line)
     if args.out:

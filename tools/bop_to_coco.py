@@ -14,14 +14,14 @@ def main():
     ap.add_argument("--images-dir", default="data/hb/train_pbr")
     ap.add_argument("--images-list", default="data/hb/image_lists/train_pbr.txt")
     ap.add_argument("--save-path", default="data/hb/detector_annotations/train_pbr.json")
-    ap.add_argument("--segmentation", action="store_true")
+    ap.add_argument("--segmentation", choices=("rle", "rle-string"), default=None,
+                    help="store every record's visible mask as a COCO run list (list form / compressed string)")
     ap.add_argument("--without-gt", action="store_true")
     ap.add_argument("--amodal", action="store_true")
     ap.add_argument("--dataset", choices=sorted(CLASS_NAMES), required=True)
     a = ap.parse_args()
-    if a.segmentation:
-        raise SystemExit("--segmentation (polygon extraction with skimage / shapely) is not restated; masks are read by path")
-    coco = bop_to_coco(a.images_dir, a.images_list, a.dataset, amodal=a.amodal, without_gt=a.without_gt)
+    coco = bop_to_coco(a.images_dir, a.images_list, a.dataset, amodal=a.amodal, without_gt=a.without_gt,
+                       segmentation=a.segmentation)
     os.makedirs(os.path.dirname(a.save_path) or ".", exist_ok=True)
     with open(a.save_path, "w") as f:
         json.dump(coco, f)

@@ -3,6 +3,8 @@
     <root>/train_pbr/000000/rgb/000000.jpg ...                   images (JPEG)
     <root>/train_pbr/000000/mask_visib/000000_000000.png ...     visible masks (PNG, 0 / 255)
     <root>/detector_annotations/train_pbr.json                   COCO-style annotations, as tools/bop_to_coco.py writes them
+    <root>/train_pbr/000000/scene_gt.json, scene_gt_info.json    the BOP ground truth tools/bop_to_coco.py reads
+    <root>/image_lists/train_pbr.txt                             the image list it reads
     <root>/backgrounds/*.jpg                                     background images of several sizes
 """
 import json
@@ -55,13 +57,31 @@ def write_tree(root, n_frames=8, objects=(3, 6), size=(640, 480), n_backgrounds=
     ann_file = os.path.join(root, "detector_annotations", "train_pbr.json")
     with open(ann_file, "w") as fh:
         json.dump(dict(images=images, annotations=anns, categories=cats), fh)
+    # the same records as BOP ground truth (scene_gt / scene_gt_info) and the image list, for the converter
+    gt, info = {}, {}
+    for a in anns:
+        f = str(a["image_id"] - 1)
+        gt.setdefault(f, []).append(dict(obj_id=a["category_id"], cam_R_m2c=[1, 0, 0, 0, 1, 0, 0, 0, 1], cam_t_m2c=[0, 0, 500]))
+        info.setdefault(f, []).append(dict(bbox_obj=a["bbox"], bbox_visib=a["bbox"], visib_fract=a["visib_fract"]))
+    for f in range(n_frames):
+        gt.setdefault(str(f), [])
+        info.setdefault(str(f), [])
+    order = sorted(info, key=int)
+    with open(os.path.join(scene, "scene_gt.json"), "w") as fh:
+        json.dump({k: gt[k] for k in order}, fh)
+    with open(os.path.join(scene, "scene_gt_info.json"), "w") as fh:
+        json.dump({k: info[k] for k in order}, fh)
+    os.makedirs(os.path.join(root, "image_lists"), exist_ok=True)
+    image_list = os.path.join(root, "image_lists", "train_pbr.txt")
+    with open(image_list, "w") as fh:
+        fh.write("".join(im["file_name"] + "\n" for im in images))
     bg_dir = os.path.join(root, "backgrounds")
     os.makedirs(bg_dir, exist_ok=True)
     for b in range(n_backgrounds):
         bw, bh = [(320, 240), (700, 500), (640, 480), (500, 375)][b % 4]
         Image.fromarray(_image(rng, bh, bw)).save(os.path.join(bg_dir, f"bg{b:03d}.jpg"), quality=quality)
     return dict(ann_file=ann_file, img_prefix=os.path.join(root, "train_pbr"), seg_prefix=os.path.join(root, "train_pbr"),
-                background_dir=bg_dir)
+                background_dir=bg_dir, image_list=image_list)
 
 
 def pipelines(background_dir, bg_prob=0.3, cosy_p=0.8):
