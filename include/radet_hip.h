@@ -490,6 +490,34 @@ int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint32_t* norm_
 int radet_rle_masks(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc, int G,
                     uint8_t* dst, uint8_t* dst_plain, int Hr, int Wr, int Hd, int Wd, int pad_val, void* stream);
 
+/* ---- baseline JPEG files decoded on the device (csrc/jpeg.hip, csrc/jpeg_index.c, radet_amd/core/jpeg.py): what libjpeg's
+ *      default decompressor gives for them byte for byte (slow-integer IDCT, fancy upsampling, fixed-point YCbCr -> RGB),
+ *      stored B, G, R.  Supported: one interleaved Huffman scan, 8 bits, 1 component or YCbCr with luma sampling 1x1, 2x1
+ *      or 2x2 and chroma 1x1.
+ *      radet_jpeg_index (host only, no device is touched): one walk over the scan file[scan_lo, scan_hi) that writes an
+ *      entry point every seg_mcus MCUs of a restart interval and at every restart marker, rows of JPEG_ROW_INTS ints
+ *      {raw byte offset, bit in that byte, first MCU, MCUs, DC predictor x 3, end offset * 8 + end bit}.  comp_blocks[c] =
+ *      blocks of component c per MCU; huff = 2 * ncomp table records of JPEG_HUFF_BYTES (DC, AC per component; layout:
+ *      csrc/jpeg_common.h, built by core/jpeg.py).  Returns the number of rows, or minus an error bit: 1 undefined code,
+ *      2 coefficient index past 63, 4 the stream ends early, 8 restart marker out of sequence, 16 MCU count / arguments,
+ *      64 more than max_rows rows.
+ *      radet_jpeg_decode: three launches for nimg images (entropy decode, IDCT, upsample + convert; `stages` bits 1 | 2 | 4
+ *      select them, 7 = all).  files: the files' bytes; desc i32 [nimg][JPEG_DESC_INTS] = {file offset, scan end (relative),
+ *      W, H, components, luma h, luma v, MCUs per row, MCU rows, first block of component 0..2 in coef, byte offset of plane
+ *      0..2 in planes (multiples of 8), destination pixel offset in dst, first index row, index rows, 0...};
+ *      wgs i32 [n_wg][2] = {image, first index row} per workgroup of 64 segments; huff [nimg][6] records; quant u16
+ *      [nimg][3][64] in natural order; rows: the index rows of all images; coef i16 [blocks][64] and planes u8: scratch
+ *      (planes are padded to whole MCUs); dst: packed u8 BGR pixels; err i32 [nimg], zero on entry: error bits per image
+ *      (the walker's, and 32: a segment did not end where its index row says).  huff, quant, coef 16-byte aligned. */
+#define JPEG_ROW_INTS 8
+#define JPEG_DESC_INTS 20
+#define JPEG_HUFF_BYTES 1424
+int radet_jpeg_index(const uint8_t* file, int scan_lo, int scan_hi, int ncomp, const int* comp_blocks, const void* huff,
+                     int n_mcus, int restart_interval, int seg_mcus, int* rows, int max_rows);
+int radet_jpeg_decode(const uint8_t* files, const int* desc, int nimg, const int* wgs, int n_wg, const void* huff,
+                      const uint16_t* quant, const int* rows, int n_rows, int16_t* coef, uint8_t* planes, uint8_t* dst,
+                      int* err, int max_blocks, int max_px, int stages, void* stream);
+
 /* ---- BOP training-image augmentation (csrc/augment.hip): RandomBackground merge, CosyPoseAug's PillowBlur /
  *      PillowSharpness / PillowContrast / PillowBrightness / PillowColor, RandomFlip, Normalize, Pad, batched over packed
  *      u8 HWC BGR images (every buffer packed alike).  params (device) = nimg rows of AUG_PARAM_INTS ints:

@@ -124,6 +124,8 @@ SIGNATURES = {
     "radet_mask_max": (_i, [_p, _p, _i, _sz, _p]),
     "radet_mask_transform": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "radet_rle_masks": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "radet_jpeg_index": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _i]),
+    "radet_jpeg_decode": (_i, [_p, _p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_augment_merge_hblur": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_augment_vblur": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "radet_augment_sharp": (_i, [_p, _p, _p, _p, _i, _i, _p]),

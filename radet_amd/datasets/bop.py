@@ -45,6 +45,13 @@ def build_dataset(cfg, default_args=None):
     contains 'dataset' is a sub-dataset config; its 'ratio', default 1, is the repeat count), a list-valued ann_file, or
     one registered dataset.  The caller's config is left as it was."""
     from .dataset_wrappers import ConcatDataset, MixDataset, RepeatDataset
+    if not isinstance(cfg, (list, tuple)) and cfg.get("type") in ("ConcatDataset", "RepeatDataset", "MixDataset"):
+        # image_decode / index_cache / seg_mcus on a wrapper are meant for the datasets inside it
+        extra = {k: cfg[k] for k in ("image_decode", "index_cache", "seg_mcus") if k in cfg}
+        if extra:
+            def push(c):
+                return [push(x) for x in c] if isinstance(c, (list, tuple)) else {**extra, **c}
+            cfg = {k: (push(v) if "dataset" in k else v) for k, v in cfg.items() if k not in extra}
     if isinstance(cfg, (list, tuple)):
         return ConcatDataset([build_dataset(c, default_args) for c in cfg])
     kind = cfg.get("type")
@@ -123,9 +130,12 @@ class BOPDataset:
 
     def __init__(self, ann_file, pipeline, classes=None, data_root=None, img_prefix="", bop_submission=False,
                  seg_prefix=None, proposal_file=None, test_mode=False, min_visib_frac=0., filter_empty_gt=True,
-                 mask_source="file"):
+                 mask_source="file", image_decode=None, index_cache=None, seg_mcus=None):
         """mask_source: 'file' = one visible-mask PNG per object under seg_prefix (LoadAnnotations(with_bop_mask=True));
-        'annotation' = the records' `segmentation` objects (LoadAnnotations(with_mask=True))"""
+        'annotation' = the records' `segmentation` objects (LoadAnnotations(with_mask=True)).
+        image_decode: 'device' decodes the pipeline's JPEG files on the GPU (None: as the pipeline config says, 'host' by
+        default); index_cache: a directory that keeps the files' scan indexes (tools/jpeg_index.py fills it); seg_mcus: MCUs
+        per index segment, or 'row' (the device decoder's parallelism: one lane per segment)"""
         if mask_source not in ("file", "annotation"):
             raise ValueError(f"mask_source is 'file' or 'annotation', got {mask_source!r}")
         self.mask_source = mask_source
@@ -142,7 +152,12 @@ class BOPDataset:
             keep = self._filter_imgs()
             self.data_infos = [self.data_infos[i] for i in keep]
             self._set_group_flag()
-        self.pipeline = ImagePipeline(pipeline) if is_image_pipeline(pipeline) else Compose(pipeline)
+        if is_image_pipeline(pipeline):
+            self.pipeline = ImagePipeline(pipeline, image_decode=image_decode, index_cache=index_cache, seg_mcus=seg_mcus)
+        elif image_decode not in (None, "host") or seg_mcus is not None:
+            raise ValueError("image_decode needs a pipeline that starts with LoadImageFromFile")
+        else:
+            self.pipeline = Compose(pipeline)
         if bop_submission:
             self._det2json = self._bop_det2json
 
@@ -469,10 +484,10 @@ class CocoDataset(BOPDataset):
     CLASSES = COCO_CLASSES
 
     def __init__(self, ann_file, pipeline, classes=None, data_root=None, img_prefix="", seg_prefix=None, proposal_file=None,
-                 test_mode=False, filter_empty_gt=True):
+                 test_mode=False, filter_empty_gt=True, image_decode=None, index_cache=None, seg_mcus=None):
         super().__init__(ann_file, pipeline, classes=classes, data_root=data_root, img_prefix=img_prefix, seg_prefix=seg_prefix,
                          proposal_file=proposal_file, test_mode=test_mode, filter_empty_gt=filter_empty_gt,
-                         mask_source="annotation")
+                         mask_source="annotation", image_decode=image_decode, index_cache=index_cache, seg_mcus=seg_mcus)
 
     def _parse_ann_info(self, img_info, ann_info):
         n = len(ann_info)

@@ -84,8 +84,16 @@ class DataLoader:
         for k in range(len(batches)):
             futures, pending = pending, (submit(batches[k + 1]) if k + 1 < len(batches) else None)
             yield self.dataset.pipeline.run([f.result() for f in futures], collate=True)
+        self._drain()
+
+    def _drain(self):
+        """the device JPEG decoder's error words of the batches whose check is still pending (the last ones of an epoch)"""
+        check = getattr(self.dataset.pipeline, "check_decode_errors", None)
+        if check is not None:
+            check(wait=True)
 
     def close(self):
+        self._drain()
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None

@@ -9,18 +9,21 @@ whole batch on the calling thread and stream: the resize of images and backgroun
 normalisation / resize / flip (radet_mask_transform; radet_rle_masks for masks annotated as run lists or polygons), the four augmentation launches of csrc/augment.hip (a mixpbr
 pipeline: merge, hsv_noise, box, finish), the box crops / distance maps of a mask-free GenerateDistanceMap
 (radet_crop_canvases, the ops' packed GDT / MBD chain, radet_paste_maps) and the label assigner -- a fixed number of
-launches whatever the batch size.  A single sample (`BOPDataset.__getitem__`) is a batch
+launches whatever the batch size.  With decode="device" on LoadImageFromFile / RandomBackground the host reads the file,
+its headers and its scan index (radet_amd/core/jpeg.py) and run() decodes the batch's baseline JPEGs in front of the
+resize (radet_jpeg_decode, three launches); files outside the decoder's subset are decoded by Pillow as before.  A single sample (`BOPDataset.__getitem__`) is a batch
 of one.  Options the RADet configs do not use raise NotImplementedError."""
 import glob
 import math
 import os
 import struct
+import threading
 
 import numpy as np
 import torch
 
 from .. import kernels as K
-from ..core import rle
+from ..core import jpeg, rle
 from ..core.mask import rescale_size
 from ..utils import build_from_cfg
 from .pipelines import PIPELINES, GenerateDistanceMap, LabelAssignment
@@ -52,6 +55,26 @@ def decode_bgr(path):
     return np.ascontiguousarray(rgb[..., ::-1])
 
 
+def _decode_arg(decode):
+    if decode not in ("host", "device"):
+        raise ValueError(f"decode is 'host' or 'device', got {decode!r}")
+    return decode
+
+
+_CACHE_LOCK = threading.Lock()
+
+
+def _plan_image(path, stage):
+    """the image of a decode='device' stage: a jpeg.DeviceJpeg (bytes, header, scan index; nothing decoded), or the host's
+    pixels for a file the device decoder does not take"""
+    if stage.cache is None:                      # (a stage used outside an ImagePipeline; the pipeline sets a shared cache)
+        with _CACHE_LOCK:
+            if stage.cache is None:
+                stage.cache = jpeg.IndexCache(stage.index_cache)
+    item = jpeg.plan_file(path, stage.cache, stage.seg_mcus)
+    return decode_bgr(path) if item is None else item
+
+
 def decode_unchanged(path):
     """mmcv.imfrombytes(flag='unchanged') of an 8-bit single-channel mask PNG"""
     from PIL import Image
@@ -80,7 +103,11 @@ def _f32_bits(v):
 # ---------------------------------------------------------------------------------------------------- loading
 @PIPELINES.register_module()
 class LoadImageFromFile:
-    def __init__(self, to_float32=False, color_type="color", file_client_args=None):
+    def __init__(self, to_float32=False, color_type="color", file_client_args=None, decode="host", index_cache=None,
+                 seg_mcus=jpeg.DEFAULT_SEG_MCUS):
+        """decode='device': plan() reads the file and its scan index, ImagePipeline.run decodes the batch on the GPU
+        (baseline JPEG; any other file is decoded here as with 'host'); index_cache: a directory for the scan indexes"""
+        self.decode, self.index_cache, self.seg_mcus, self.cache = _decode_arg(decode), index_cache, seg_mcus, None
         if to_float32:
             _refuse("LoadImageFromFile(to_float32=True)")
         if color_type != "color":
@@ -92,7 +119,7 @@ class LoadImageFromFile:
         name = s["img_info"]["filename"]
         s["filename"] = osp.join(s["img_prefix"], name) if s.get("img_prefix") is not None else name
         s["ori_filename"] = name
-        s["img"] = decode_bgr(s["filename"])
+        s["img"] = decode_bgr(s["filename"]) if self.decode == "host" else _plan_image(s["filename"], self)
         s["img_shape"] = s["ori_shape"] = s["pad_shape"] = s["img"].shape
         s["img_fields"] = ["img"]
 
@@ -225,7 +252,9 @@ class Pad:
 # ---------------------------------------------------------------------------------------------------- photometric
 @PIPELINES.register_module()
 class RandomBackground:
-    def __init__(self, background_dir, prob=0.8, file_client_args=None, flag="color"):
+    def __init__(self, background_dir, prob=0.8, file_client_args=None, flag="color", decode="host", index_cache=None,
+                 seg_mcus=jpeg.DEFAULT_SEG_MCUS):
+        self.decode, self.index_cache, self.seg_mcus, self.cache = _decode_arg(decode), index_cache, seg_mcus, None
         if flag != "color":
             _refuse(f"RandomBackground(flag={flag!r})")
         # sorted: the reference's glob order depends on the file system
@@ -237,7 +266,8 @@ class RandomBackground:
     def plan(self, s, rnd, nprnd):
         if rnd.random() > self.prob:
             return
-        s["background"] = decode_bgr(rnd.choice(self.background_images))
+        path = rnd.choice(self.background_images)
+        s["background"] = decode_bgr(path) if self.decode == "host" else _plan_image(path, self)
 
 
 class _PillowStage:
@@ -413,9 +443,33 @@ def is_image_pipeline(transforms):
 class ImagePipeline:
     """A pipeline that starts from files: host planning per sample, one batched device pass per batch."""
 
-    def __init__(self, transforms):
+    def __init__(self, transforms, image_decode=None, index_cache=None, seg_mcus=None):
+        """image_decode ('host' / 'device'), index_cache (a directory) and seg_mcus (MCUs per index segment, or 'row'),
+        when given, are set on the pipeline's LoadImageFromFile and RandomBackground stages"""
+        given = image_decode is not None or index_cache is not None or seg_mcus is not None
+        if given:
+            extra = dict(**({} if image_decode is None else dict(decode=_decode_arg(image_decode))),
+                         **({} if index_cache is None else dict(index_cache=index_cache)),
+                         **({} if seg_mcus is None else dict(seg_mcus=seg_mcus)))
+            transforms = [{**t, **extra} if isinstance(t, dict) and t.get("type") in ("LoadImageFromFile", "RandomBackground") else t
+                          for t in transforms]
         self.cfg = list(transforms)                       # (wrapped datasets share one pipeline when their configs are equal)
         self.transforms = [build_from_cfg(t, PIPELINES) if isinstance(t, dict) else t for t in transforms]
+        if given:
+            for t in self.transforms:                     # (stages that were passed as objects)
+                if isinstance(t, (LoadImageFromFile, RandomBackground)):
+                    t.decode = t.decode if image_decode is None else image_decode
+                    t.index_cache = t.index_cache if index_cache is None else index_cache
+                    t.seg_mcus = t.seg_mcus if seg_mcus is None else seg_mcus
+        # one index cache per pipeline (= per dataset), shared by the frames and the backgrounds
+        shared = None
+        for t in self.transforms:
+            if isinstance(t, (LoadImageFromFile, RandomBackground)) and t.decode == "device":
+                shared = shared or jpeg.IndexCache(t.index_cache)
+                t.cache = shared
+        self.device_decode = shared is not None
+        self.decode_stats = dict(device=0, fallback=0)
+        self._decode_pending = []
         flat = []
         for t in self.transforms:
             flat += [t] + (list(t.transforms) if isinstance(t, MultiScaleFlipAug) else [])
@@ -458,12 +512,57 @@ class ImagePipeline:
     def _dev():
         return torch.device("cuda", torch.cuda.current_device())
 
-    def _resize_packed(self, arrays, dst_hw, dev, align=1):
+    def _decode_packed(self, sources, dev, align=1):
+        """The packed u8 BGR source buffer of a batch whose images are jpeg.DeviceJpeg plans (and host arrays, for the files
+        the device decoder does not take): one pinned non-blocking upload of the files, tables and index rows, then
+        radet_jpeg_decode's three launches.  Returns (buffer, pixel offset per source); nothing waits for the device: the
+        decoder's error words are copied to pinned memory and read by a later call (check_decode_errors)."""
+        self.check_decode_errors()
+        offs, o = [], 0
+        for a in sources:
+            offs.append(o)
+            o += -(-a.shape[0] * a.shape[1] // align) * align
+        src = torch.empty(o * 3, dtype=torch.uint8, device=dev)
+        on_dev = [k for k, a in enumerate(sources) if isinstance(a, jpeg.DeviceJpeg)]
+        on_host = [k for k, a in enumerate(sources) if not isinstance(a, jpeg.DeviceJpeg)]
+        self.decode_stats["device"] += len(on_dev)
+        self.decode_stats["fallback"] += len(on_host)
+        if on_host:
+            up = torch.from_numpy(np.concatenate([sources[k].reshape(-1) for k in on_host])).pin_memory().to(dev, non_blocking=True)
+            u = 0
+            for k in on_host:
+                n = sources[k].size
+                src[offs[k] * 3:offs[k] * 3 + n].copy_(up[u:u + n])
+                u += n
+        items = [sources[k] for k in on_dev]
+        blob, sections, sizes = jpeg.pack_batch(items, [offs[k] for k in on_dev])
+        blob = torch.from_numpy(blob).pin_memory().to(dev, non_blocking=True)
+        err, _, _ = K.jpeg_decode(blob, sections, sizes, len(items), src)
+        host_err = torch.empty(len(items), dtype=torch.int32).pin_memory()
+        host_err.copy_(err, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._decode_pending.append((ev, host_err, [it.path for it in items]))
+        return src, offs
+
+    def check_decode_errors(self, wait=False):
+        """raise for a file whose device decode set an error word (the batches whose copy has arrived; wait=True: all)"""
+        while self._decode_pending and (wait or self._decode_pending[0][0].query()):
+            ev, host_err, paths = self._decode_pending.pop(0)
+            if wait:
+                ev.synchronize()
+            bad = [(p, int(e)) for p, e in zip(paths, host_err.tolist()) if e]
+            if bad:
+                what = "; ".join(f"{p}: " + ", ".join(v for k, v in jpeg.ERRORS.items() if e & k) for p, e in bad)
+                raise ValueError(f"device JPEG decode failed (the pixels of that batch are undefined): {what}")
+
+    def _resize_packed(self, arrays, dst_hw, dev, align=1, src=None):
         """u8 HWC images of any sizes -> one packed device buffer of the dst sizes (one resize launch); every image starts at
-        a multiple of `align` pixels"""
-        src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(dev)
+        a multiple of `align` pixels.  src: (packed device buffer, pixel offsets) when the images are there already"""
+        src, src_offs = src if src is not None else (torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(dev), None)
         sdesc, ddesc, so, do = [], [], 0, 0
-        for a, (h, w) in zip(arrays, dst_hw):
+        for k, (a, (h, w)) in enumerate(zip(arrays, dst_hw)):
+            so = so if src_offs is None else src_offs[k]
             sdesc.append((so, a.shape[0], a.shape[1]))
             ddesc.append((do, h, w))
             so += a.shape[0] * a.shape[1]
@@ -483,10 +582,20 @@ class ImagePipeline:
             if h > K.AUG_MAX_W or w > K.AUG_MAX_W:
                 raise ValueError(f"image of {h} x {w}: the augmentation kernels take sides up to {K.AUG_MAX_W}")
         # (mix pipelines: images start at multiples of 4 pixels, so the mix kernels' dword accesses are aligned)
-        img, offs = self._resize_packed([s["img"] for s in planned], hw, dev, align=4 if self.mix else 1)
         with_bg = [i for i, s in enumerate(planned) if "background" in s]
-        bg, bg_offs = (self._resize_packed([planned[i]["background"] for i in with_bg], [hw[i] for i in with_bg], dev)
-                       if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
+        sources = [s["img"] for s in planned] + [planned[i]["background"] for i in with_bg]
+        if self.device_decode and not any(isinstance(a, jpeg.DeviceJpeg) for a in sources):
+            self.decode_stats["fallback"] += len(sources)          # (every file of the batch went to the host decoder)
+        if any(isinstance(a, jpeg.DeviceJpeg) for a in sources):
+            # decode='device': frames and backgrounds are decoded by the same three launches into one packed source buffer
+            src, soffs = self._decode_packed(sources, dev, align=4 if self.mix else 1)
+            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, src=(src, soffs[:B]))
+            bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev, src=(src, soffs[B:]))
+                           if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
+        else:
+            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1)
+            bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev)
+                           if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         bg_off = dict(zip(with_bg, bg_offs))
         masks, flipped_masks = self._masks(planned, hw, dev)
 

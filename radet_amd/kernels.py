@@ -1511,6 +1511,27 @@ def rle_masks(run_ends, part_desc, mask_desc, out_hw, resized_hw=None, pad_val=0
     return (dst, plain) if with_plain else dst
 
 
+JPEG_ROW_INTS, JPEG_DESC_INTS, JPEG_HUFF_BYTES = 8, 20, 1424       # include/radet_hip.h
+
+
+def jpeg_decode(blob, sections, sizes, nimg, dst, stages=7, work=None):
+    """Baseline JPEG files -> packed u8 BGR pixels in `dst`, three launches (radet_jpeg_decode).  blob: the device copy of
+    radet_amd.core.jpeg.pack_batch's buffer, sections / sizes as it returned them.  stages: bits 1 | 2 | 4 select the
+    entropy / IDCT / convert launch (a benchmark times them one by one, with work = the (coef, planes) of a full call).
+    Returns (err i32 [nimg] device view of the blob: error bits per image, zero for a good one; coef; planes)."""
+    def sec(name):
+        o, n = sections[name]
+        return blob[o:o + n]
+    coef, planes = work if work is not None else (
+        torch.empty(sizes["coef_blocks"] * 64, dtype=torch.int16, device=blob.device),
+        torch.empty(sizes["plane_bytes"], dtype=torch.uint8, device=blob.device))
+    err = sec("err").view(torch.int32)
+    _lib.call("radet_jpeg_decode", _ptr(sec("files")), _ptr(sec("desc")), nimg, _ptr(sec("wgs")), sizes["n_wg"], _ptr(sec("huff")),
+              _ptr(sec("quant")), _ptr(sec("rows")), sizes["n_rows"], _ptr(coef), _ptr(planes), _ptr(dst), _ptr(err),
+              sizes["max_blocks"], sizes["max_px"], int(stages), _stream())
+    return err, coef, planes
+
+
 def assign_points(gt_boxes, gt_off, masks, H, W, rng_words, U, ldesc, ranges, nlvl, B, positive_num, neg_thr, p2g, pw, used,
                   ws, flags=1):
     """masks: u8 [sumG, H, W] visible masks, or f32 per-box distance maps (mask-free sampler); rng_words: int32 / uint32 bit

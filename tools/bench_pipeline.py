@@ -13,6 +13,11 @@
                                                                    # host plan, device mask stage, loader-fed training
                                                                    # (timeout -k 10 500 python tools/bench_pipeline.py --part rle
                                                                    #  --out profiles/bench_pipeline_rle.json)
+    python tools/bench_pipeline.py --part jpeg [--iters 20] [--steps 30]   # the same frames with decode='host' and 'device':
+                                                                   # host plan (cold / cached index), the decode stage per
+                                                                   # launch for seg_mcus 8 / 16 / row, loader-fed training
+                                                                   # (timeout -k 10 700 python tools/bench_pipeline.py --part jpeg
+                                                                   #  --steps 30 --out profiles/bench_pipeline_jpeg.json)
 `--pipeline mix` runs the mixpbr train pipeline instead (RandomHSV / RandomNoise / RandomSmooth in place of CosyPoseAug,
 the training set a MixDataset of the tree twice, ratios 2 and 1).
 Each part prints one JSON line (and writes it to --out if given)."""
@@ -376,6 +381,152 @@ def part_rle(args, root):
     return res
 
 
+def part_jpeg(args, root):
+    """bs 16, 640 x 480, the frames of --part rle under run-list annotations; the same call runs decode='host' (the
+    baseline) and decode='device'.  (a) host plan per sample: host decoding, device decoding with a cold index (the walk is
+    paid) and with a cached one; images/s at 1 / 2 / 12 / 16 loader threads; (b) the device decode stage of one batch
+    (frames + backgrounds) for seg_mcus 8 / 16 / one MCU row: upload + three launches between a device event pair, and
+    each launch alone; (c) loader-fed training against one prebuilt batch, host and device decoding alternated."""
+    import copy
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    from radet_amd import kernels as K
+    from radet_amd.core import jpeg
+    from radet_amd.datasets import build_dataloader, build_dataset
+    from radet_amd.datasets.bop_convert import add_segmentation
+    from radet_amd.datasets.loader import sample_generators
+    tree = write_tree(root, n_frames=64, objects=(6, 6), seed=0)
+    ann = os.path.join(root, "train_pbr_rle.json")
+    with open(tree["ann_file"]) as f:
+        coco = add_segmentation(json.load(f), tree["seg_prefix"], "rle")
+    with open(ann, "w") as f:
+        json.dump(coco, f)
+    train, _ = pipelines(tree["background_dir"])
+    train = copy.deepcopy(train)
+    train[1] = dict(type="LoadAnnotations", with_bbox=True, with_mask=True)
+
+    def build(decode, **kw):
+        return build_dataset(dict(type="BOPDataset", ann_file=ann, img_prefix=tree["img_prefix"], mask_source="annotation",
+                                  pipeline=train, image_decode=decode, **kw))
+
+    def plan_all(d, epoch=0):
+        per = []
+        for i in range(len(d)):
+            t0 = time.perf_counter()
+            d.plan_sample(i, *sample_generators(0, epoch, i))
+            per.append((time.perf_counter() - t0) * 1e3)
+        return per
+    res = dict(part="jpeg", batch=16, iters=args.iters, frames=64, default_seg_mcus=jpeg.DEFAULT_SEG_MCUS)
+    # (a) host planning
+    host_ds, dev_ds = build("host"), build("device")
+    build("device").plan_sample(0, *sample_generators(0, 0, 0))           # (library load, Pillow import: not the walk's cost)
+    host_ds.plan_sample(0, *sample_generators(0, 0, 0))
+    plans = dict(host=_scatter(plan_all(host_ds)), device_cold_index=_scatter(plan_all(dev_ds)),
+                 device_cached_index=_scatter(plan_all(dev_ds)))
+    rates = {}
+    for name, d in (("host", host_ds), ("device_cached_index", dev_ds)):
+        rate = {}
+        for threads in (1, 2, 12, 16):
+            with ThreadPoolExecutor(threads) as pool:
+                list(pool.map(lambda i: d.plan_sample(i, *sample_generators(0, 0, i)), range(threads)))
+                runs = []
+                for rep in range(3):
+                    t0 = time.perf_counter()
+                    list(pool.map(lambda i: d.plan_sample(i, *sample_generators(0, rep, i)), range(len(d))))
+                    runs.append(len(d) / (time.perf_counter() - t0))
+                rate[threads] = dict(median=float(np.median(runs)), runs=runs)
+        rates[name] = rate
+    res["host"] = dict(plan_ms_per_sample=plans, images_per_s_by_threads=rates,
+                       cached_plan_over_host_plan=plans["device_cached_index"]["median"] / plans["host"]["median"],
+                       images_per_s_at_2_threads_device_over_host=rates["device_cached_index"][2]["median"] / rates["host"][2]["median"])
+    # (b) the decode stage of one batch, per segment length
+    stage = {}
+    for seg in (8, 16, "row"):
+        d = build("device", seg_mcus=seg)
+        planned = [d.plan_sample(i, *sample_generators(0, 0, i)) for i in range(16)]
+        sources = [s["img"] for s in planned] + [s["background"] for s in planned if "background" in s]
+        assert all(isinstance(a, jpeg.DeviceJpeg) for a in sources)
+        pipe, dev = d.pipeline, d.pipeline._dev()
+        offs = np.cumsum([0] + [a.shape[0] * a.shape[1] for a in sources])
+        blob, sections, sizes = jpeg.pack_batch(sources, offs[:-1])
+        dblob = torch.from_numpy(blob).to(dev)
+        dst = torch.empty(int(offs[-1]) * 3, dtype=torch.uint8, device=dev)
+        _, coef, planes = K.jpeg_decode(dblob, sections, sizes, len(sources), dst)
+        whole, launches = [], {1: [], 2: [], 4: []}
+        for it in range(args.iters + 3):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            pipe._decode_packed(sources, dev)
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= 3:
+                whole.append(e0.elapsed_time(e1))
+            for bit in (1, 2, 4):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                K.jpeg_decode(dblob, sections, sizes, len(sources), dst, stages=bit, work=(coef, planes))
+                e1.record()
+                torch.cuda.synchronize()
+                if it >= 3:
+                    launches[bit].append(e0.elapsed_time(e1))
+        pipe.check_decode_errors(wait=True)
+        stage[str(seg)] = dict(images=len(sources), segments=sizes["n_rows"], workgroups=sizes["n_wg"], upload_bytes=int(blob.size),
+                               file_bytes=int(sections["files"][1]), upload_and_launches_event_ms=_scatter(whole),
+                               entropy_event_ms=_scatter(launches[1]), idct_event_ms=_scatter(launches[2]),
+                               convert_event_ms=_scatter(launches[4]))
+    res["device_decode_stage"] = stage
+    # (c) loader-fed training
+    if args.steps > 0:
+        from oracle import synth
+        from radet_amd.models import build_detector
+        from radet_amd.utils import Config
+        cfg = Config.fromfile(os.path.join(ROOT, "configs", "bop", "r50_ycbv_pbr.py"))
+        cfg.model["pretrained"] = None
+        torch.manual_seed(0)
+        det = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
+        synth.fill_state_dict(det.state_dict(), seed=0)
+        det = det.cuda().train()
+        rt = det.runtime()
+        rt.init_optimizer(lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=35.0)
+        rt.set_loss_from_head(det.bbox_head)
+
+        def step(b):
+            tg = rt.pack_targets(b["gt_bboxes"], b["gt_labels"], b["points_to_gt_index"], b["points_weight"])
+            rt.train_step(b["img"], tg, lr=1e-4)
+        loaders = {k: build_dataloader(d, samples_per_gpu=16, workers=args.workers, seed=0)
+                   for k, d in (("host", host_ds), ("device", dev_ds))}
+
+        def stream(loader):
+            epoch = 0
+            while True:
+                loader.set_epoch(epoch)
+                yield from loader
+                epoch += 1
+        its = {k: stream(v) for k, v in loaders.items()}
+        fixed = next(its["host"])
+        for _ in range(args.warmup):
+            step(fixed)
+            step(next(its["host"]))
+            step(next(its["device"]))
+        torch.cuda.synchronize()
+        tr = dict(prebuilt=[], host=[], device=[])
+        for rnd in range(args.rounds):
+            for name in tr:
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    step(fixed if name == "prebuilt" else next(its[name]))
+                torch.cuda.synchronize()
+                tr[name].append(16 * args.steps / (time.perf_counter() - t0))
+        for v in loaders.values():
+            v.close()
+        med = {k: float(np.median(v)) for k, v in tr.items()}
+        res["train"] = dict(steps=args.steps, rounds=args.rounds, workers=args.workers, images_per_s=tr, median=med,
+                            host_over_prebuilt=med["host"] / med["prebuilt"], device_over_prebuilt=med["device"] / med["prebuilt"],
+                            decode_stats=dev_ds.pipeline.decode_stats)
+    return res
+
+
 def _fresh(planned):
     """the planned samples with copies of their RandomStates (the assigner advances them)"""
     import copy
@@ -384,7 +535,7 @@ def _fresh(planned):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree", "rle"), required=True)
+    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree", "rle", "jpeg"), required=True)
     ap.add_argument("--pipeline", choices=("pbr", "mix"), default="pbr")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=60)
@@ -394,7 +545,7 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as root:
-        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree, rle=part_rle)[args.part](args, root)
+        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree, rle=part_rle, jpeg=part_jpeg)[args.part](args, root)
     line = json.dumps(res)
     print(line)
     if args.out:
