@@ -687,6 +687,19 @@ int radet_fill_zero(void* dst, size_t nbytes, void* stream);
 int radet_stream_create_cumask(const uint32_t* cu_mask, int nwords, void** stream_out);
 int radet_copy_d2d(void* dst, const void* src, size_t nbytes, void* stream);
 
+/* ---- segmented copy between arbitrary device byte addresses (csrc/copy.hip): the sample cache's gather (HBM arena -> a
+ *      batch's packed source buffer) and insert (buffer -> arena), one launch for a whole table.
+ *      desc (device) = n rows of COPY_DESC_INTS ints: {source address lo, hi, destination address lo, hi, bytes, first tile}.
+ *      A row owns ((destination & 15) + bytes + COPY_TILE_BYTES - 1) / COPY_TILE_BYTES tiles (none for bytes <= 0);
+ *      `first tile` is the exclusive prefix sum of those counts over the rows and n_tiles their total (one workgroup per
+ *      tile, so rows of very different sizes share the device evenly).  Any source / destination alignment; rows may not
+ *      overlap each other's destinations.  Only bytes of [source, source + bytes) are read and only bytes of
+ *      [destination, destination + bytes) are written, whatever the tile column holds.
+ *      Returns RADET_ERR_ARG for n < 0, n_tiles < 0 or a NULL table with n > 0; n = 0 launches nothing. */
+#define COPY_DESC_INTS 6
+#define COPY_TILE_BYTES 16384
+int radet_copy_segments(const int* desc, int n, int n_tiles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

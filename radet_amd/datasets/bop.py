@@ -19,6 +19,7 @@ import numpy as np
 from ..utils import Registry, build_from_cfg
 from .cocoeval import COCO, COCOeval, eval_recalls
 from .loading import ImagePipeline, is_image_pipeline
+from .sample_cache import cache_args
 from .pipelines import PIPELINES
 
 osp = os.path
@@ -46,8 +47,8 @@ def build_dataset(cfg, default_args=None):
     one registered dataset.  The caller's config is left as it was."""
     from .dataset_wrappers import ConcatDataset, MixDataset, RepeatDataset
     if not isinstance(cfg, (list, tuple)) and cfg.get("type") in ("ConcatDataset", "RepeatDataset", "MixDataset"):
-        # image_decode / index_cache / seg_mcus on a wrapper are meant for the datasets inside it
-        extra = {k: cfg[k] for k in ("image_decode", "index_cache", "seg_mcus") if k in cfg}
+        # image_decode / index_cache / seg_mcus / sample_cache / cache_bytes on a wrapper are meant for the datasets inside it
+        extra = {k: cfg[k] for k in ("image_decode", "index_cache", "seg_mcus", "sample_cache", "cache_bytes") if k in cfg}
         if extra:
             def push(c):
                 return [push(x) for x in c] if isinstance(c, (list, tuple)) else {**extra, **c}
@@ -130,12 +131,15 @@ class BOPDataset:
 
     def __init__(self, ann_file, pipeline, classes=None, data_root=None, img_prefix="", bop_submission=False,
                  seg_prefix=None, proposal_file=None, test_mode=False, min_visib_frac=0., filter_empty_gt=True,
-                 mask_source="file", image_decode=None, index_cache=None, seg_mcus=None):
+                 mask_source="file", image_decode=None, index_cache=None, seg_mcus=None, sample_cache=None, cache_bytes=None):
         """mask_source: 'file' = one visible-mask PNG per object under seg_prefix (LoadAnnotations(with_bop_mask=True));
         'annotation' = the records' `segmentation` objects (LoadAnnotations(with_mask=True)).
         image_decode: 'device' decodes the pipeline's JPEG files on the GPU (None: as the pipeline config says, 'host' by
         default); index_cache: a directory that keeps the files' scan indexes (tools/jpeg_index.py fills it); seg_mcus: MCUs
-        per index segment, or 'row' (the device decoder's parallelism: one lane per segment)"""
+        per index segment, or 'row' (the device decoder's parallelism: one lane per segment).
+        sample_cache: 'device' keeps every decoded frame and background in HBM after its first visit, up to cache_bytes (the
+        budget in bytes, required with it), and the mask PNGs in host memory as run lists; wrapped datasets share one cache"""
+        cache_args(sample_cache, cache_bytes)
         if mask_source not in ("file", "annotation"):
             raise ValueError(f"mask_source is 'file' or 'annotation', got {mask_source!r}")
         self.mask_source = mask_source
@@ -153,9 +157,10 @@ class BOPDataset:
             self.data_infos = [self.data_infos[i] for i in keep]
             self._set_group_flag()
         if is_image_pipeline(pipeline):
-            self.pipeline = ImagePipeline(pipeline, image_decode=image_decode, index_cache=index_cache, seg_mcus=seg_mcus)
-        elif image_decode not in (None, "host") or seg_mcus is not None:
-            raise ValueError("image_decode needs a pipeline that starts with LoadImageFromFile")
+            self.pipeline = ImagePipeline(pipeline, image_decode=image_decode, index_cache=index_cache, seg_mcus=seg_mcus,
+                                          sample_cache=sample_cache, cache_bytes=cache_bytes)
+        elif image_decode not in (None, "host") or seg_mcus is not None or sample_cache is not None:
+            raise ValueError("image_decode / sample_cache need a pipeline that starts with LoadImageFromFile")
         else:
             self.pipeline = Compose(pipeline)
         if bop_submission:
@@ -484,10 +489,12 @@ class CocoDataset(BOPDataset):
     CLASSES = COCO_CLASSES
 
     def __init__(self, ann_file, pipeline, classes=None, data_root=None, img_prefix="", seg_prefix=None, proposal_file=None,
-                 test_mode=False, filter_empty_gt=True, image_decode=None, index_cache=None, seg_mcus=None):
+                 test_mode=False, filter_empty_gt=True, image_decode=None, index_cache=None, seg_mcus=None, sample_cache=None,
+                 cache_bytes=None):
         super().__init__(ann_file, pipeline, classes=classes, data_root=data_root, img_prefix=img_prefix, seg_prefix=seg_prefix,
                          proposal_file=proposal_file, test_mode=test_mode, filter_empty_gt=filter_empty_gt,
-                         mask_source="annotation", image_decode=image_decode, index_cache=index_cache, seg_mcus=seg_mcus)
+                         mask_source="annotation", image_decode=image_decode, index_cache=index_cache, seg_mcus=seg_mcus,
+                         sample_cache=sample_cache, cache_bytes=cache_bytes)
 
     def _parse_ann_info(self, img_info, ann_info):
         n = len(ann_info)

@@ -11,7 +11,9 @@ pipeline: merge, hsv_noise, box, finish), the box crops / distance maps of a mas
 (radet_crop_canvases, the ops' packed GDT / MBD chain, radet_paste_maps) and the label assigner -- a fixed number of
 launches whatever the batch size.  With decode="device" on LoadImageFromFile / RandomBackground the host reads the file,
 its headers and its scan index (radet_amd/core/jpeg.py) and run() decodes the batch's baseline JPEGs in front of the
-resize (radet_jpeg_decode, three launches); files outside the decoder's subset are decoded by Pillow as before.  A single sample (`BOPDataset.__getitem__`) is a batch
+resize (radet_jpeg_decode, three launches); files outside the decoder's subset are decoded by Pillow as before.  With
+sample_cache='device' decoded frames and backgrounds stay in HBM after their first visit and later batches gather them
+with one radet_copy_segments launch (sample_cache.py).  A single sample (`BOPDataset.__getitem__`) is a batch
 of one.  Options the RADet configs do not use raise NotImplementedError."""
 import glob
 import math
@@ -27,6 +29,7 @@ from ..core import jpeg, rle
 from ..core.mask import rescale_size
 from ..utils import build_from_cfg
 from .pipelines import PIPELINES, GenerateDistanceMap, LabelAssignment
+from .sample_cache import CachedImage, SampleCache, cache_args, normalised_runs
 
 osp = os.path
 DEFAULT_META_KEYS = ("filename", "ori_filename", "ori_shape", "img_shape", "pad_shape", "scale_factor", "flip",
@@ -75,6 +78,17 @@ def _plan_image(path, stage):
     return decode_bgr(path) if item is None else item
 
 
+def _plan_pixels(path, stage, s, field):
+    """s[field] of a LoadImageFromFile / RandomBackground stage: with a sample cache, the placeholder of a cached file (one
+    stat, the file is not opened) or the file's key in s["_cache_keys"][field] for run() to enter it; then the stage's decode"""
+    if stage.sample_cache is not None:
+        hit, key = stage.sample_cache.lookup(path)
+        if hit is not None:
+            return hit
+        s.setdefault("_cache_keys", {})[field] = key
+    return decode_bgr(path) if stage.decode == "host" else _plan_image(path, stage)
+
+
 def decode_unchanged(path):
     """mmcv.imfrombytes(flag='unchanged') of an 8-bit single-channel mask PNG"""
     from PIL import Image
@@ -108,6 +122,7 @@ class LoadImageFromFile:
         """decode='device': plan() reads the file and its scan index, ImagePipeline.run decodes the batch on the GPU
         (baseline JPEG; any other file is decoded here as with 'host'); index_cache: a directory for the scan indexes"""
         self.decode, self.index_cache, self.seg_mcus, self.cache = _decode_arg(decode), index_cache, seg_mcus, None
+        self.sample_cache = None                      # (an ImagePipeline with sample_cache='device' sets its cache here)
         if to_float32:
             _refuse("LoadImageFromFile(to_float32=True)")
         if color_type != "color":
@@ -119,7 +134,7 @@ class LoadImageFromFile:
         name = s["img_info"]["filename"]
         s["filename"] = osp.join(s["img_prefix"], name) if s.get("img_prefix") is not None else name
         s["ori_filename"] = name
-        s["img"] = decode_bgr(s["filename"]) if self.decode == "host" else _plan_image(s["filename"], self)
+        s["img"] = _plan_pixels(s["filename"], self, s, "img")
         s["img_shape"] = s["ori_shape"] = s["pad_shape"] = s["img"].shape
         s["img_fields"] = ["img"]
 
@@ -135,6 +150,7 @@ class LoadAnnotations:
         if with_mask and with_bop_mask:
             _refuse("LoadAnnotations(with_mask=True, with_bop_mask=True) (two sources for gt_masks)")
         self.with_bbox, self.with_label, self.with_bop_mask, self.with_mask = with_bbox, with_label, with_bop_mask, with_mask
+        self.sample_cache = None
 
     def plan(self, s, rnd, nprnd):
         ann = s["ann_info"]
@@ -148,11 +164,22 @@ class LoadAnnotations:
             s["gt_labels"] = np.asarray(ann["labels"], np.int64).copy()
         if self.with_bop_mask:
             h, w = s["img_info"]["height"], s["img_info"]["width"]
-            masks = [decode_unchanged(osp.join(s["seg_prefix"], p)) for p in ann["masks"]]
-            for m in masks:
-                if m.shape != (h, w):
-                    raise ValueError(f"mask of shape {m.shape} for an image of {h} x {w}")
-            s["gt_masks"] = np.stack(masks) if masks else np.zeros((0, h, w), np.uint8)
+            paths = [osp.join(s["seg_prefix"], p) for p in ann["masks"]]
+            cache = self.sample_cache
+            looked = [cache.mask_lookup(p, (h, w)) for p in paths] if cache is not None else None
+            if looked is not None and all(runs is not None for runs, _ in looked):
+                # every mask file was seen before: their run lists (sample_cache.normalised_runs) take the radet_rle_masks path
+                s["gt_masks_rle"] = ([[runs] for runs, _ in looked], (h, w))
+                cache.count_mask_hits(len(looked))
+            else:
+                masks = [decode_unchanged(p) for p in paths]
+                for m in masks:
+                    if m.shape != (h, w):
+                        raise ValueError(f"mask of shape {m.shape} for an image of {h} x {w}")
+                for m, (runs, key) in zip(masks, looked or ()):
+                    if runs is None:
+                        cache.mask_insert(key, normalised_runs(m), (h, w))
+                s["gt_masks"] = np.stack(masks) if masks else np.zeros((0, h, w), np.uint8)
             s["mask_fields"].append("gt_masks")
         if self.with_mask:
             # the `segmentation` objects of the annotation file (polygons, run lists, compressed run lists) as run lists:
@@ -255,6 +282,7 @@ class RandomBackground:
     def __init__(self, background_dir, prob=0.8, file_client_args=None, flag="color", decode="host", index_cache=None,
                  seg_mcus=jpeg.DEFAULT_SEG_MCUS):
         self.decode, self.index_cache, self.seg_mcus, self.cache = _decode_arg(decode), index_cache, seg_mcus, None
+        self.sample_cache = None
         if flag != "color":
             _refuse(f"RandomBackground(flag={flag!r})")
         # sorted: the reference's glob order depends on the file system
@@ -267,7 +295,7 @@ class RandomBackground:
         if rnd.random() > self.prob:
             return
         path = rnd.choice(self.background_images)
-        s["background"] = decode_bgr(path) if self.decode == "host" else _plan_image(path, self)
+        s["background"] = _plan_pixels(path, self, s, "background")
 
 
 class _PillowStage:
@@ -443,9 +471,12 @@ def is_image_pipeline(transforms):
 class ImagePipeline:
     """A pipeline that starts from files: host planning per sample, one batched device pass per batch."""
 
-    def __init__(self, transforms, image_decode=None, index_cache=None, seg_mcus=None):
+    def __init__(self, transforms, image_decode=None, index_cache=None, seg_mcus=None, sample_cache=None, cache_bytes=None):
         """image_decode ('host' / 'device'), index_cache (a directory) and seg_mcus (MCUs per index segment, or 'row'),
-        when given, are set on the pipeline's LoadImageFromFile and RandomBackground stages"""
+        when given, are set on the pipeline's LoadImageFromFile and RandomBackground stages.
+        sample_cache='device' with cache_bytes (the HBM budget for pixels, required): decoded frames and backgrounds stay
+        in HBM and mask PNGs in host memory as run lists after their first visit (datasets/sample_cache.py)"""
+        sample_cache, cache_bytes = cache_args(sample_cache, cache_bytes)
         given = image_decode is not None or index_cache is not None or seg_mcus is not None
         if given:
             extra = dict(**({} if image_decode is None else dict(decode=_decode_arg(image_decode))),
@@ -468,7 +499,16 @@ class ImagePipeline:
                 shared = shared or jpeg.IndexCache(t.index_cache)
                 t.cache = shared
         self.device_decode = shared is not None
+        # decode_stats: files decoded by the device decoder / files of a decode='device' stage that went to the host decoder.
+        # cache_stats (a property): the sample cache's counters -- hits / misses (frame and background lookups), inserted /
+        # bytes (entries and pixel bytes in the HBM arena), rejected_full (decoded files the budget or the chunk size did not
+        # take), invalidated (entries dropped because the file changed), mask_hits / mask_bytes (masks served from, and
+        # bytes of, the host run-list table); all zero without sample_cache='device'
         self.decode_stats = dict(device=0, fallback=0)
+        self.sample_cache = None if sample_cache is None else SampleCache(cache_bytes)
+        for t in self.transforms:
+            if isinstance(t, (LoadImageFromFile, RandomBackground, LoadAnnotations)):
+                t.sample_cache = self.sample_cache
         self._decode_pending = []
         flat = []
         for t in self.transforms:
@@ -492,6 +532,11 @@ class ImagePipeline:
         if self.mask_free is not None and getattr(dm.distance_transform, "extract_edge_func", None) is not None:
             _refuse("GenerateDistanceMap(extract_edge_func=...) in an image pipeline (a host callback)")
         self.tta = any(isinstance(t, MultiScaleFlipAug) for t in self.transforms)
+
+    @property
+    def cache_stats(self):
+        from .sample_cache import COUNTERS
+        return dict(self.sample_cache.stats) if self.sample_cache is not None else dict.fromkeys(COUNTERS, 0)
 
     def plan(self, results, rnd, nprnd):
         """host part of one sample (thread-safe for distinct generators): decoding, boxes, random draws"""
@@ -534,8 +579,12 @@ class ImagePipeline:
                 n = sources[k].size
                 src[offs[k] * 3:offs[k] * 3 + n].copy_(up[u:u + n])
                 u += n
-        items = [sources[k] for k in on_dev]
-        blob, sections, sizes = jpeg.pack_batch(items, [offs[k] for k in on_dev])
+        self._decode_into(src, [sources[k] for k in on_dev], [offs[k] for k in on_dev], dev)
+        return src, offs
+
+    def _decode_into(self, src, items, item_offs, dev):
+        """radet_jpeg_decode of `items` to their pixel offsets of the packed buffer `src`; the error words go to the pending list"""
+        blob, sections, sizes = jpeg.pack_batch(items, item_offs)
         blob = torch.from_numpy(blob).pin_memory().to(dev, non_blocking=True)
         err, _, _ = K.jpeg_decode(blob, sections, sizes, len(items), src)
         host_err = torch.empty(len(items), dtype=torch.int32).pin_memory()
@@ -543,6 +592,48 @@ class ImagePipeline:
         ev = torch.cuda.Event()
         ev.record()
         self._decode_pending.append((ev, host_err, [it.path for it in items]))
+
+    def _cached_packed(self, planned, with_bg, sources, dev, align=1):
+        """The packed u8 BGR source buffer of a batch under sample_cache='device', whose sources are host arrays, jpeg.DeviceJpeg
+        plans and cache hits (CachedImage).  Host arrays go up in one pinned non-blocking copy; one radet_copy_segments
+        launch moves them and every hit to their places; the JPEG plans are decoded in place.  Then the newly decoded files
+        that the arena takes are copied into it by a second launch and entered in the table.  A batch of hits only uploads
+        no pixels; nothing here waits for the device.  Returns (buffer, pixel offset per source)."""
+        self.check_decode_errors()
+        cache = self.sample_cache
+        keys = ([s.get("_cache_keys", {}).get("img") for s in planned]
+                + [planned[i].get("_cache_keys", {}).get("background") for i in with_bg])
+        offs, o = [], 0
+        for a in sources:
+            offs.append(o)
+            o += -(-a.shape[0] * a.shape[1] // align) * align
+        src = torch.empty(o * 3, dtype=torch.uint8, device=dev)
+        base = src.data_ptr()
+        hits = [k for k, a in enumerate(sources) if isinstance(a, CachedImage)]
+        on_dev = [k for k, a in enumerate(sources) if isinstance(a, jpeg.DeviceJpeg)]
+        on_host = [k for k, a in enumerate(sources) if isinstance(a, np.ndarray)]
+        if self.device_decode:
+            self.decode_stats["device"] += len(on_dev)
+            self.decode_stats["fallback"] += len(on_host)
+        cache.wait_inserts()
+        rows = [(sources[k].addr, base + offs[k] * 3, sources[k].nbytes) for k in hits]
+        if on_host:
+            up = torch.from_numpy(np.concatenate([sources[k].reshape(-1) for k in on_host])).pin_memory().to(dev, non_blocking=True)
+            u = up.data_ptr()
+            for k in on_host:
+                rows.append((u, base + offs[k] * 3, sources[k].size))
+                u += sources[k].size
+        if rows:
+            cache.copy(rows, dev)
+        if on_dev:
+            self._decode_into(src, [sources[k] for k in on_dev], [offs[k] for k in on_dev], dev)
+        fresh = [k for k in on_host + on_dev if keys[k] is not None]
+        taken = cache.reserve([(keys[k], sources[k].shape) for k in fresh])
+        if taken:
+            where = {keys[k][0]: base + offs[k] * 3 for k in reversed(fresh)}
+            cache.copy([(where[key[0]], addr, nbytes) for key, _, addr, nbytes in taken], dev)
+            cache.record_insert()
+            cache.commit(taken)
         return src, offs
 
     def check_decode_errors(self, wait=False):
@@ -552,6 +643,9 @@ class ImagePipeline:
             if wait:
                 ev.synchronize()
             bad = [(p, int(e)) for p, e in zip(paths, host_err.tolist()) if e]
+            if bad and self.sample_cache is not None:
+                for p, _ in bad:
+                    self.sample_cache.drop(p)
             if bad:
                 what = "; ".join(f"{p}: " + ", ".join(v for k, v in jpeg.ERRORS.items() if e & k) for p, e in bad)
                 raise ValueError(f"device JPEG decode failed (the pixels of that batch are undefined): {what}")
@@ -584,11 +678,13 @@ class ImagePipeline:
         # (mix pipelines: images start at multiples of 4 pixels, so the mix kernels' dword accesses are aligned)
         with_bg = [i for i, s in enumerate(planned) if "background" in s]
         sources = [s["img"] for s in planned] + [planned[i]["background"] for i in with_bg]
-        if self.device_decode and not any(isinstance(a, jpeg.DeviceJpeg) for a in sources):
+        if self.sample_cache is None and self.device_decode and not any(isinstance(a, jpeg.DeviceJpeg) for a in sources):
             self.decode_stats["fallback"] += len(sources)          # (every file of the batch went to the host decoder)
-        if any(isinstance(a, jpeg.DeviceJpeg) for a in sources):
-            # decode='device': frames and backgrounds are decoded by the same three launches into one packed source buffer
-            src, soffs = self._decode_packed(sources, dev, align=4 if self.mix else 1)
+        if self.sample_cache is not None or any(isinstance(a, jpeg.DeviceJpeg) for a in sources):
+            # decode='device': frames and backgrounds are decoded by the same three launches into one packed source buffer;
+            # sample_cache='device': cached files are gathered into that buffer, new ones leave it for the arena
+            src, soffs = (self._cached_packed(planned, with_bg, sources, dev, align=4 if self.mix else 1)
+                          if self.sample_cache is not None else self._decode_packed(sources, dev, align=4 if self.mix else 1))
             img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, src=(src, soffs[:B]))
             bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev, src=(src, soffs[B:]))
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))

@@ -120,6 +120,32 @@ def copy_d2d(dst, src):
     _lib.call("radet_copy_d2d", _ptr(dst), _ptr(src), C.c_size_t(n), _stream())
 
 
+COPY_DESC_INTS, COPY_TILE_BYTES = 6, 16384       # include/radet_hip.h
+
+
+def copy_segments_table(rows):
+    """The descriptor table of radet_copy_segments for rows of (source byte address, destination byte address, bytes):
+    (int32 [n, COPY_DESC_INTS] host array, tile total).  Host arithmetic only."""
+    import numpy as np
+    r = np.asarray(rows, np.int64).reshape(-1, 3)
+    if (r[:, 2] < 0).any() or (r[:, 2] >= 2 ** 31).any():
+        raise ValueError("a segment holds 0 .. 2^31 - 1 bytes")
+    tiles = np.where(r[:, 2] > 0, ((r[:, 1] & 15) + r[:, 2] + COPY_TILE_BYTES - 1) // COPY_TILE_BYTES, 0)
+    total = int(tiles.sum())
+    if total >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 tiles in one table")
+    t = np.empty((len(r), COPY_DESC_INTS), np.int32)
+    t[:, 0:4] = np.ascontiguousarray(r[:, :2]).view(np.uint32).reshape(-1, 4).view(np.int32)   # (little endian: lo, hi)
+    t[:, 4] = r[:, 2]
+    t[:, 5] = np.cumsum(tiles) - tiles
+    return t, total
+
+
+def copy_segments(desc, n, n_tiles):
+    """one launch that copies every row of a device descriptor table (copy_segments_table, uploaded by the caller)"""
+    _lib.call("radet_copy_segments", _ptr(desc), int(n), int(n_tiles), _stream())
+
+
 class Levels:
     """Row-concatenated multi-level NHWC geometry: level l = B images of h_l x w_l pixels."""
 

@@ -18,6 +18,10 @@
                                                                    # launch for seg_mcus 8 / 16 / row, loader-fed training
                                                                    # (timeout -k 10 700 python tools/bench_pipeline.py --part jpeg
                                                                    #  --steps 30 --out profiles/bench_pipeline_jpeg.json)
+    python tools/bench_pipeline.py --part cache [--iters 20] [--steps 30]  # the same frames without and with sample_cache='device',
+                                                                   # PNG masks + host decoding and run lists + device decoding
+                                                                   # (timeout -k 10 900 python tools/bench_pipeline.py --part cache
+                                                                   #  --steps 30 --out profiles/bench_pipeline_cache.json)
 `--pipeline mix` runs the mixpbr train pipeline instead (RandomHSV / RandomNoise / RandomSmooth in place of CosyPoseAug,
 the training set a MixDataset of the tree twice, ratios 2 and 1).
 Each part prints one JSON line (and writes it to --out if given)."""
@@ -527,6 +531,165 @@ def part_jpeg(args, root):
     return res
 
 
+def part_cache(args, root):
+    """bs 16, 640 x 480, the frames of --part rle, for (png_host: PNG-mask annotations, host decoding) and (rle_device:
+    run-list annotations, device decoding); the uncached pipeline of the same call is the baseline.  (a) host plan per
+    sample: uncached, cached cold (every file a miss; the masks are converted) and warm; images/s at 1 / 2 / 12 / 16
+    loader threads; (b) run() of one batch between a device event pair, uncached and warm, and the gather and insert
+    launches alone with the bytes they move; (c) loader-fed training against one prebuilt batch, all variants alternated."""
+    import copy
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    from radet_amd import kernels as K
+    from radet_amd.datasets import build_dataloader, build_dataset
+    from radet_amd.datasets.bop_convert import add_segmentation
+    from radet_amd.datasets.loader import sample_generators
+    from radet_amd.datasets.sample_cache import CachedImage
+    tree = write_tree(root, n_frames=64, objects=(6, 6), seed=0)
+    ann = os.path.join(root, "train_pbr_rle.json")
+    with open(tree["ann_file"]) as f:
+        coco = add_segmentation(json.load(f), tree["seg_prefix"], "rle")
+    with open(ann, "w") as f:
+        json.dump(coco, f)
+    train, _ = pipelines(tree["background_dir"])
+    rle_train = copy.deepcopy(train)
+    rle_train[1] = dict(type="LoadAnnotations", with_bbox=True, with_mask=True)
+    budget = 2 << 30
+
+    def build(style, **kw):
+        if style == "png_host":
+            return build_dataset(dict(type="BOPDataset", ann_file=tree["ann_file"], img_prefix=tree["img_prefix"],
+                                      seg_prefix=tree["seg_prefix"], pipeline=train, image_decode="host", **kw))
+        return build_dataset(dict(type="BOPDataset", ann_file=ann, img_prefix=tree["img_prefix"], mask_source="annotation",
+                                  pipeline=rle_train, image_decode="device", **kw))
+
+    def plan_all(d, epoch):
+        per = []
+        for i in range(len(d)):
+            t0 = time.perf_counter()
+            d.plan_sample(i, *sample_generators(0, epoch, i))
+            per.append((time.perf_counter() - t0) * 1e3)
+        return per
+
+    def rate_by_threads(d):
+        rate = {}
+        for threads in (1, 2, 12, 16):
+            with ThreadPoolExecutor(threads) as pool:
+                list(pool.map(lambda i: d.plan_sample(i, *sample_generators(0, 0, i)), range(threads)))
+                runs = []
+                for rep in range(3):
+                    t0 = time.perf_counter()
+                    list(pool.map(lambda i: d.plan_sample(i, *sample_generators(0, rep, i)), range(len(d))))
+                    runs.append(len(d) / (time.perf_counter() - t0))
+                rate[threads] = dict(median=float(np.median(runs)), runs=runs)
+        return rate
+
+    def timed(fn, iters):
+        out = []
+        for it in range(iters + 3):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= 3:
+                out.append(e0.elapsed_time(e1))
+        return _scatter(out)
+    res = dict(part="cache", batch=16, iters=args.iters, frames=64, cache_bytes=budget)
+    sets = {}
+    for style in ("png_host", "rle_device"):
+        plain, cached = build(style), build(style, sample_cache="device", cache_bytes=budget)
+        plain.plan_sample(0, *sample_generators(0, 0, 0))                   # (library load, Pillow import)
+        r = dict(plan_ms_per_sample=dict(uncached=_scatter(plan_all(plain, 0)), cached_cold=_scatter(plan_all(cached, 0))))
+        # the first epoch: every batch of 16 through run(), then every background a later epoch may draw
+        for epoch in (0, 1, 2):
+            for b in range(0, len(cached), 16):
+                cached.pipeline.run([cached.plan_sample(i, *sample_generators(0, epoch, i)) for i in range(b, b + 16)])
+        cached.pipeline.check_decode_errors(wait=True)
+        r["plan_ms_per_sample"]["cached_warm"] = _scatter(plan_all(cached, 3))
+        r["images_per_s_by_threads"] = dict(uncached=rate_by_threads(plain), cached_warm=rate_by_threads(cached))
+        # (b) run() of one batch
+        warm = [cached.plan_sample(i, *sample_generators(0, 3, i)) for i in range(16)]
+        cold = [plain.plan_sample(i, *sample_generators(0, 3, i)) for i in range(16)]
+        sources = [s["img"] for s in warm] + [s["background"] for s in warm if "background" in s]
+        assert all(isinstance(a, CachedImage) for a in sources), "a file of the timed batch is not cached"
+        dev = cached.pipeline._dev()
+        nbytes = sum(a.nbytes for a in sources)
+        buf = torch.empty(nbytes + 16 * len(sources), dtype=torch.uint8, device=dev)
+        arena = torch.empty(nbytes + 256 * len(sources), dtype=torch.uint8, device=dev)
+        g_rows, i_rows, o, ao = [], [], 0, 0
+        for a in sources:                                                    # (packed at 3-byte granularity, like run())
+            g_rows.append((a.addr, buf.data_ptr() + o, a.nbytes))
+            i_rows.append((buf.data_ptr() + o, arena.data_ptr() + ao, a.nbytes))
+            o += a.nbytes + 3
+            ao += -(-a.nbytes // 256) * 256
+        tabs = {}
+        for name, rows in (("gather", g_rows), ("insert", i_rows)):
+            t, tiles = K.copy_segments_table(rows)
+            tabs[name] = (torch.from_numpy(t).to(dev), len(t), tiles)
+        r["run_event_ms"] = dict(uncached=timed(lambda: plain.pipeline.run(_fresh(cold)), args.iters),
+                                 cached_warm=timed(lambda: cached.pipeline.run(_fresh(warm)), args.iters))
+        launches = {}
+        for name, tab in tabs.items():
+            ms = timed(lambda: K.copy_segments(*tab), args.iters)
+            launches[name] = dict(event_ms=ms, bytes=int(nbytes), tiles=tab[2], rows=tab[1],
+                                  gbytes_per_s_read_plus_write=2 * nbytes / (ms["median"] * 1e-3) / 1e9)
+        r["launches"] = launches
+        r["cache_stats"] = cached.pipeline.cache_stats
+        sets[style] = (plain, cached)
+        res[style] = r
+    # (c) loader-fed training
+    if args.steps > 0:
+        from oracle import synth
+        from radet_amd.models import build_detector
+        from radet_amd.utils import Config
+        cfg = Config.fromfile(os.path.join(ROOT, "configs", "bop", "r50_ycbv_pbr.py"))
+        cfg.model["pretrained"] = None
+        torch.manual_seed(0)
+        det = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
+        synth.fill_state_dict(det.state_dict(), seed=0)
+        det = det.cuda().train()
+        rt = det.runtime()
+        rt.init_optimizer(lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=35.0)
+        rt.set_loss_from_head(det.bbox_head)
+
+        def step(b):
+            tg = rt.pack_targets(b["gt_bboxes"], b["gt_labels"], b["points_to_gt_index"], b["points_weight"])
+            rt.train_step(b["img"], tg, lr=1e-4)
+        loaders = {f"{style}_{kind}": build_dataloader(d, samples_per_gpu=16, workers=args.workers, seed=0)
+                   for style, pair in sets.items() for kind, d in zip(("uncached", "cached"), pair)}
+
+        def stream(loader):
+            epoch = 0
+            while True:
+                loader.set_epoch(epoch)
+                yield from loader
+                epoch += 1
+        its = {k: stream(v) for k, v in loaders.items()}
+        fixed = next(its["png_host_uncached"])
+        for _ in range(args.warmup):
+            step(fixed)
+            for it in its.values():
+                step(next(it))
+        torch.cuda.synchronize()
+        tr = {k: [] for k in ["prebuilt", *its]}
+        for rnd in range(args.rounds):
+            for name in tr:
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    step(fixed if name == "prebuilt" else next(its[name]))
+                torch.cuda.synchronize()
+                tr[name].append(16 * args.steps / (time.perf_counter() - t0))
+        for v in loaders.values():
+            v.close()
+        med = {k: float(np.median(v)) for k, v in tr.items()}
+        res["train"] = dict(steps=args.steps, rounds=args.rounds, workers=args.workers, images_per_s=tr, median=med,
+                            over_prebuilt={k: med[k] / med["prebuilt"] for k in its},
+                            cache_stats={style: pair[1].pipeline.cache_stats for style, pair in sets.items()})
+    return res
+
+
 def _fresh(planned):
     """the planned samples with copies of their RandomStates (the assigner advances them)"""
     import copy
@@ -535,7 +698,7 @@ def _fresh(planned):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree", "rle", "jpeg"), required=True)
+    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree", "rle", "jpeg", "cache"), required=True)
     ap.add_argument("--pipeline", choices=("pbr", "mix"), default="pbr")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=60)
@@ -545,7 +708,7 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as root:
-        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree, rle=part_rle, jpeg=part_jpeg)[args.part](args, root)
+        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree, rle=part_rle, jpeg=part_jpeg, cache=part_cache)[args.part](args, root)
     line = json.dumps(res)
     print(line)
     if args.out:
