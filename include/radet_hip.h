@@ -570,6 +570,20 @@ int radet_crop_canvases(const uint8_t* src, size_t src_bytes, const unsigned lon
 int radet_paste_maps(const void* maps, size_t map_px, int is_f64, const int* desc, int nbox, int H, int W, float* out,
                      void* stream);
 
+/* ---- in-memory frames through the test pipeline in one launch (csrc/preprocess.hip): LoadImageFromWebcam -> Resize ->
+ *      Normalize -> Pad (radet/datasets/pipelines/loading.py:88 as radet/apis/inference.py:97-102 uses it).  nimg u8 HWC BGR
+ *      frames of any, mixed sizes -> out f32 [nimg,3,Hp,Wp]: what radet_resize_linear_u8 followed by radet_augment_finish
+ *      (no augmentation flag set) writes for the same pixels, bit for bit; every element of out is written.
+ *      desc (device) = nimg rows of PREP_DESC_INTS ints:
+ *      {source byte address lo, hi, source row stride in bytes (unsigned), source h, w, destination (resized) h, w, flags};
+ *      a pixel is 3 consecutive bytes, pixels of a row are contiguous; any address alignment (byte loads), so a frame may
+ *      be a view into a larger device tensor.  flags: PREP_TO_RGB.  Pixels beyond the destination h x w are zero; a row
+ *      with source h or w <= 0 is all zeros.  nimg <= 65535, Hp * Wp < 2^31. */
+#define PREP_DESC_INTS 8
+#define PREP_TO_RGB 1
+int radet_preprocess_frames(const int* desc, int nimg, int Hp, int Wp, float m0, float m1, float m2, float s0, float s1,
+                            float s2, float* out, void* stream);
+
 /* ---- stand-alone box / loss operators behind the registered classes (used on their own; inside the detector the same
  *      arithmetic runs fused in radet_head_loss / radet_decode_candidates) ------------------------------------------ */
 /* bbox_overlaps / BboxOverlaps2D (radet/core/bbox/iou_calculators/iou2d_calculator.py:43-159): boxes [batch, M, 4] and

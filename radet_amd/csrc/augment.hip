@@ -11,6 +11,7 @@
 //                   image's luma sum for Contrast (u64 atomics: integer, order-independent)
 //   finish        : Contrast, Brightness, Color blends, horizontal flip, BGR->RGB, Normalize, zero pad -> f32[B,3,Hp,Wp]
 #include "common.h"
+#include "pixel_ops.h"
 #include "../../include/radet_hip.h"
 
 enum {
@@ -213,16 +214,12 @@ __global__ __launch_bounds__(256) void aug_finish_kernel(const uint8_t* __restri
     float* o = out + (size_t)blockIdx.y * 3 * Hp * Wp + p;
     const size_t plane = (size_t)Hp * Wp;
     if (y >= a.h || x >= a.w) {
-        o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
+        zero_store(o, plane);
         return;
     }
     int v[3];
     aug_final_bgr(src, lsum, a, blockIdx.y, y, x, v);
-    const bool rgb = a.flags & AUG_TO_RGB;
-    const float q0 = (float)(rgb ? v[2] : v[0]), q1 = (float)v[1], q2 = (float)(rgb ? v[0] : v[2]);
-    o[0] = (q0 - m0) * s0;
-    o[plane] = (q1 - m1) * s1;
-    o[2 * plane] = (q2 - m2) * s2;
+    norm_store(o, plane, v, a.flags & AUG_TO_RGB, m0, m1, m2, s0, s1, s2);
 }
 
 // The padded box crops of the mask-free sampler (GenerateDistanceMap(with_gt_mask=False)): one descriptor row per box

@@ -15,6 +15,7 @@
 //     RGB2GRAY = (4899 c0 + 9617 c1 + 1868 c2 + 8192) >> 14, 3x3 Sobel d/dx and d/dy (REFLECT_101) in float,
 //     |0.5 gx + 0.5 gy| divided by the crop's maximum.
 #include "common.h"
+#include "pixel_ops.h"
 #include "../../include/radet_hip.h"
 
 struct Crop { int off, h, w; };
@@ -31,26 +32,6 @@ __device__ __forceinline__ int reflect101(int p, int n) {      // cv::borderInte
     return p;
 }
 
-// source index + fraction of destination index d (cv::resize, INTER_LINEAR): f = (d + 0.5) * scale - 0.5 in float
-__device__ __forceinline__ void lin_coord(int d, double scale, int n, bool clamp_frac, int* s, float* f) {
-    float fx = (float)(((double)d + 0.5) * scale - 0.5);
-    int sx = (int)floorf(fx);
-    fx -= (float)sx;
-    if (clamp_frac) {                                           // x direction: coefficients are reset at the borders
-        if (sx < 0) { fx = 0.f; sx = 0; }
-        if (sx >= n - 1) { fx = 0.f; sx = n - 1; }
-    }
-    *s = sx;
-    *f = fx;
-}
-
-__device__ __forceinline__ int clip_row(int y, int n) { return y < 0 ? 0 : (y < n ? y : n - 1); }
-
-__device__ __forceinline__ int coef_fix(float c) {             // saturate_cast<short>(c * 2048): round to nearest even
-    int v = __float2int_rn(c * 2048.f);
-    return v > 32767 ? 32767 : (v < -32768 ? -32768 : v);
-}
-
 template <int C>
 __global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restrict__ src, const int* __restrict__ sdesc,
                                                         uint8_t* __restrict__ dst, const int* __restrict__ ddesc) {
@@ -58,24 +39,13 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restric
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= d.h * d.w) return;
     const int dy = p / d.w, dx = p - dy * d.w;
-    const double scale_x = 1.0 / ((double)d.w / (double)s.w), scale_y = 1.0 / ((double)d.h / (double)s.h);
-    int sx, sy;
-    float fx, fy;
-    lin_coord(dx, scale_x, s.w, true, &sx, &fx);
-    lin_coord(dy, scale_y, s.h, false, &sy, &fy);
-    const int a0 = coef_fix(1.f - fx), a1 = coef_fix(fx), b0 = coef_fix(1.f - fy), b1 = coef_fix(fy);
-    const int y0 = clip_row(sy, s.h), y1 = clip_row(sy + 1, s.h);
-    const int x1 = sx + 1 < s.w ? sx + 1 : sx;                  // a1 == 0 whenever sx is the last column
-    const uint8_t* r0 = src + ((size_t)s.off + (size_t)y0 * s.w) * C;
-    const uint8_t* r1 = src + ((size_t)s.off + (size_t)y1 * s.w) * C;
+    const LinTaps t = lin_taps_u8(dy, dx, s.h, s.w, d.h, d.w);
+    const uint8_t* r0 = src + ((size_t)s.off + (size_t)t.y0 * s.w) * C;
+    const uint8_t* r1 = src + ((size_t)s.off + (size_t)t.y1 * s.w) * C;
     uint8_t* o = dst + ((size_t)d.off + p) * C;
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int h0 = (int)r0[sx * C + c] * a0 + (int)r0[x1 * C + c] * a1;
-        const int h1 = (int)r1[sx * C + c] * a0 + (int)r1[x1 * C + c] * a1;
-        const int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-        o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-    }
+    for (int c = 0; c < C; ++c)
+        o[c] = (uint8_t)lin_blend_u8(r0[t.sx * C + c], r0[t.x1 * C + c], r1[t.sx * C + c], r1[t.x1 * C + c], t);
 }
 
 template <class T>

@@ -14,7 +14,9 @@ its headers and its scan index (radet_amd/core/jpeg.py) and run() decodes the ba
 resize (radet_jpeg_decode, three launches); files outside the decoder's subset are decoded by Pillow as before.  With
 sample_cache='device' decoded frames and backgrounds stay in HBM after their first visit and later batches gather them
 with one radet_copy_segments launch (sample_cache.py).  A single sample (`BOPDataset.__getitem__`) is a batch
-of one.  Options the RADet configs do not use raise NotImplementedError."""
+of one.  A pipeline whose first stage is LoadImageFromWebcam takes frames that are in memory already (ndarray or device
+tensor): a test pipeline, whose run() is one pinned upload and one radet_preprocess_frames launch (_run_frames).
+Options the RADet configs do not use raise NotImplementedError."""
 import glob
 import math
 import os
@@ -136,6 +138,41 @@ class LoadImageFromFile:
         s["ori_filename"] = name
         s["img"] = _plan_pixels(s["filename"], self, s, "img")
         s["img_shape"] = s["ori_shape"] = s["pad_shape"] = s["img"].shape
+        s["img_fields"] = ["img"]
+
+
+@PIPELINES.register_module()
+class LoadImageFromWebcam:
+    """The frame is in results["img"] already (radet/datasets/pipelines/loading.py:88): an ndarray HxWx3 uint8 in BGR order, as
+    mmcv.imread gives, or a torch.uint8 tensor of that shape -- on the device it is read in place by ImagePipeline.run,
+    also as a view into a larger tensor (rows may be strided; the 3 bytes of a pixel and the pixels of a row are contiguous)"""
+
+    def __init__(self, to_float32=False, color_type="color", file_client_args=None):
+        if to_float32:
+            _refuse("LoadImageFromWebcam(to_float32=True)")
+        if color_type != "color":
+            _refuse(f"LoadImageFromWebcam(color_type={color_type!r})")
+        if file_client_args not in (None, dict(backend="disk")):
+            _refuse(f"LoadImageFromWebcam(file_client_args={file_client_args})")
+
+    def plan(self, s, rnd, nprnd):
+        img = s["img"]
+        if isinstance(img, torch.Tensor) and not img.is_cuda and img.dtype == torch.uint8:
+            img = img.numpy()                                   # (a host tensor is a host frame)
+        if not isinstance(img, (np.ndarray, torch.Tensor)):
+            raise ValueError(f"LoadImageFromWebcam takes an ndarray or a torch tensor HxWx3 uint8, got {type(img).__name__}")
+        u8 = img.dtype == (np.uint8 if isinstance(img, np.ndarray) else torch.uint8)
+        if not u8 or len(img.shape) != 3 or img.shape[2] != 3 or 0 in img.shape:
+            raise ValueError(f"LoadImageFromWebcam takes a frame HxWx3 uint8 (BGR), got {img.dtype} of shape {tuple(img.shape)}")
+        if isinstance(img, torch.Tensor):
+            h, w = img.shape[:2]
+            sy, sx, sc = img.stride()
+            if sc != 1 or (w > 1 and sx != 3) or (h > 1 and sy >= 2 ** 31):
+                raise ValueError(f"LoadImageFromWebcam reads a device frame in place: its pixels must be 3 contiguous bytes and "
+                                 f"the pixels of a row contiguous, got strides {tuple(img.stride())} for shape {tuple(img.shape)}")
+        s["filename"] = s["ori_filename"] = None
+        s["img"] = img
+        s["img_shape"] = s["ori_shape"] = s["pad_shape"] = tuple(img.shape)
         s["img_fields"] = ["img"]
 
 
@@ -468,8 +505,37 @@ def is_image_pipeline(transforms):
     return any((t.get("type") if isinstance(t, dict) else type(t).__name__) == "LoadImageFromFile" for t in transforms or ())
 
 
+# the stages of a pipeline that starts from LoadImageFromWebcam: the reference's test pipeline, nothing else
+_FRAME_STAGES = ("LoadImageFromWebcam", "MultiScaleFlipAug", "Resize", "RandomFlip", "Normalize", "Pad", "DefaultFormatBundle",
+                 "ImageToTensor", "Collect")
+
+
+def frame_desc_rows(frames, dst_hw, to_rgb, host_base):
+    """The descriptor rows of radet_preprocess_frames (include/radet_hip.h, PREP_DESC_INTS) for a batch of frames HxWx3 u8:
+    an ndarray goes into the batch's upload buffer, packed, at the byte offset returned for it (its address: host_base +
+    offset, the device address of that buffer's pixel part); a torch tensor is read where it is (data_ptr, row stride).
+    Host arithmetic only.  Returns (int32 [B, PREP_DESC_INTS], byte offset per frame or None, bytes of the upload)."""
+    rows = np.zeros((len(frames), K.PREP_DESC_INTS), np.int32)
+    offs, o = [], 0
+    for row, f, (dh, dw) in zip(rows, frames, dst_hw):
+        h, w = int(f.shape[0]), int(f.shape[1])
+        if isinstance(f, np.ndarray):
+            addr, stride = host_base + o, 3 * w
+            offs.append(o)
+            o += 3 * h * w
+        else:
+            addr, stride = f.data_ptr(), (int(f.stride(0)) if h > 1 else 3 * w)
+            offs.append(None)
+        if not 0 <= stride < 2 ** 31:
+            raise ValueError(f"frame of shape {tuple(f.shape)}: a row stride of {stride} bytes does not fit the descriptor")
+        row[0:2] = np.array([addr & 0xFFFFFFFF, addr >> 32], np.uint32).view(np.int32)
+        row[2:8] = [stride, h, w, dh, dw, K.PREP_TO_RGB if to_rgb else 0]
+    return rows, offs, o
+
+
 class ImagePipeline:
-    """A pipeline that starts from files: host planning per sample, one batched device pass per batch."""
+    """A pipeline that starts from files: host planning per sample, one batched device pass per batch.  Or from frames in
+    memory (LoadImageFromWebcam first): a test pipeline whose device pass is one upload and one launch (_run_frames)."""
 
     def __init__(self, transforms, image_decode=None, index_cache=None, seg_mcus=None, sample_cache=None, cache_bytes=None):
         """image_decode ('host' / 'device'), index_cache (a directory) and seg_mcus (MCUs per index segment, or 'row'),
@@ -514,6 +580,13 @@ class ImagePipeline:
         for t in self.transforms:
             flat += [t] + (list(t.transforms) if isinstance(t, MultiScaleFlipAug) else [])
         names = [type(t).__name__ for t in flat]
+        # frames in memory: LoadImageFromWebcam stands where LoadImageFromFile does, in front of a test pipeline
+        self.frames = bool(names) and names[0] == "LoadImageFromWebcam"
+        if "LoadImageFromWebcam" in names and (not self.frames or "LoadImageFromFile" in names):
+            _refuse(f"pipeline {names} (LoadImageFromWebcam is the first stage and the only loader)")
+        if self.frames:
+            names[0] = "LoadImageFromFile"
+            self._check_frame_pipeline(flat, sample_cache)
         pos = [(_ORDER.index(n) if n in _ORDER else -1) for n in names]
         if -1 in pos or pos != sorted(set(pos)):
             _refuse(f"pipeline {names} (an image pipeline runs a subsequence of {_ORDER}, each stage once)")
@@ -532,6 +605,18 @@ class ImagePipeline:
         if self.mask_free is not None and getattr(dm.distance_transform, "extract_edge_func", None) is not None:
             _refuse("GenerateDistanceMap(extract_edge_func=...) in an image pipeline (a host callback)")
         self.tta = any(isinstance(t, MultiScaleFlipAug) for t in self.transforms)
+
+    @staticmethod
+    def _check_frame_pipeline(flat, sample_cache):
+        """a pipeline on frames is a test pipeline: no annotations, background, augmentation stages or assigner"""
+        for t in flat:
+            n = type(t).__name__
+            if n not in _FRAME_STAGES:
+                _refuse(f"{n} in a pipeline that starts with LoadImageFromWebcam (a test pipeline: {_FRAME_STAGES})")
+            if isinstance(t, RandomFlip) and t.flip_ratio:
+                _refuse("RandomFlip(flip_ratio > 0) in a pipeline that starts with LoadImageFromWebcam")
+        if sample_cache is not None:
+            _refuse("sample_cache with a pipeline that starts with LoadImageFromWebcam (frames have no file to key them)")
 
     @property
     def cache_stats(self):
@@ -669,6 +754,8 @@ class ImagePipeline:
 
     def run(self, planned, collate=False):
         """device part of a batch of planned samples; returns per-sample dicts, or one collated batch dict"""
+        if self.frames:
+            return self._run_frames(planned, collate)
         dev = self._dev()
         B = len(planned)
         hw = [tuple(s.get("resize_hw", s["img"].shape[:2])) for s in planned]
@@ -763,6 +850,47 @@ class ImagePipeline:
                 for j, i in enumerate(idx):
                     p2g[i], pw[i] = a[j], b[j]
         return self._collect(planned, out, p2g, pw, collate)
+
+    def _run_frames(self, planned, collate):
+        """device part of a batch of planned frames (LoadImageFromWebcam): the descriptor table and the host frames go up
+        in ONE pinned, non-blocking copy -- frames that are device tensors are not copied at all, the table holds their
+        addresses -- and ONE radet_preprocess_frames launch writes the batch; no packed temporaries.  Device frames must be
+        ready on the current stream; nothing here waits for the device."""
+        dev = self._dev()
+        B = len(planned)
+        frames = [s["img"] for s in planned]
+        for f in frames:
+            if isinstance(f, torch.Tensor) and f.device != dev:
+                raise ValueError(f"a frame on {f.device} in a batch prepared on {dev}")
+        hw = [tuple(int(v) for v in s.get("resize_hw", s["img"].shape[:2])) for s in planned]
+        cfg0 = planned[0]["img_norm_cfg"]
+        for s in planned[1:]:
+            c = s["img_norm_cfg"]
+            if not (np.array_equal(c["mean"], cfg0["mean"]) and np.array_equal(c["std"], cfg0["std"]) and c["to_rgb"] == cfg0["to_rgb"]):
+                raise ValueError("one batch, one Normalize")
+        if any(s.get("flip") for s in planned):
+            raise ValueError("a pipeline that starts with LoadImageFromWebcam does not flip")
+        Hp = max(s["pad_shape"][0] for s in planned)
+        Wp = max(s["pad_shape"][1] for s in planned)
+        if any(s["pad_shape"][0] < h or s["pad_shape"][1] < w for s, (h, w) in zip(planned, hw)):
+            raise ValueError("pad_shape smaller than the image")
+        # upload buffer: [descriptor table | host frames, packed]; the table needs the buffer's address, so allocate first
+        head = B * K.PREP_DESC_INTS * 4
+        _, _, nbytes = frame_desc_rows(frames, hw, cfg0["to_rgb"], 0)
+        up = torch.empty(head + nbytes, dtype=torch.uint8, device=dev)
+        rows, offs, _ = frame_desc_rows(frames, hw, cfg0["to_rgb"], up.data_ptr() + head)
+        stage = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=True)
+        host = stage.numpy()
+        host[:head] = rows.reshape(-1).view(np.uint8)
+        for f, o in zip(frames, offs):
+            if o is not None:
+                np.copyto(host[head + o:head + o + f.size].reshape(f.shape), f)
+        up.copy_(stage, non_blocking=True)
+        out = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=dev)
+        mean = cfg0["mean"].astype(np.float64).astype(np.float32)
+        stdinv = (1.0 / cfg0["std"].astype(np.float64)).astype(np.float32)
+        K.preprocess_frames(up[:head].view(torch.int32), B, Hp, Wp, mean, stdinv, out)
+        return self._collect(planned, out, None, None, collate)
 
     def _distance_maps(self, planned, hw, img, lsum, params, dev):
         """The mask-free sampler's maps of a batch, f32 [G_i, h, w] per sample: every box's padded crop cut from the

@@ -1653,6 +1653,20 @@ def paste_maps(maps, desc, n, H, W, out):
               H, W, _ptr(out), _stream())
 
 
+# ---------------------------------------------------------------------- in-memory frames, one launch (csrc/preprocess.hip)
+PREP_DESC_INTS = 8                 # include/radet_hip.h
+PREP_TO_RGB = 1
+
+
+def preprocess_frames(desc, n, Hp, Wp, mean, stdinv, out):
+    """u8 HWC BGR frames at the addresses of desc i32 [n, PREP_DESC_INTS] -> out f32 [n, 3, Hp, Wp]: resize, optional
+    BGR->RGB, (q - mean) * stdinv, zero pad -- what resize_linear_u8 -> augment_finish give, in one launch"""
+    assert out.dtype == torch.float32 and out.numel() >= n * 3 * Hp * Wp and desc.dtype == torch.int32
+    assert desc.numel() >= n * PREP_DESC_INTS
+    _lib.call("radet_preprocess_frames", _ptr(desc), int(n), int(Hp), int(Wp), *[float(v) for v in mean],
+              *[float(v) for v in stdinv], _ptr(out), _stream())
+
+
 # ---------------------------------------------------------------------- COCO-protocol evaluation (csrc/cocoeval.hip)
 COCO_MAX_GT = 512                  # RADET_COCO_MAX_GT of include/radet_hip.h: ground truths per (category, image) segment
 COCO_ERR_OVERSIZE = -3             # RADET_ERR_COCO_OVERSIZE

@@ -1,0 +1,132 @@
+"""Times the preparation of in-memory frames and writes profiles/bench_frames.json:
+
+  * the frame path (ImagePipeline on LoadImageFromWebcam: one pinned upload, one radet_preprocess_frames launch) against
+    the file pipeline's device chain (upload, radet_resize_linear_u8, the four augmentation launches) fed the SAME pixels
+    from host arrays, per batch of --batch frames of 640 x 480 -> img_scale (640, 480), upload included, planning excluded;
+    the two are timed in alternation, round by round, and their outputs are compared bit for bit first;
+  * the same frame path on frames that already are device tensors (no pixel upload);
+  * `detect_frames` end to end (host frames in, per-class arrays out) in images / s.
+
+Host clock around work that ends in a device synchronise; medians over --reps rounds of --iters batches after a warm-up of
+every shape.  No figure here is a pass condition.
+
+    python tools/bench_frames.py [--batch 8] [--iters 50] [--reps 7] [--frames 400]
+"""
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+NORM = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
+
+
+def pipeline_cfg(loader):
+    return [dict(type=loader),
+            dict(type="MultiScaleFlipAug", img_scale=(640, 480), flip=False, transforms=[
+                dict(type="Resize", keep_ratio=True), dict(type="RandomFlip"), dict(type="Normalize", **NORM),
+                dict(type="Pad", size_divisor=32), dict(type="ImageToTensor", keys=["img"]), dict(type="Collect", keys=["img"])])]
+
+
+def wall_ms(fn, iters):
+    """host milliseconds per call of `iters` back-to-back calls, the last one followed by a device synchronise"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--frames", type=int, default=400, help="frames of the end-to-end pass")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_frames.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_frames.py measures on the GPU: no device found")
+    from radet_amd.apis import detect_frames
+    from radet_amd.datasets.loading import ImagePipeline
+    from radet_amd.models import build_detector
+    from radet_amd.utils import Config
+    from radet_amd.utils.synth_init import synth_fill
+    dev = torch.device("cuda")
+    B = args.batch
+    rng = np.random.RandomState(0)
+    frames = [rng.randint(0, 256, (480, 640, 3)).astype(np.uint8) for _ in range(B)]
+    on_dev = [torch.from_numpy(f).to(dev) for f in frames]
+    new, old = ImagePipeline(pipeline_cfg("LoadImageFromWebcam")), ImagePipeline(pipeline_cfg("LoadImageFromFile"))
+
+    def plan(imgs):
+        return [new.plan(dict(img=f, bbox_fields=[], mask_fields=[], seg_fields=[]), random, np.random) for f in imgs]
+    planned, planned_dev = plan(frames), plan(on_dev)
+    # (a planned frame is what the file pipeline plans for a decoded file, but for the file names: its device chain takes it)
+    a = new.run(planned, collate=True)["img"][0]
+    b = old.run(planned, collate=True)["img"][0]
+    c = new.run(planned_dev, collate=True)["img"][0]
+    torch.cuda.synchronize()
+    equal = bool(torch.equal(a, b) and torch.equal(a, c))
+    paths = dict(frames_ms=lambda: new.run(planned, collate=True), file_chain_ms=lambda: old.run(planned, collate=True),
+                 device_frames_ms=lambda: new.run(planned_dev, collate=True))
+    for fn in paths.values():                                       # warm-up: code objects, pinned and device allocator
+        wall_ms(fn, 10)
+    rounds = {k: [] for k in paths}
+    for _ in range(args.reps):
+        for k, fn in paths.items():                                 # alternating: drift hits every path alike
+            rounds[k].append(wall_ms(fn, args.iters))
+    plan_ms = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        plan(frames)
+        plan_ms.append((time.perf_counter() - t0) * 1e3)
+
+    cfg = Config.fromfile(os.path.join(ROOT, "configs", "bop", "r50_ycbv_pbr.py"))
+    cfg.model["pretrained"] = None
+    torch.manual_seed(0)
+    model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).to(dev).eval()
+    synth_fill(model, seed=0)
+    model.cfg = Config(dict(data=dict(test=dict(pipeline=pipeline_cfg("LoadImageFromFile")))))
+    n = -(-args.frames // B) * B
+
+    def end_to_end():
+        return sum(1 for _ in detect_frames(model, (frames[i % B] for i in range(n)), batch_size=B))
+    end_to_end()
+    e2e = []
+    for _ in range(max(3, args.reps // 2)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        assert end_to_end() == n
+        torch.cuda.synchronize()
+        e2e.append(n / (time.perf_counter() - t0))
+
+    med = statistics.median
+    out = dict(case=dict(batch=B, frame_hw=[480, 640], img_scale=[640, 480], pad_divisor=32, iters=args.iters, reps=args.reps),
+               device=torch.cuda.get_device_name(0), clocks="default governor, not pinned; medians of alternating rounds",
+               outputs_bit_identical=equal,
+               prepare_frames_ms=med(rounds["frames_ms"]), prepare_file_chain_ms=med(rounds["file_chain_ms"]),
+               prepare_device_frames_ms=med(rounds["device_frames_ms"]),
+               prepare_frames_ms_all=rounds["frames_ms"], prepare_file_chain_ms_all=rounds["file_chain_ms"],
+               prepare_device_frames_ms_all=rounds["device_frames_ms"],
+               file_chain_over_frames=med(rounds["file_chain_ms"]) / med(rounds["frames_ms"]),
+               plan_ms_per_batch=med(plan_ms), detect_frames_images=n, detect_frames_img_per_s=med(e2e),
+               detect_frames_img_per_s_all=e2e)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
