@@ -460,6 +460,14 @@ int radet_resize_linear_u8(const uint8_t* src, const int* src_desc, uint8_t* dst
                            int max_dst_px, int channels, void* stream);
 int radet_resize_linear_f(const void* src, const int* src_desc, void* dst, const int* dst_desc, int ncrop, int max_dst_px,
                           int is_f64, void* stream);
+/* radet_resize_linear_u8 for Resize followed by RandomCrop: only a window of each resized image is computed.  win_desc
+ * (device) = ncrop rows of RESIZE_WIN_DESC_INTS ints {packed pixel offset, window h, w, virtual resized Hr, Wr, window
+ * origin y0, x0}: the scale factors and taps are those of (src h, w) -> (Hr, Wr), output pixel (y, x) of the row is the
+ * virtual pixel (y0 + y, x0 + x) -- bit for bit the full resize, sliced; h * w pixels are written at the offset.  A row
+ * whose window is not inside its Hr x Wr image is not written.  max_dst_px = the largest window's pixel count. */
+#define RESIZE_WIN_DESC_INTS 7
+int radet_resize_linear_u8_window(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* win_desc, int ncrop,
+                                  int max_dst_px, int channels, void* stream);
 int radet_gaussian_blur9_u8(const uint8_t* src, const int* desc, uint8_t* dst, float* tmp, const float* kernel5, int ncrop,
                             int max_px, void* stream);
 int radet_sobel_edge(const uint8_t* src, const int* desc, float* edge, uint8_t* gray_ws, uint32_t* max_ws, int ncrop,
@@ -473,6 +481,16 @@ int radet_sobel_edge(const uint8_t* src, const int* desc, float* edge, uint8_t* 
 int radet_mask_max(const uint8_t* masks, uint32_t* maxes /* [G] */, int G, size_t hw, void* stream);
 int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, int G, int Hs, int Ws, int Hr, int Wr,
                          int Hd, int Wd, int flip, int pad_val, void* stream);
+/* the window variants (Resize followed by RandomCrop): per mask a window of its virtual resized mask, one geometry per mask.
+ * win_desc (device) i32 [G][MASK_WIN_INTS] = {virtual resized Hr, Wr, window origin y0, x0, window h, w, flip}:
+ *      dst[g][y][x] = y < h && x < w ? norm(src[g][nn(y0 + flip_y(y))][nn(x0 + flip_x(x))]) : pad_val, nn over the Hr x Wr
+ *      grid, the flip inside the window (it follows the crop), norm_max still the maximum of the whole source mask: what
+ *      radet_mask_transform to [Hr, Wr] gives, sliced and then flipped.  h <= Hd, w <= Wd; a row whose window is not inside
+ *      its Hr x Wr mask writes pad_val only.  radet_rle_masks_window: the same window of what radet_rle_masks decodes; the
+ *      flip is mask_desc's (the flip word of win_desc is not read), dst_plain as there. */
+#define MASK_WIN_INTS 7
+int radet_mask_transform_window(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, const int* win_desc, int G, int Hs,
+                                int Ws, int Hd, int Wd, int pad_val, void* stream);
 
 /* ---- the same masks from run-length annotations (COCO RLE / rasterised polygons, radet/datasets/pipelines/loading.py:313-380
  *      `_poly2mask`), without a bitmap on the host or in HBM: one launch per group of masks of one destination geometry.
@@ -489,6 +507,8 @@ int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint32_t* norm_
 #define RLE_PART_INTS 2
 int radet_rle_masks(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc, int G,
                     uint8_t* dst, uint8_t* dst_plain, int Hr, int Wr, int Hd, int Wd, int pad_val, void* stream);
+int radet_rle_masks_window(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc,
+                           const int* win_desc, int G, uint8_t* dst, uint8_t* dst_plain, int Hd, int Wd, int pad_val, void* stream);
 
 /* ---- baseline JPEG files decoded on the device (csrc/jpeg.hip, csrc/jpeg_index.c, radet_amd/core/jpeg.py): what libjpeg's
  *      default decompressor gives for them byte for byte (slow-integer IDCT, fancy upsampling, fixed-point YCbCr -> RGB),
@@ -522,7 +542,9 @@ int radet_jpeg_decode(const uint8_t* files, const int* desc, int nimg, const int
  *      PillowSharpness / PillowContrast / PillowBrightness / PillowColor, RandomFlip, Normalize, Pad, batched over packed
  *      u8 HWC BGR images (every buffer packed alike).  params (device) = nimg rows of AUG_PARAM_INTS ints:
  *      {pixel offset, h, w, flags, background pixel offset, mask count, mask address lo, hi (u8 [G,h,w]), blur radius,
- *       blur ww, blur fw, f32 bits of the sharpness / contrast / brightness / color factors, 0};
+ *       blur ww, blur fw, f32 bits of the sharpness / contrast / brightness / color factors, mask pitch};
+ *      mask pitch: 0, or Hm << 16 | Wm when the masks are the top-left h x w of u8 [G,Hm,Wm] (Hm >= h, Wm >= w; the
+ *      assigner's zero-padded masks of a sample smaller than a fixed pad size serve the merge as they are);
  *      flags: 1 merge, 2 blur, 4 sharpness, 8 contrast, 16 brightness, 32 color, 64 horizontal flip, 128 BGR->RGB.
  *      Four launches per batch in this order; lsum = one u64 luma sum per image (sharp -> finish); out = f32 [nimg,3,Hp,Wp]
  *      with out = (x - m) * s per channel and zeros beyond each image.  Widths and heights up to AUG_MAX_W. */

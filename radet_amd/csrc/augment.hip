@@ -71,13 +71,18 @@ __global__ __launch_bounds__(256) void aug_merge_hblur_kernel(const uint8_t* __r
     uint8_t* A = lds;
     uint8_t* B = lds + n;
     const size_t row = (size_t)a.off + (size_t)y * a.w;
-    const size_t plane = (size_t)a.h * a.w;
+    // the masks are u8 [G,h,w], or (mask pitch word Hm << 16 | Wm) the top-left h x w of u8 [G,Hm,Wm]; a pitch that does
+    // not hold the image counts as no masks
+    const int pitch = params[AUG_PARAM_INTS * blockIdx.y + 15];
+    const int mh = pitch ? pitch >> 16 : a.h, mw = pitch ? pitch & 0xFFFF : a.w;
+    const int nmask = (mh >= a.h && mw >= a.w) ? a.nmask : 0;
+    const size_t mplane = (size_t)mh * mw;
     for (int i = threadIdx.x; i < n; i += 256) {
         uint8_t v = src[row * 3 + i];
         if (a.flags & AUG_MERGE) {
             const int x = i / 3;
             bool fg = false;
-            for (int g = 0; g < a.nmask && !fg; ++g) fg = a.masks[g * plane + (size_t)y * a.w + x] == 1;
+            for (int g = 0; g < nmask && !fg; ++g) fg = a.masks[g * mplane + (size_t)y * mw + x] == 1;
             if (!fg) v = bg[((size_t)a.bg_off + (size_t)y * a.w) * 3 + i];
         }
         A[i] = v;

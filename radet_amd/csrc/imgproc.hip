@@ -48,6 +48,29 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restric
         o[c] = (uint8_t)lin_blend_u8(r0[t.sx * C + c], r0[t.x1 * C + c], r1[t.sx * C + c], r1[t.x1 * C + c], t);
 }
 
+// The window variant (Resize + RandomCrop): only the h x w window at (y0, x0) of the virtual Hr x Wr resized image is
+// written, packed at the row's offset.  Output pixel (y, x) is the virtual pixel (y0 + y, x0 + x): same taps, same blend
+// as above, so the result is that of the full resize sliced.  A row whose window does not lie inside its virtual image
+// is not written.
+template <int C>
+__global__ __launch_bounds__(256) void resize_u8_window_kernel(const uint8_t* __restrict__ src, const int* __restrict__ sdesc,
+                                                               uint8_t* __restrict__ dst, const int* __restrict__ wdesc) {
+    const Crop s = load_crop(sdesc, blockIdx.y);
+    const int* d = wdesc + RESIZE_WIN_DESC_INTS * blockIdx.y;
+    const int h = d[1], w = d[2], Hr = d[3], Wr = d[4], y0 = d[5], x0 = d[6];
+    if (h <= 0 || w <= 0 || y0 < 0 || x0 < 0 || y0 > Hr - h || x0 > Wr - w || s.h <= 0 || s.w <= 0) return;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= h * w) return;
+    const int dy = p / w, dx = p - dy * w;
+    const LinTaps t = lin_taps_u8(y0 + dy, x0 + dx, s.h, s.w, Hr, Wr);
+    const uint8_t* r0 = src + ((size_t)s.off + (size_t)t.y0 * s.w) * C;
+    const uint8_t* r1 = src + ((size_t)s.off + (size_t)t.y1 * s.w) * C;
+    uint8_t* o = dst + ((size_t)d[0] + p) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+        o[c] = (uint8_t)lin_blend_u8(r0[t.sx * C + c], r0[t.x1 * C + c], r1[t.sx * C + c], r1[t.x1 * C + c], t);
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void resize_f_kernel(const T* __restrict__ src, const int* __restrict__ sdesc,
                                                        T* __restrict__ dst, const int* __restrict__ ddesc) {
@@ -217,6 +240,19 @@ extern "C" int radet_resize_linear_u8(const uint8_t* src, const int* src_desc, u
         hipLaunchKernelGGL(resize_u8_kernel<3>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc, dst, dst_desc);
     else
         hipLaunchKernelGGL(resize_u8_kernel<1>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc, dst, dst_desc);
+    return radet_check_launch();
+}
+
+extern "C" int radet_resize_linear_u8_window(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* win_desc, int ncrop,
+                                             int max_dst_px, int channels, void* stream) {
+    if (ncrop < 0 || max_dst_px < 0 || (channels != 1 && channels != 3)) return RADET_ERR_ARG;
+    if (ncrop == 0 || max_dst_px == 0) return RADET_OK;
+    if (channels == 3)
+        hipLaunchKernelGGL(resize_u8_window_kernel<3>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc, dst,
+                           win_desc);
+    else
+        hipLaunchKernelGGL(resize_u8_window_kernel<1>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc, dst,
+                           win_desc);
     return radet_check_launch();
 }
 

@@ -24,13 +24,38 @@ __device__ __forceinline__ int nn_src(int d, double inv, int n) {
     return s < n - 1 ? s : n - 1;
 }
 
+// A window row (WIN, include/radet_hip.h MASK_WIN_INTS) of mask g: {Hr, Wr, oy, ox, h, w, flip}.  The h x w window at
+// (oy, ox) of the virtual Hr x Wr resized mask; a window that does not lie inside its virtual mask or the destination is empty.
+struct MaskWin { int Hr, Wr, oy, ox, h, w, flip; };
+
+__device__ __forceinline__ MaskWin load_mask_win(const int* __restrict__ win, int g, int Hd, int Wd) {
+    const int* d = win + (size_t)g * MASK_WIN_INTS;
+    MaskWin m = {d[0], d[1], d[2], d[3], d[4], d[5], d[6]};
+    if (m.Hr <= 0 || m.Wr <= 0 || m.oy < 0 || m.ox < 0 || m.h < 0 || m.w < 0 || m.h > Hd || m.w > Wd || m.oy > m.Hr - m.h ||
+        m.ox > m.Wr - m.w) {
+        m.Hr = m.Wr = 1;
+        m.oy = m.ox = m.h = m.w = 0;
+    }
+    return m;
+}
+
+// WIN: the resized geometry comes per mask from `win` (the kernel arguments Hr, Wr, ify, ifx, flip are not used) and the
+// flip acts inside the window; otherwise the window is the whole resized mask at the origin.
+template <bool WIN>
 __global__ __launch_bounds__(256) void mask_transform_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                             const unsigned* __restrict__ norm_max, int Hs, int Ws, int Hr,
-                                                             int Wr, int Hd, int Wd, double ify, double ifx, int flip,
-                                                             int pad_val) {
+                                                             const unsigned* __restrict__ norm_max, const int* __restrict__ win,
+                                                             int Hs, int Ws, int Hr, int Wr, int Hd, int Wd, double ify,
+                                                             double ifx, int flip, int pad_val) {
     const int g = blockIdx.z, y = blockIdx.y;
     const int x0 = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (x0 >= Wd) return;
+    int oy = 0, ox = 0;
+    if (WIN) {
+        const MaskWin m = load_mask_win(win, g, Hd, Wd);
+        oy = m.oy; ox = m.ox; flip = m.flip & 3;
+        ify = 1.0 / ((double)m.Hr / (double)Hs); ifx = 1.0 / ((double)m.Wr / (double)Ws);
+        Hr = m.h; Wr = m.w;                                   // (from here on: the window's size)
+    }
     const uint8_t* sp = src + (size_t)g * Hs * Ws;
     const unsigned mx = norm_max ? norm_max[g] : 0u;
     unsigned out[4];
@@ -41,7 +66,7 @@ __global__ __launch_bounds__(256) void mask_transform_kernel(const uint8_t* __re
         if (y < Hr && x < Wr) {
             const int yr = (flip & 2) ? Hr - 1 - y : y;       // flip acts on the resized image
             const int xr = (flip & 1) ? Wr - 1 - x : x;
-            v = sp[(size_t)nn_src(yr, ify, Hs) * Ws + nn_src(xr, ifx, Ws)];
+            v = sp[(size_t)nn_src(oy + yr, ify, Hs) * Ws + nn_src(ox + xr, ifx, Ws)];
             // (mask / mask.max()).astype(u8): 1 where the value equals the mask's maximum, else 0; an all-zero mask
             // is 0 / 0 = NaN -> 0 after the cast
             if (norm_max) v = (mx != 0u && v == mx) ? 1u : 0u;
@@ -72,24 +97,34 @@ __device__ __forceinline__ int rle_run_of(const uint32_t* __restrict__ ends, int
 // ascend with x, so each part is searched once (binary, over its run ends) and the search for the next pixel starts at the
 // run found last -- one compare when it is the same run.  The packed row goes to LDS; from there the mirrored copy is
 // composed, so both orientations leave as aligned 32-bit stores and the runs are looked up once.
+// WIN: per mask the h x w window at (oy, ox) of its virtual resized mask (`win`, as above; its flip word is not read, the
+// flip is mask_desc's); the mirrored copy is composed inside the window.
 #define RLE_MAX_W 8192
+template <bool WIN>
 __global__ __launch_bounds__(256) void rle_masks_kernel(const uint32_t* __restrict__ run_ends, int n_ends,
                                                         const int* __restrict__ part_desc, int n_parts,
-                                                        const int* __restrict__ mask_desc, uint8_t* __restrict__ dst,
-                                                        uint8_t* __restrict__ dst_plain, int Hr, int Wr, int Hd, int Wd,
-                                                        int pad_val) {
+                                                        const int* __restrict__ mask_desc, const int* __restrict__ win,
+                                                        uint8_t* __restrict__ dst, uint8_t* __restrict__ dst_plain, int Hr,
+                                                        int Wr, int Hd, int Wd, int pad_val) {
     __shared__ unsigned row[RLE_MAX_W / 4 + 1];
     const int g = blockIdx.y, y = blockIdx.x;
     const int* md = mask_desc + (size_t)g * RLE_MASK_INTS;
     const int first = md[0], Hs = md[2], Ws = md[3], flip = md[4] & 1;
     int np = md[1];
     if (first < 0 || np < 0 || first > n_parts - np || Hs <= 0 || Ws <= 0) np = 0;         // (a row that points outside the part table: no parts)
+    int oy = 0, ox = 0, wh = Hr, ww = Wr;
+    if (WIN) {
+        const MaskWin m = load_mask_win(win, g, Hd, Wd);
+        oy = m.oy; ox = m.ox; wh = m.h; ww = m.w;
+        Hr = m.Hr; Wr = m.Wr;
+    }
     // OpenCV computes inv_scale = dsize / ssize and then 1. / inv_scale (not ssize / dsize)
     const double ify = 1.0 / ((double)Hr / (double)Hs), ifx = 1.0 / ((double)Wr / (double)Ws);
+    Hr = wh; Wr = ww;                                             // (from here on: the window's size)
     const unsigned pad = (unsigned)pad_val & 0xFFu;
     const int nwords = (Wd + 3) >> 2;
     const bool inside = y < Hr;
-    const uint32_t sy = inside ? (uint32_t)nn_src(y, ify, Hs) : 0u;
+    const uint32_t sy = inside ? (uint32_t)nn_src(oy + y, ify, Hs) : 0u;
     for (int wd = threadIdx.x; wd < nwords; wd += blockDim.x) {
         const int x0 = wd * 4;
         unsigned out[4] = {pad, pad, pad, pad};
@@ -98,7 +133,7 @@ __global__ __launch_bounds__(256) void rle_masks_kernel(const uint32_t* __restri
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 out[j] = x0 + j < Wr ? 0u : pad;
-                pos[j] = (uint32_t)nn_src(min(x0 + j, Wr - 1), ifx, Ws) * (uint32_t)Hs + sy;
+                pos[j] = (uint32_t)nn_src(ox + min(x0 + j, Wr - 1), ifx, Ws) * (uint32_t)Hs + sy;
             }
             for (int k = 0; k < np; ++k) {
                 const int off = part_desc[(size_t)(first + k) * RLE_PART_INTS], n = part_desc[(size_t)(first + k) * RLE_PART_INTS + 1];
@@ -164,8 +199,16 @@ extern "C" int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint
         return RADET_ERR_ARG;
     // OpenCV computes inv_scale = dsize / ssize and then 1. / inv_scale (not ssize / dsize)
     const double ify = 1.0 / ((double)Hr / (double)Hs), ifx = 1.0 / ((double)Wr / (double)Ws);
-    hipLaunchKernelGGL(mask_transform_kernel, dim3((Wd + 1023) / 1024, Hd, G), dim3(256), 0, (hipStream_t)stream, src, dst,
-                       norm_max, Hs, Ws, Hr, Wr, Hd, Wd, ify, ifx, flip, pad_val);
+    hipLaunchKernelGGL(mask_transform_kernel<false>, dim3((Wd + 1023) / 1024, Hd, G), dim3(256), 0, (hipStream_t)stream, src, dst,
+                       norm_max, (const int*)nullptr, Hs, Ws, Hr, Wr, Hd, Wd, ify, ifx, flip, pad_val);
+    return radet_check_launch();
+}
+
+extern "C" int radet_mask_transform_window(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, const int* win_desc, int G,
+                                           int Hs, int Ws, int Hd, int Wd, int pad_val, void* stream) {
+    if (G <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0 || Hd > 65535 || !win_desc) return RADET_ERR_ARG;
+    hipLaunchKernelGGL(mask_transform_kernel<true>, dim3((Wd + 1023) / 1024, Hd, G), dim3(256), 0, (hipStream_t)stream, src, dst,
+                       norm_max, win_desc, Hs, Ws, 0, 0, Hd, Wd, 0.0, 0.0, 0, pad_val);
     return radet_check_launch();
 }
 
@@ -176,7 +219,18 @@ extern "C" int radet_rle_masks(const uint32_t* run_ends, int n_ends, const int* 
         return RADET_ERR_ARG;
     const int nwords = (Wd + 3) / 4;
     const int threads = nwords >= 256 ? 256 : ((nwords + 63) / 64) * 64;
-    hipLaunchKernelGGL(rle_masks_kernel, dim3(Hd, G), dim3(threads), 0, (hipStream_t)stream, run_ends, n_ends, part_desc, n_parts,
-                       mask_desc, dst, dst_plain, Hr, Wr, Hd, Wd, pad_val);
+    hipLaunchKernelGGL(rle_masks_kernel<false>, dim3(Hd, G), dim3(threads), 0, (hipStream_t)stream, run_ends, n_ends, part_desc,
+                       n_parts, mask_desc, (const int*)nullptr, dst, dst_plain, Hr, Wr, Hd, Wd, pad_val);
+    return radet_check_launch();
+}
+
+extern "C" int radet_rle_masks_window(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc,
+                                      const int* win_desc, int G, uint8_t* dst, uint8_t* dst_plain, int Hd, int Wd, int pad_val,
+                                      void* stream) {
+    if (G <= 0 || G > 65535 || n_ends < 0 || n_parts < 0 || Hd <= 0 || Wd <= 0 || Wd > RLE_MAX_W || !win_desc) return RADET_ERR_ARG;
+    const int nwords = (Wd + 3) / 4;
+    const int threads = nwords >= 256 ? 256 : ((nwords + 63) / 64) * 64;
+    hipLaunchKernelGGL(rle_masks_kernel<true>, dim3(Hd, G), dim3(threads), 0, (hipStream_t)stream, run_ends, n_ends, part_desc,
+                       n_parts, mask_desc, win_desc, dst, dst_plain, 0, 0, Hd, Wd, pad_val);
     return radet_check_launch();
 }

@@ -218,8 +218,8 @@ class BOPDataset:
         wh = np.array([[i["width"], i["height"]] for i in self.data_infos], dtype=np.float64).reshape(-1, 2)
         self.flag = (wh[:, 0] > wh[:, 1]).astype(np.uint8)
 
-    def _rand_another(self, idx):
-        return np.random.choice(np.flatnonzero(self.flag == self.flag[idx]))
+    def _rand_another(self, idx, nprnd=np.random):
+        return nprnd.choice(np.flatnonzero(self.flag == self.flag[idx]))
 
     # ------------------------------------------------------------------ samples
     def pre_pipeline(self, results):
@@ -237,8 +237,13 @@ class BOPDataset:
         return self.pipeline(self._results(idx, with_ann))
 
     def plan_sample(self, idx, rnd, nprnd):
-        """host part of sample `idx` of an image pipeline on the given generators (thread-safe for distinct ones)"""
-        return self.pipeline.plan(self._results(idx, not self.test_mode), rnd, nprnd)
+        """host part of sample `idx` of an image pipeline on the given generators (thread-safe for distinct ones); when the
+        pipeline drops the sample (a RandomCrop without a gt box), another image of the same group, drawn from and planned
+        on the same generators -- what __getitem__ does on the global ones"""
+        s = self.pipeline.plan(self._results(idx, not self.test_mode), rnd, nprnd)
+        while s is None and not self.test_mode:
+            s = self.pipeline.plan(self._results(self._rand_another(idx, nprnd), True), rnd, nprnd)
+        return s
 
     def prepare_train_img(self, idx):
         return self._sample(idx, True)

@@ -16,6 +16,9 @@ sample_cache='device' decoded frames and backgrounds stay in HBM after their fir
 with one radet_copy_segments launch (sample_cache.py).  A single sample (`BOPDataset.__getitem__`) is a batch
 of one.  A pipeline whose first stage is LoadImageFromWebcam takes frames that are in memory already (ndarray or device
 tensor): a test pipeline, whose run() is one pinned upload and one radet_preprocess_frames launch (_run_frames).
+Scale jitter (Resize with random scales, RandomCrop, Pad(size=)): RandomCrop plans a window of the virtual resized image and
+run() computes that window only -- radet_resize_linear_u8_window, radet_mask_transform_window, radet_rle_masks_window in
+the place of their plain counterparts -- so a batch keeps one tensor shape at the cost of the crop's pixels.
 Options the RADet configs do not use raise NotImplementedError."""
 import glob
 import math
@@ -37,7 +40,7 @@ osp = os.path
 DEFAULT_META_KEYS = ("filename", "ori_filename", "ori_shape", "img_shape", "pad_shape", "scale_factor", "flip",
                      "flip_direction", "img_norm_cfg")
 # stage order of the device part (a pipeline lists a subsequence of it; MultiScaleFlipAug's transforms sit in its place)
-_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Resize", "RandomBackground", "CosyPoseAug", "RandomHSV",
+_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Resize", "RandomCrop", "RandomBackground", "CosyPoseAug", "RandomHSV",
           "RandomNoise", "RandomSmooth", "RandomFlip", "GenerateDistanceMap", "LabelAssignment", "Normalize", "Pad",
           "DefaultFormatBundle", "ImageToTensor", "Collect")
 _MIX = ("RandomHSV", "RandomNoise", "RandomSmooth")          # the mixpbr stages: aug_hsv_noise + aug_box
@@ -232,21 +235,54 @@ class LoadAnnotations:
 # ---------------------------------------------------------------------------------------------------- geometry
 @PIPELINES.register_module()
 class Resize:
+    """One scale, or the reference's random scales (transforms.py:97-200), drawn from the sample's NumPy generator with the
+    reference's calls in its order: ratio_range -> random_sample(); several img_scale values with multiscale_mode 'range'
+    -> randint for the long edge, then the short edge; 'value' -> randint(len(img_scale))."""
+
     def __init__(self, img_scale=None, multiscale_mode="range", ratio_range=None, keep_ratio=True, bbox_clip_border=True,
                  backend="cv2", override=False):
-        scales = None if img_scale is None else (img_scale if isinstance(img_scale, list) else [img_scale])
-        if scales is not None and len(scales) != 1:
-            _refuse("Resize with several img_scale values")
-        if ratio_range is not None or override or backend != "cv2":
-            _refuse("Resize(ratio_range / override / backend)")
-        self.img_scale = None if scales is None else tuple(scales[0])
+        if override or backend != "cv2":
+            _refuse("Resize(override / backend)")
+        if img_scale is None:
+            self.img_scale = None
+        else:
+            scales = img_scale if isinstance(img_scale, list) else [img_scale]
+            if not scales or not all(isinstance(v, (tuple, list)) and len(v) == 2 for v in scales):
+                raise TypeError(f"Resize: img_scale is a tuple or a list of tuples, got {img_scale!r}")
+            self.img_scale = [tuple(v) for v in scales]
+        if ratio_range is not None:
+            if self.img_scale is None or len(self.img_scale) != 1:
+                raise ValueError("Resize(ratio_range=...) takes exactly one img_scale")
+            if len(ratio_range) != 2 or not ratio_range[0] <= ratio_range[1]:
+                raise ValueError(f"Resize: ratio_range is (min_ratio, max_ratio), got {ratio_range!r}")
+        elif multiscale_mode not in ("value", "range"):
+            raise ValueError(f"Resize: multiscale_mode is 'value' or 'range', got {multiscale_mode!r}")
+        elif multiscale_mode == "range" and self.img_scale is not None and len(self.img_scale) not in (1, 2):
+            raise ValueError("Resize(multiscale_mode='range') takes two img_scale values: the bounds of the range")
+        self.multiscale_mode, self.ratio_range = multiscale_mode, None if ratio_range is None else tuple(ratio_range)
         self.keep_ratio, self.bbox_clip_border = keep_ratio, bbox_clip_border
+
+    def _random_scale(self, nprnd):
+        """(scale, scale_idx) as Resize._random_scale of the reference sets them"""
+        if self.ratio_range is not None:
+            lo, hi = self.ratio_range
+            ratio = nprnd.random_sample() * (hi - lo) + lo
+            return (int(self.img_scale[0][0] * ratio), int(self.img_scale[0][1] * ratio)), None
+        if len(self.img_scale) == 1:
+            return self.img_scale[0], 0
+        if self.multiscale_mode == "range":
+            long_, short = [max(v) for v in self.img_scale], [min(v) for v in self.img_scale]
+            long_edge = nprnd.randint(min(long_), max(long_) + 1)
+            short_edge = nprnd.randint(min(short), max(short) + 1)
+            return (long_edge, short_edge), None
+        idx = nprnd.randint(len(self.img_scale))
+        return self.img_scale[idx], idx
 
     def plan(self, s, rnd, nprnd):
         if "scale" not in s:
             if self.img_scale is None:
                 raise KeyError("Resize: no img_scale given and no 'scale' in the results")
-            s["scale"], s["scale_idx"] = self.img_scale, 0
+            s["scale"], s["scale_idx"] = self._random_scale(nprnd)
         h, w = s["img"].shape[:2]
         if self.keep_ratio:
             nw, nh = rescale_size((w, h), s["scale"])
@@ -262,6 +298,75 @@ class Resize:
                 b[:, 0::2] = np.clip(b[:, 0::2], 0, nw)
                 b[:, 1::2] = np.clip(b[:, 1::2], 0, nh)
             s[key] = b
+
+
+@PIPELINES.register_module()
+class RandomCrop:
+    """The reference's RandomCrop (transforms.py:587-770), planned: the crop-size draws of _get_crop_size, then offset_h,
+    then offset_w, on the sample's NumPy generator; boxes shifted, clipped and filtered, the labels and masks of dropped
+    boxes dropped with them.  No pixel is touched: s["crop_window"] = (y0, x0, h, w) inside the virtual resized image
+    s["resize_hw"]; ImagePipeline.run computes that window only.  plan() returns False for a crop without a gt box
+    (allow_negative_crop=False): the reference's None, ImagePipeline.plan returns None then."""
+    bbox2label = {"gt_bboxes": "gt_labels", "gt_bboxes_ignore": "gt_labels_ignore"}
+    bbox2mask = {"gt_bboxes": "gt_masks", "gt_bboxes_ignore": "gt_masks_ignore"}
+
+    def __init__(self, crop_size, crop_type="absolute", allow_negative_crop=False, bbox_clip_border=True):
+        if crop_type not in ("relative_range", "relative", "absolute", "absolute_range"):
+            raise ValueError(f"Invalid crop_type {crop_type}.")
+        if crop_type in ("absolute", "absolute_range"):
+            if not (isinstance(crop_size[0], int) and isinstance(crop_size[1], int) and crop_size[0] > 0 and crop_size[1] > 0):
+                raise ValueError(f"RandomCrop(crop_type={crop_type!r}): crop_size is two positive ints, got {crop_size!r}")
+            if crop_type == "absolute_range" and crop_size[0] > crop_size[1]:
+                raise ValueError(f"RandomCrop(crop_type='absolute_range'): crop_size is (min, max), got {crop_size!r}")
+        elif not (0 < crop_size[0] <= 1 and 0 < crop_size[1] <= 1):
+            raise ValueError(f"RandomCrop(crop_type={crop_type!r}): crop_size is two ratios in (0, 1], got {crop_size!r}")
+        self.crop_size, self.crop_type = tuple(crop_size), crop_type
+        self.allow_negative_crop, self.bbox_clip_border = allow_negative_crop, bbox_clip_border
+
+    def _get_crop_size(self, h, w, nprnd):
+        if self.crop_type == "absolute":
+            return min(self.crop_size[0], h), min(self.crop_size[1], w)
+        if self.crop_type == "absolute_range":
+            crop_h = nprnd.randint(min(h, self.crop_size[0]), min(h, self.crop_size[1]) + 1)
+            crop_w = nprnd.randint(min(w, self.crop_size[0]), min(w, self.crop_size[1]) + 1)
+            return crop_h, crop_w
+        if self.crop_type == "relative":
+            crop_h, crop_w = self.crop_size
+        else:
+            size = np.asarray(self.crop_size, dtype=np.float32)
+            crop_h, crop_w = size + nprnd.rand(2) * (1 - size)
+        return int(h * crop_h + 0.5), int(w * crop_w + 0.5)
+
+    def plan(self, s, rnd, nprnd):
+        h, w = (int(v) for v in s["img_shape"][:2])
+        ch, cw = self._get_crop_size(h, w, nprnd)
+        if ch <= 0 or cw <= 0:
+            raise ValueError(f"RandomCrop: a crop of {ch} x {cw} from an image of {h} x {w}")
+        y0 = int(nprnd.randint(0, max(h - ch, 0) + 1))
+        x0 = int(nprnd.randint(0, max(w - cw, 0) + 1))
+        ch, cw = min(ch, h - y0), min(cw, w - x0)
+        offset = np.array([x0, y0, x0, y0], dtype=np.float32)
+        for key in s.get("bbox_fields", []):
+            b = s[key] - offset
+            if self.bbox_clip_border:
+                b[:, 0::2] = np.clip(b[:, 0::2], 0, cw)
+                b[:, 1::2] = np.clip(b[:, 1::2], 0, ch)
+            valid = (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
+            if key == "gt_bboxes" and not valid.any() and not self.allow_negative_crop:
+                return False
+            s[key] = b[valid, :]
+            label_key, mask_key = self.bbox2label.get(key), self.bbox2mask.get(key)
+            if label_key in s:
+                s[label_key] = s[label_key][valid]
+            if mask_key in s:
+                s[mask_key] = s[mask_key][valid.nonzero()[0]]
+            if mask_key is not None and mask_key + "_rle" in s:
+                parts, src_hw = s[mask_key + "_rle"]
+                s[mask_key + "_rle"] = ([parts[k] for k in valid.nonzero()[0]], src_hw)
+        s.setdefault("resize_hw", (h, w))
+        s["crop_window"] = (y0, x0, ch, cw)
+        # (pad_shape follows the crop, so that a pipeline without Pad collects the cropped image)
+        s["img_shape"] = s["pad_shape"] = (ch, cw, 3)
 
 
 @PIPELINES.register_module()
@@ -302,12 +407,21 @@ class Normalize:
 @PIPELINES.register_module()
 class Pad:
     def __init__(self, size=None, size_divisor=None, pad_val=0):
-        if size is not None or size_divisor is None or pad_val != 0:
-            _refuse("Pad(size= / pad_val != 0)")
-        self.size_divisor = int(size_divisor)
+        if pad_val != 0:
+            _refuse("Pad(pad_val != 0)")
+        if (size is None) == (size_divisor is None):
+            raise ValueError("Pad takes one of size and size_divisor")
+        self.size = None if size is None else (int(size[0]), int(size[1]))
+        self.size_divisor = None if size_divisor is None else int(size_divisor)
 
     def plan(self, s, rnd, nprnd):
         h, w = s["img_shape"][:2]
+        if self.size is not None:
+            if h > self.size[0] or w > self.size[1]:
+                raise ValueError(f"Pad(size={self.size}): the image is {h} x {w}")
+            s["pad_shape"] = (*self.size, 3)
+            s["pad_fixed_size"], s["pad_size_divisor"] = self.size, None
+            return
         d = self.size_divisor
         s["pad_shape"] = (int(math.ceil(h / d)) * d, int(math.ceil(w / d)) * d, 3)
         s["pad_fixed_size"], s["pad_size_divisor"] = None, d
@@ -588,6 +702,10 @@ class ImagePipeline:
             names[0] = "LoadImageFromFile"
             self._check_frame_pipeline(flat, sample_cache)
         pos = [(_ORDER.index(n) if n in _ORDER else -1) for n in names]
+        if "RandomCrop" in names and (-1 not in pos and pos != sorted(set(pos)) or any(isinstance(t, MultiScaleFlipAug) for t in flat)):
+            _refuse(f"RandomCrop at position {names.index('RandomCrop')} of {names} (it stands directly after Resize: after "
+                    f"{_ORDER[:_ORDER.index('RandomCrop')][-3:]}, before every stage of {_ORDER[_ORDER.index('RandomCrop') + 1:]}; "
+                    f"not in a MultiScaleFlipAug pipeline)")
         if -1 in pos or pos != sorted(set(pos)):
             _refuse(f"pipeline {names} (an image pipeline runs a subsequence of {_ORDER}, each stage once)")
         if "CosyPoseAug" in names and any(n in _MIX for n in names):
@@ -628,14 +746,16 @@ class ImagePipeline:
         s = dict(results)
         for t in self.transforms:
             if not isinstance(t, LabelAssignment):     # (device-only: run() does it; GenerateDistanceMap plans its crops)
-                t.plan(s, rnd, nprnd)
+                if t.plan(s, rnd, nprnd) is False:     # (RandomCrop left no gt box: the reference's pipeline returns None)
+                    return None
         s["_nprnd"] = nprnd
         return s
 
     def __call__(self, results):
-        """one sample on the global generators, like the reference"""
+        """one sample on the global generators, like the reference (None when RandomCrop dropped it)"""
         import random
-        return self.run([self.plan(results, random, np.random)])[0]
+        s = self.plan(results, random, np.random)
+        return None if s is None else self.run([s])[0]
 
     # --------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -735,9 +855,11 @@ class ImagePipeline:
                 what = "; ".join(f"{p}: " + ", ".join(v for k, v in jpeg.ERRORS.items() if e & k) for p, e in bad)
                 raise ValueError(f"device JPEG decode failed (the pixels of that batch are undefined): {what}")
 
-    def _resize_packed(self, arrays, dst_hw, dev, align=1, src=None):
+    def _resize_packed(self, arrays, dst_hw, dev, align=1, src=None, windows=None):
         """u8 HWC images of any sizes -> one packed device buffer of the dst sizes (one resize launch); every image starts at
-        a multiple of `align` pixels.  src: (packed device buffer, pixel offsets) when the images are there already"""
+        a multiple of `align` pixels.  src: (packed device buffer, pixel offsets) when the images are there already.
+        windows: per image (Hr, Wr, y0, x0) -- dst_hw is then the size of the window at (y0, x0) of the Hr x Wr resized
+        image, and only that window is computed (radet_resize_linear_u8_window)"""
         src, src_offs = src if src is not None else (torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(dev), None)
         sdesc, ddesc, so, do = [], [], 0, 0
         for k, (a, (h, w)) in enumerate(zip(arrays, dst_hw)):
@@ -747,8 +869,15 @@ class ImagePipeline:
             so += a.shape[0] * a.shape[1]
             do += -(-h * w // align) * align
         dst = torch.empty(do * 3, dtype=torch.uint8, device=dev)
-        desc = torch.from_numpy(np.array(sdesc + ddesc, np.int32).reshape(-1, 3)).to(dev)
         n = len(arrays)
+        if windows is not None:
+            # (one upload: the source rows, then the window rows)
+            wdesc = [(*d, *win) for d, win in zip(ddesc, windows)]
+            desc = torch.from_numpy(np.concatenate([np.array(sdesc, np.int32).reshape(-1), np.array(wdesc, np.int32).reshape(-1)])).to(dev)
+            K.resize_linear_u8_window(src, desc[:3 * n].view(n, 3), dst, desc[3 * n:].view(n, K.RESIZE_WIN_DESC_INTS), n,
+                                      max(h * w for h, w in dst_hw), 3)
+            return dst, [d[0] for d in ddesc]
+        desc = torch.from_numpy(np.array(sdesc + ddesc, np.int32).reshape(-1, 3)).to(dev)
         K.resize_linear_u8(src, desc[:n], dst, desc[n:], n, max(h * w for h, w in dst_hw), 3)
         return dst, [d[0] for d in ddesc]
 
@@ -759,6 +888,15 @@ class ImagePipeline:
         dev = self._dev()
         B = len(planned)
         hw = [tuple(s.get("resize_hw", s["img"].shape[:2])) for s in planned]
+        # RandomCrop: the batch's images are windows (Hr, Wr, y0, x0) of the virtual resized images; hw is the crop size
+        # from here on (a sample of the batch without a window is the window that holds its whole image)
+        win = None
+        if any("crop_window" in s for s in planned):
+            win = [(*hw[i], *s["crop_window"][:2]) if "crop_window" in s else (*hw[i], 0, 0) for i, s in enumerate(planned)]
+            hw = [tuple(s["crop_window"][2:]) if "crop_window" in s else hw[i] for i, s in enumerate(planned)]
+            for (Hr, Wr, y0, x0), (h, w) in zip(win, hw):
+                if not (0 <= y0 <= Hr - h and 0 <= x0 <= Wr - w and h > 0 and w > 0):
+                    raise ValueError(f"crop window {h} x {w} at ({y0}, {x0}) of a resized image of {Hr} x {Wr}")
         for h, w in hw:
             if h > K.AUG_MAX_W or w > K.AUG_MAX_W:
                 raise ValueError(f"image of {h} x {w}: the augmentation kernels take sides up to {K.AUG_MAX_W}")
@@ -772,15 +910,19 @@ class ImagePipeline:
             # sample_cache='device': cached files are gathered into that buffer, new ones leave it for the arena
             src, soffs = (self._cached_packed(planned, with_bg, sources, dev, align=4 if self.mix else 1)
                           if self.sample_cache is not None else self._decode_packed(sources, dev, align=4 if self.mix else 1))
-            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, src=(src, soffs[:B]))
+            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, src=(src, soffs[:B]), windows=win)
             bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev, src=(src, soffs[B:]))
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         else:
-            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1)
+            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, windows=win)
             bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev)
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         bg_off = dict(zip(with_bg, bg_offs))
-        masks, flipped_masks = self._masks(planned, hw, dev)
+        # Pad(size=): the assigner sees the padded sample -- its masks / maps zero-padded to the fixed size, its points those
+        # of that size, which are the head's for every sample of the batch whatever scale was drawn (with Pad(size_divisor=)
+        # the points follow img_shape as in the reference)
+        ahw = [tuple(s["pad_shape"][:2]) if s.get("pad_fixed_size") is not None else hw[i] for i, s in enumerate(planned)]
+        masks, flipped_masks = self._masks(planned, hw, dev, win, ahw)
 
         P = np.zeros((B, K.AUG_PARAM_INTS), np.int32)
         for i, s in enumerate(planned):
@@ -799,6 +941,8 @@ class ImagePipeline:
                 if m is not None and m.shape[0]:
                     addr = m.data_ptr()
                     P[i, 6], P[i, 7] = np.array([addr & 0xFFFFFFFF, addr >> 32], np.uint32).view(np.int32)
+                    if tuple(m.shape[1:]) != hw[i]:        # (the assigner's padded masks: the mask pitch word)
+                        P[i, 15] = m.shape[1] << 16 | m.shape[2]
             if "aug_blur" in s:
                 fl |= F_BLUR
                 r, ww, fw = blur_params(s["aug_blur"])
@@ -842,9 +986,9 @@ class ImagePipeline:
         if self.assigner is not None:
             p2g, pw = [None] * B, [None] * B
             # (t1 / lsum / params: what augment_finish has just read -- the augmented u8 image exists nowhere else)
-            maps = flipped_masks if self.mask_free is None else self._distance_maps(planned, hw, t1, lsum, params, dev)
-            for shape in sorted(set(hw)):
-                idx = [i for i in range(B) if hw[i] == shape]
+            maps = flipped_masks if self.mask_free is None else self._distance_maps(planned, ahw, t1, lsum, params, dev)
+            for shape in sorted(set(ahw)):
+                idx = [i for i in range(B) if ahw[i] == shape]
                 a, b = self.assigner.assign_batch([planned[i]["gt_bboxes"] for i in idx], [maps[i] for i in idx], shape,
                                                   rngs=[planned[i]["_nprnd"] for i in idx], device=dev)
                 for j, i in enumerate(idx):
@@ -895,7 +1039,8 @@ class ImagePipeline:
     def _distance_maps(self, planned, hw, img, lsum, params, dev):
         """The mask-free sampler's maps of a batch, f32 [G_i, h, w] per sample: every box's padded crop cut from the
         augmented image (one launch), the GDT / MBD chain over all crops (ops.*_box2distance.packed_maps), one paste launch
-        per image size.  All descriptors come from the planned box geometry; nothing is read back from the device."""
+        per image size.  All descriptors come from the planned box geometry; nothing is read back from the device.
+        hw: the size the maps are pasted into (the image's, or the fixed pad size: zeros outside the image)"""
         from ..ops import _Packed, _upload
         boxes = [(i, k) for i, s in enumerate(planned) for k in range(len(s["_crop_plan"][0].corners))]
         maps = [torch.zeros(0, *hw[i], dtype=torch.float32, device=dev) for i in range(len(planned))]
@@ -963,10 +1108,17 @@ class ImagePipeline:
             P[i, 3] = fl
         return P
 
-    def _masks(self, planned, hw, dev):
+    def _masks(self, planned, hw, dev, win=None, ahw=None):
         """normalised (mask / max), nearest-resized instance masks per sample (for the merge) and the same after the
-        sample's flip (for the assigner): one normalise + resize pass per group of equal sizes, one flip pass per group"""
+        sample's flip (for the assigner): one normalise + resize pass per group of equal sizes, one flip pass per group.
+        win: per sample (Hr, Wr, y0, x0), hw then being the size of the sample's window of its Hr x Wr resized masks; ahw:
+        per sample the size of the assigner's masks where it is not hw (Pad(size=)) -- either makes this _window_masks"""
         masks, flipped = [None] * len(planned), [None] * len(planned)
+        if win is None and ahw is not None and list(ahw) != list(hw):
+            win = [(*hw[i], 0, 0) for i in range(len(planned))]
+        if win is not None:
+            self._window_masks(planned, hw, dev, win, hw if ahw is None else ahw, masks, flipped)
+            return masks, flipped
         groups = {}
         for i, s in enumerate(planned):
             if "gt_masks" in s:
@@ -1019,6 +1171,68 @@ class ImagePipeline:
                 flipped[i] = out[o:o + c]
                 masks[i] = plain[o:o + c] if planned[i].get("flip") else flipped[i]
                 o += c
+
+    def _window_masks(self, planned, hw, dev, win, ahw, masks, flipped):
+        """_masks for a batch whose samples are windows of their virtual resized images.  The second list (the assigner's
+        masks: flipped with the sample, zero-padded to ahw) comes straight from the source masks, per group of equal source
+        and assigner sizes -- one launch whatever scales and window sizes the samples drew: radet_mask_max +
+        radet_mask_transform_window with one row per mask for bitmaps, radet_rle_masks_window for run lists.  The first
+        list (the merge's masks: unflipped) is filled for the samples that carry a background only, with the same launch's
+        output for an unflipped sample; when a merged sample is flipped, bitmaps take a second pass over the stack and the
+        run-list launch writes both orientations.  These masks have the assigner's size: for a sample smaller than the
+        pad the merge reads their top-left corner (the mask pitch word of its params row).  The launches of a batch do not
+        depend on the scales and window sizes its samples drew.  Nothing waits for the device."""
+        groups, rle_groups = {}, {}
+        for i, s in enumerate(planned):
+            if "gt_masks_rle" in s and "gt_masks" in s:
+                raise ValueError("a sample carries both gt_masks and gt_masks_rle")
+            if "gt_masks" in s:
+                groups.setdefault((tuple(s["gt_masks"].shape[1:]), ahw[i]), []).append(i)
+            elif "gt_masks_rle" in s:
+                rle_groups.setdefault((tuple(s["gt_masks_rle"][1]), ahw[i]), []).append(i)
+
+        def rows_of(idx, counts, with_flip):
+            rows = np.array([[*win[i], *hw[i], with_flip and bool(planned[i].get("flip"))] for i in idx], np.int32)
+            return np.repeat(rows.reshape(-1, K.MASK_WIN_INTS), counts, axis=0)
+
+        def hand_out(idx, counts, out, plain):
+            o = 0
+            for i, c in zip(idx, counts):
+                flipped[i] = out[o:o + c]
+                if "background" in planned[i]:
+                    masks[i] = plain[o:o + c] if planned[i].get("flip") and c else out[o:o + c]
+                o += c
+
+        for (src_hw, out_hw), idx in groups.items():
+            counts = [planned[i]["gt_masks"].shape[0] for i in idx]
+            G = sum(counts)
+            if not G:
+                hand_out(idx, counts, torch.zeros(0, *out_hw, dtype=torch.uint8, device=dev), None)
+                continue
+            both = any(planned[i].get("flip") and "background" in planned[i] for i in idx)
+            src = torch.from_numpy(np.concatenate([planned[i]["gt_masks"] for i in idx])).to(dev)
+            rows = torch.from_numpy(np.concatenate([rows_of(idx, counts, True)] + ([rows_of(idx, counts, False)] if both else []))).to(dev)
+            mx = K.mask_max(src)
+            out = K.mask_transform_window(src, rows[:G], out_hw, norm_max=mx)
+            plain = K.mask_transform_window(src, rows[G:], out_hw, norm_max=mx) if both else None
+            hand_out(idx, counts, out, plain)
+        for (src_hw, out_hw), idx in rle_groups.items():
+            per_mask = [m for i in idx for m in planned[i]["gt_masks_rle"][0]]
+            counts = [len(planned[i]["gt_masks_rle"][0]) for i in idx]
+            if not per_mask:
+                hand_out(idx, counts, torch.zeros(0, *out_hw, dtype=torch.uint8, device=dev), None)
+                continue
+            flips = np.repeat([bool(planned[i].get("flip")) for i in idx], counts)
+            both = any(planned[i].get("flip") and "background" in planned[i] for i in idx)
+            ends, prows, mrows = rle.pack_runs(per_mask, *src_hw, flips)
+            packed = torch.from_numpy(np.concatenate([ends.view(np.int32), prows.reshape(-1), mrows.reshape(-1),
+                                                      rows_of(idx, counts, False).reshape(-1)]))
+            packed = packed.pin_memory().to(dev, non_blocking=True)
+            a, b, c = ends.size, ends.size + prows.size, ends.size + prows.size + mrows.size
+            res = K.rle_masks_window(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:c].view(-1, K.RLE_MASK_INTS),
+                                     packed[c:].view(-1, K.MASK_WIN_INTS), out_hw, with_plain=both)
+            out, plain = res if both else (res, None)
+            hand_out(idx, counts, out, plain)
 
     def _collect(self, planned, out, p2g, pw, collate):
         samples = []

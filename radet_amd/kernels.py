@@ -1516,6 +1516,38 @@ def mask_transform(src, out_hw=None, resized_hw=None, flip=None, pad_val=0, norm
     return dst
 
 
+MASK_WIN_INTS = 7                         # include/radet_hip.h
+
+
+def mask_max(src):
+    """src: u8[G,Hs,Ws] device tensor (G > 0) -> i32[G]: each mask's maximum, what normalize=True divides by"""
+    G, Hs, Ws = src.shape
+    mx = torch.empty(G, dtype=torch.int32, device=src.device)
+    _lib.call("radet_mask_max", _ptr(src), _ptr(mx), G, C.c_size_t(Hs * Ws), _stream())
+    return mx
+
+
+def mask_transform_window(src, win_desc, out_hw, pad_val=0, normalize=False, norm_max=None):
+    """src: u8[G,Hs,Ws] device tensor -> u8[G,Hd,Wd]: per mask the window of its virtual nearest-resized mask that its
+    win_desc row names (i32 [G, MASK_WIN_INTS] on the device: {Hr, Wr, y0, x0, h, w, flip}), flipped inside the window,
+    padded to out_hw -- mask_transform(resized_hw=(Hr, Wr)) sliced, then flipped, one pass.  norm_max: the masks' maxima
+    from mask_max (several passes over one stack share them) instead of normalize=True"""
+    G, Hs, Ws = src.shape
+    Hd, Wd = out_hw
+    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=src.device)
+    if G == 0:
+        return dst
+    assert tuple(win_desc.shape) == (G, MASK_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
+    mx = norm_max
+    if mx is not None:
+        assert tuple(mx.shape) == (G,) and mx.dtype == torch.int32 and mx.is_contiguous()
+    elif normalize:
+        mx = mask_max(src)
+    _lib.call("radet_mask_transform_window", _ptr(src), _ptr(dst), _ptr(mx), _ptr(win_desc), G, Hs, Ws, Hd, Wd, int(pad_val),
+              _stream())
+    return dst
+
+
 RLE_MASK_INTS, RLE_PART_INTS = 5, 2       # include/radet_hip.h
 RLE_MAX_W = 8192
 
@@ -1534,6 +1566,20 @@ def rle_masks(run_ends, part_desc, mask_desc, out_hw, resized_hw=None, pad_val=0
     if G:
         _lib.call("radet_rle_masks", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc), G,
                   _ptr(dst), _ptr(plain), Hr, Wr, Hd, Wd, int(pad_val), _stream())
+    return (dst, plain) if with_plain else dst
+
+
+def rle_masks_window(run_ends, part_desc, mask_desc, win_desc, out_hw, pad_val=0, with_plain=False):
+    """rle_masks for per-mask windows of the virtual resized masks (win_desc as for mask_transform_window; the flip is
+    mask_desc's, applied inside the window)"""
+    G = mask_desc.shape[0]
+    Hd, Wd = out_hw
+    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=mask_desc.device)
+    plain = torch.empty_like(dst) if with_plain else None
+    if G:
+        assert tuple(win_desc.shape) == (G, MASK_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
+        _lib.call("radet_rle_masks_window", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc),
+                  _ptr(win_desc), G, _ptr(dst), _ptr(plain), Hd, Wd, int(pad_val), _stream())
     return (dst, plain) if with_plain else dst
 
 
@@ -1585,6 +1631,15 @@ def gauss9_kernel():
 
 def resize_linear_u8(src, sdesc, dst, ddesc, n, max_dst_px, channels=3):
     _lib.call("radet_resize_linear_u8", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(ddesc), n, max_dst_px, channels, _stream())
+
+
+RESIZE_WIN_DESC_INTS = 7                  # include/radet_hip.h
+
+
+def resize_linear_u8_window(src, sdesc, dst, wdesc, n, max_dst_px, channels=3):
+    """resize_linear_u8 writing only a window of each virtual resized image: wdesc i32 [n, RESIZE_WIN_DESC_INTS] on the
+    device, {packed pixel offset, window h, w, resized Hr, Wr, window origin y0, x0}"""
+    _lib.call("radet_resize_linear_u8_window", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(wdesc), n, max_dst_px, channels, _stream())
 
 
 def resize_linear_f(src, sdesc, dst, ddesc, n, max_dst_px):

@@ -22,6 +22,11 @@
                                                                    # PNG masks + host decoding and run lists + device decoding
                                                                    # (timeout -k 10 900 python tools/bench_pipeline.py --part cache
                                                                    #  --steps 30 --out profiles/bench_pipeline_cache.json)
+    python tools/bench_pipeline.py --part jitter [--iters 20]       # Resize(ratio_range) + RandomCrop + Pad(size) against the
+                                                                   # fixed-scale pipeline on the same files, output 480 x 640
+                                                                   # both: the device part of one bs-16 batch, alternating rounds
+                                                                   # (timeout -k 10 400 python tools/bench_pipeline.py --part
+                                                                   #  jitter --out profiles/bench_jitter.json)
 `--pipeline mix` runs the mixpbr train pipeline instead (RandomHSV / RandomNoise / RandomSmooth in place of CosyPoseAug,
 the training set a MixDataset of the tree twice, ratios 2 and 1).
 Each part prints one JSON line (and writes it to --out if given)."""
@@ -690,6 +695,69 @@ def part_cache(args, root):
     return res
 
 
+def part_jitter(args, root):
+    """bs 16, 640 x 480 frames, 6 objects per image.  The device part (ImagePipeline.run) of one planned batch per variant:
+    `fixed` = the r50_ycbv_pbr train pipeline (output 480 x 640), `jitter` = the same with Resize(ratio_range=(0.6, 1.6)) +
+    RandomCrop((480, 640)) + Pad(size=(480, 640)) (configs/base/datasets/bop_detection_jitter.py: samples drawn below 1 are
+    smaller than the crop), `jitter_up` = ratio_range (1.0, 1.6): every sample is a 480 x 640 window of a larger virtual
+    image, the same output pixels as `fixed`.  The variants alternate within each round; per call a device event pair and a
+    host clock around the call and a synchronise.  Also the entry points each variant calls."""
+    import torch
+    from radet_amd import _lib
+    from radet_amd.datasets import build_dataset
+    from radet_amd.datasets.loader import sample_generators
+    tree = write_tree(root, n_frames=16, objects=(6, 6), seed=0)
+    train, _ = pipelines(tree["background_dir"])
+
+    def jitter(ratio_range):
+        p = list(train)
+        p[2] = dict(type="Resize", img_scale=(640, 480), ratio_range=ratio_range, keep_ratio=True)
+        p.insert(3, dict(type="RandomCrop", crop_size=(480, 640)))
+        return [dict(type="Pad", size=(480, 640)) if t["type"] == "Pad" else t for t in p]
+    sub = dict(type="BOPDataset", ann_file=tree["ann_file"], img_prefix=tree["img_prefix"], seg_prefix=tree["seg_prefix"])
+    ds = dict(fixed=build_dataset(dict(sub, pipeline=train)), jitter=build_dataset(dict(sub, pipeline=jitter((0.6, 1.6)))),
+              jitter_up=build_dataset(dict(sub, pipeline=jitter((1.0, 1.6)))))
+    planned = {k: [d.plan_sample(i, *sample_generators(0, 0, i)) for i in range(16)] for k, d in ds.items()}
+    res = dict(part="jitter", batch=16, iters=args.iters, rounds=args.rounds, device=torch.cuda.get_device_name(0),
+               clocks="default governor, not pinned; medians over alternating rounds")
+    res["samples"] = {k: dict(windowed=sum(tuple(s.get("crop_window", (0, 0, *s["resize_hw"]))[2:]) != tuple(s["resize_hw"]) for s in v),
+                              resized_px=int(sum(s["resize_hw"][0] * s["resize_hw"][1] for s in v)),
+                              output_px=int(sum(s["img_shape"][0] * s["img_shape"][1] for s in v)),
+                              flips=sum(bool(s["flip"]) for s in v), backgrounds=sum("background" in s for s in v))
+                      for k, v in planned.items()}
+    calls = {}
+    for k, d in ds.items():
+        seen, call = [], _lib.call
+        _lib.call = lambda name, *a: seen.append(name) or call(name, *a)
+        try:
+            out = d.pipeline.run(_fresh(planned[k]), collate=True)
+        finally:
+            _lib.call = call
+        assert tuple(out["img"].shape) == (16, 3, 480, 640)
+        calls[k] = seen
+    res["entry_points"] = calls
+    for k, d in ds.items():                                    # warm-up of every variant's shapes
+        for _ in range(args.warmup):
+            d.pipeline.run(_fresh(planned[k]), collate=True)
+    wall, evt = {k: [] for k in ds}, {k: [] for k in ds}
+    for _ in range(args.rounds):
+        for k, d in ds.items():
+            for _ in range(args.iters):
+                batch = _fresh(planned[k])
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record()
+                d.pipeline.run(batch, collate=True)
+                e1.record()
+                torch.cuda.synchronize()
+                wall[k].append((time.perf_counter() - t0) * 1e3)
+                evt[k].append(e0.elapsed_time(e1))
+    res["run_ms"] = {k: dict(wall=_scatter(wall[k]), event=_scatter(evt[k])) for k in ds}
+    res["median_event_ms"] = {k: float(np.median(evt[k])) for k in ds}
+    return res
+
+
 def _fresh(planned):
     """the planned samples with copies of their RandomStates (the assigner advances them)"""
     import copy
@@ -698,7 +766,7 @@ def _fresh(planned):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree", "rle", "jpeg", "cache"), required=True)
+    ap.add_argument("--part", choices=("kernels", "decode", "train", "maskfree", "rle", "jpeg", "cache", "jitter"), required=True)
     ap.add_argument("--pipeline", choices=("pbr", "mix"), default="pbr")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=60)
@@ -708,7 +776,8 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as root:
-        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree, rle=part_rle, jpeg=part_jpeg, cache=part_cache)[args.part](args, root)
+        res = dict(kernels=part_kernels, decode=part_decode, train=part_train, maskfree=part_maskfree, rle=part_rle, jpeg=part_jpeg, cache=part_cache,
+                   jitter=part_jitter)[args.part](args, root)
     line = json.dumps(res)
     print(line)
     if args.out:
