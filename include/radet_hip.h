@@ -468,6 +468,19 @@ int radet_resize_linear_f(const void* src, const int* src_desc, void* dst, const
 #define RESIZE_WIN_DESC_INTS 7
 int radet_resize_linear_u8_window(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* win_desc, int ncrop,
                                   int max_dst_px, int channels, void* stream);
+/* radet_resize_linear_u8 for Expand / MinIoURandomCrop followed by Resize: the image that is resized is a window of the
+ * source, given in the source's own coordinates; it may overhang the source or miss it, and what lies outside reads as a
+ * fill colour (Expand's canvas, which is never made).  src_desc as above; win_desc (device) = ncrop rows of
+ * RESIZE_SRC_WIN_DESC_INTS ints {packed pixel offset of the output, output Hr, Wr, window origin wy0, wx0 (may be negative),
+ * window wh, ww, fill = c0 | c1 << 8 | c2 << 16 in the source's channel order (channels == 1: c0)}.  Taps and coefficients
+ * are those of a wh x ww image resized to Hr x Wr (the edge clamp is at the window's border); each tap is read at
+ * (wy0 + ty, wx0 + tx) of the source when that lies inside it and is the fill otherwise: bit for bit "paste the source on
+ * the filled canvas, slice the window, radet_resize_linear_u8".  Hr * Wr pixels are written at the offset.  A row with
+ * Hr, Wr, wh or ww <= 0, an empty source, or wy0 + wh / wx0 + ww beyond int is not written.  max_dst_px = the largest
+ * output's pixel count. */
+#define RESIZE_SRC_WIN_DESC_INTS 8
+int radet_resize_linear_u8_src_window(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* win_desc, int ncrop,
+                                      int max_dst_px, int channels, void* stream);
 int radet_gaussian_blur9_u8(const uint8_t* src, const int* desc, uint8_t* dst, float* tmp, const float* kernel5, int ncrop,
                             int max_px, void* stream);
 int radet_sobel_edge(const uint8_t* src, const int* desc, float* edge, uint8_t* gray_ws, uint32_t* max_ws, int ncrop,
@@ -491,6 +504,19 @@ int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint32_t* norm_
 #define MASK_WIN_INTS 7
 int radet_mask_transform_window(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, const int* win_desc, int G, int Hs,
                                 int Ws, int Hd, int Wd, int pad_val, void* stream);
+/* the source-window variants (Expand / MinIoURandomCrop followed by Resize): per mask a window of the SOURCE mask is what
+ * gets resized.  win_desc (device) i32 [G][MASK_SRC_WIN_INTS] = {resized Hr, Wr, window origin wy0, wx0 in the source's
+ * coordinates (may be negative), window wh, ww, flip}:
+ *      dst[g][y][x] = y < Hr && x < Wr ? norm(S(wy0 + nn(flip_y(y)), wx0 + nn(flip_x(x)))) : pad_val, nn over the wh x ww
+ *      window grid resized to Hr x Wr, S(sy, sx) = src[g][sy][sx] inside the Hs x Ws source and 0 outside it
+ *      (BitmapMasks.expand pads with zeros), norm_max still the maximum of the whole source mask: what np.pad / slicing the
+ *      source and radet_mask_transform give.  Hr <= Hd, Wr <= Wd; a row that breaks that, or with wh or ww <= 0, writes
+ *      pad_val only.  radet_rle_masks_src_window (declared below): the same window of what radet_rle_masks decodes -- a
+ *      sample outside the source is 0, not a lookup in a neighbouring column's runs; the flip is mask_desc's (the flip
+ *      word of win_desc is not read), dst_plain as there. */
+#define MASK_SRC_WIN_INTS 7
+int radet_mask_transform_src_window(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, const int* win_desc, int G, int Hs,
+                                    int Ws, int Hd, int Wd, int pad_val, void* stream);
 
 /* ---- the same masks from run-length annotations (COCO RLE / rasterised polygons, radet/datasets/pipelines/loading.py:313-380
  *      `_poly2mask`), without a bitmap on the host or in HBM: one launch per group of masks of one destination geometry.
@@ -509,6 +535,9 @@ int radet_rle_masks(const uint32_t* run_ends, int n_ends, const int* part_desc, 
                     uint8_t* dst, uint8_t* dst_plain, int Hr, int Wr, int Hd, int Wd, int pad_val, void* stream);
 int radet_rle_masks_window(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc,
                            const int* win_desc, int G, uint8_t* dst, uint8_t* dst_plain, int Hd, int Wd, int pad_val, void* stream);
+int radet_rle_masks_src_window(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc,
+                               const int* win_desc, int G, uint8_t* dst, uint8_t* dst_plain, int Hd, int Wd, int pad_val,
+                               void* stream);
 
 /* ---- baseline JPEG files decoded on the device (csrc/jpeg.hip, csrc/jpeg_index.c, radet_amd/core/jpeg.py): what libjpeg's
  *      default decompressor gives for them byte for byte (slow-integer IDCT, fancy upsampling, fixed-point YCbCr -> RGB),

@@ -103,6 +103,7 @@ SIGNATURES = {
     "radet_assign_points_f": (_i, [_p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
     "radet_resize_linear_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_resize_linear_u8_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "radet_resize_linear_u8_src_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_resize_linear_f": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_gaussian_blur9_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "radet_sobel_edge": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
@@ -125,8 +126,10 @@ SIGNATURES = {
     "radet_mask_max": (_i, [_p, _p, _i, _sz, _p]),
     "radet_mask_transform": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "radet_mask_transform_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "radet_mask_transform_src_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "radet_rle_masks": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "radet_rle_masks_window": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p]),
+    "radet_rle_masks_src_window": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p]),
     "radet_jpeg_index": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _i]),
     "radet_jpeg_decode": (_i, [_p, _p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_augment_merge_hblur": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),

@@ -83,6 +83,64 @@ __global__ __launch_bounds__(256) void mask_transform_kernel(const uint8_t* __re
     }
 }
 
+// A source-window row (include/radet_hip.h MASK_SRC_WIN_INTS) of mask g: {Hr, Wr, wy0, wx0, wh, ww, flip}.  The mask that
+// is resized to Hr x Wr is the wh x ww window at (wy0, wx0) of the source mask in the source's coordinates (Expand /
+// MinIoURandomCrop in front of Resize); the window may overhang the source, what lies outside is 0 (BitmapMasks.expand
+// pads with zeros).  A row without a window, or whose Hr x Wr does not fit the destination, is empty.
+struct MaskSrcWin { int Hr, Wr, wy0, wx0, wh, ww, flip; };
+
+__device__ __forceinline__ MaskSrcWin load_mask_src_win(const int* __restrict__ win, int g, int Hd, int Wd) {
+    const int* d = win + (size_t)g * MASK_SRC_WIN_INTS;
+    MaskSrcWin m = {d[0], d[1], d[2], d[3], d[4], d[5], d[6]};
+    if (m.Hr <= 0 || m.Wr <= 0 || m.Hr > Hd || m.Wr > Wd || m.wh <= 0 || m.ww <= 0 || (long long)m.wy0 + m.wh > 0x7FFFFFFFLL ||
+        (long long)m.wx0 + m.ww > 0x7FFFFFFFLL) {
+        m.Hr = m.Wr = 0;
+        m.wy0 = m.wx0 = 0;
+        m.wh = m.ww = 1;
+    }
+    return m;
+}
+
+// mask_transform_kernel over source windows: nearest sampling over the wh x ww window grid, each sample fetched at
+// (wy0 + sy, wx0 + sx) of the source mask or 0 outside it; norm_max stays the maximum of the whole source mask (the
+// reference normalises at load time, before Expand); flip and pad as there.
+__global__ __launch_bounds__(256) void mask_transform_src_window_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                                        const unsigned* __restrict__ norm_max,
+                                                                        const int* __restrict__ win, int Hs, int Ws, int Hd, int Wd,
+                                                                        int pad_val) {
+    const int g = blockIdx.z, y = blockIdx.y;
+    const int x0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (x0 >= Wd) return;
+    const MaskSrcWin m = load_mask_src_win(win, g, Hd, Wd);
+    const int Hr = m.Hr, Wr = m.Wr, flip = m.flip & 3;
+    // OpenCV computes inv_scale = dsize / ssize and then 1. / inv_scale (not ssize / dsize)
+    const double ify = Hr > 0 ? 1.0 / ((double)Hr / (double)m.wh) : 0.0, ifx = Wr > 0 ? 1.0 / ((double)Wr / (double)m.ww) : 0.0;
+    const uint8_t* sp = src + (size_t)g * Hs * Ws;
+    const unsigned mx = norm_max ? norm_max[g] : 0u;
+    unsigned out[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int x = x0 + j;
+        unsigned v = (unsigned)pad_val & 0xFFu;
+        if (y < Hr && x < Wr) {
+            const int yr = (flip & 2) ? Hr - 1 - y : y;       // flip acts on the resized image
+            const int xr = (flip & 1) ? Wr - 1 - x : x;
+            const int sy = m.wy0 + nn_src(yr, ify, m.wh), sx = m.wx0 + nn_src(xr, ifx, m.ww);
+            v = ((unsigned)sy < (unsigned)Hs && (unsigned)sx < (unsigned)Ws) ? sp[(size_t)sy * Ws + sx] : 0u;
+            if (norm_max) v = (mx != 0u && v == mx) ? 1u : 0u;
+        }
+        out[j] = v;
+    }
+    uint8_t* dp = dst + ((size_t)g * Hd + y) * Wd + x0;
+    if ((Wd & 3) == 0) {
+        *reinterpret_cast<unsigned*>(dp) = out[0] | (out[1] << 8) | (out[2] << 16) | (out[3] << 24);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (x0 + j < Wd) dp[j] = (uint8_t)out[j];
+    }
+}
+
 // Number of run ends <= p among ends[lo, n) (ends ascending): the index of the run that holds position p.
 __device__ __forceinline__ int rle_run_of(const uint32_t* __restrict__ ends, int lo, int n, uint32_t p) {
     int hi = n;
@@ -183,6 +241,90 @@ __global__ __launch_bounds__(256) void rle_masks_kernel(const uint32_t* __restri
     }
 }
 
+// rle_masks_kernel over source windows (`win` rows as for mask_transform_src_window_kernel; the flip is mask_desc's): a
+// sample that falls outside the source image decodes as 0 -- it is not looked up, so it cannot land in a neighbouring
+// column's run.  The positions of the samples that are looked up still ascend with x.
+__global__ __launch_bounds__(256) void rle_masks_src_window_kernel(const uint32_t* __restrict__ run_ends, int n_ends,
+                                                                   const int* __restrict__ part_desc, int n_parts,
+                                                                   const int* __restrict__ mask_desc, const int* __restrict__ win,
+                                                                   uint8_t* __restrict__ dst, uint8_t* __restrict__ dst_plain,
+                                                                   int Hd, int Wd, int pad_val) {
+    __shared__ unsigned row[RLE_MAX_W / 4 + 1];
+    const int g = blockIdx.y, y = blockIdx.x;
+    const int* md = mask_desc + (size_t)g * RLE_MASK_INTS;
+    const int first = md[0], Hs = md[2], Ws = md[3], flip = md[4] & 1;
+    int np = md[1];
+    if (first < 0 || np < 0 || first > n_parts - np || Hs <= 0 || Ws <= 0) np = 0;         // (a row that points outside the part table: no parts)
+    const MaskSrcWin m = load_mask_src_win(win, g, Hd, Wd);
+    const int Hr = m.Hr, Wr = m.Wr;
+    const double ify = Hr > 0 ? 1.0 / ((double)Hr / (double)m.wh) : 0.0, ifx = Wr > 0 ? 1.0 / ((double)Wr / (double)m.ww) : 0.0;
+    const unsigned pad = (unsigned)pad_val & 0xFFu;
+    const int nwords = (Wd + 3) >> 2;
+    const bool inside = y < Hr;
+    const int sy = inside ? m.wy0 + nn_src(y, ify, m.wh) : -1;
+    const bool row_in = np > 0 && (unsigned)sy < (unsigned)Hs;
+    for (int wd = threadIdx.x; wd < nwords; wd += blockDim.x) {
+        const int x0 = wd * 4;
+        unsigned out[4] = {pad, pad, pad, pad};
+        if (inside && x0 < Wr) {
+            uint32_t pos[4];
+            bool ok[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                out[j] = x0 + j < Wr ? 0u : pad;
+                const int sx = m.wx0 + nn_src(min(x0 + j, Wr - 1), ifx, m.ww);
+                ok[j] = row_in && x0 + j < Wr && (unsigned)sx < (unsigned)Ws;
+                pos[j] = ok[j] ? (uint32_t)sx * (uint32_t)Hs + (uint32_t)sy : 0u;
+            }
+            for (int k = 0; k < np; ++k) {
+                const int off = part_desc[(size_t)(first + k) * RLE_PART_INTS], n = part_desc[(size_t)(first + k) * RLE_PART_INTS + 1];
+                if (off < 0 || n <= 0 || off > n_ends - n) continue;
+                const uint32_t* e = run_ends + off;
+                int r = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!ok[j]) continue;
+                    if (r < n && e[r] <= pos[j]) r = rle_run_of(e, r + 1, n, pos[j]);
+                    out[j] |= (unsigned)r & 1u;
+                }
+            }
+        }
+        row[wd] = out[0] | (out[1] << 8) | (out[2] << 16) | (out[3] << 24);
+    }
+    __syncthreads();
+    const uint8_t* rb = reinterpret_cast<const uint8_t*>(row);
+    uint8_t* dp = dst + ((size_t)g * Hd + y) * Wd;
+    uint8_t* pp = (dst_plain && flip) ? dst_plain + ((size_t)g * Hd + y) * Wd : nullptr;
+    for (int wd = threadIdx.x; wd < nwords; wd += blockDim.x) {
+        const int x0 = wd * 4;
+        unsigned v = row[wd];
+        if (pp) {
+            if ((Wd & 3) == 0) {
+                *reinterpret_cast<unsigned*>(pp + x0) = v;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (x0 + j < Wd) pp[x0 + j] = (uint8_t)(v >> (8 * j));
+            }
+        }
+        if (flip && inside) {                                        // flip acts on the resized image; the pad stays right
+            v = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = x0 + j;
+                v |= (unsigned)(x < Wr ? rb[Wr - 1 - x] : (uint8_t)pad) << (8 * j);
+            }
+        }
+        if ((Wd & 3) == 0) {
+            *reinterpret_cast<unsigned*>(dp + x0) = v;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < Wd) dp[x0 + j] = (uint8_t)(v >> (8 * j));
+        }
+    }
+}
+
 extern "C" int radet_mask_max(const uint8_t* masks, uint32_t* maxes, int G, size_t hw, void* stream) {
     if (G <= 0 || hw == 0) return RADET_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -232,5 +374,24 @@ extern "C" int radet_rle_masks_window(const uint32_t* run_ends, int n_ends, cons
     const int threads = nwords >= 256 ? 256 : ((nwords + 63) / 64) * 64;
     hipLaunchKernelGGL(rle_masks_kernel<true>, dim3(Hd, G), dim3(threads), 0, (hipStream_t)stream, run_ends, n_ends, part_desc,
                        n_parts, mask_desc, win_desc, dst, dst_plain, 0, 0, Hd, Wd, pad_val);
+    return radet_check_launch();
+}
+
+extern "C" int radet_mask_transform_src_window(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, const int* win_desc, int G,
+                                               int Hs, int Ws, int Hd, int Wd, int pad_val, void* stream) {
+    if (G <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0 || Hd > 65535 || !win_desc) return RADET_ERR_ARG;
+    hipLaunchKernelGGL(mask_transform_src_window_kernel, dim3((Wd + 1023) / 1024, Hd, G), dim3(256), 0, (hipStream_t)stream, src, dst,
+                       norm_max, win_desc, Hs, Ws, Hd, Wd, pad_val);
+    return radet_check_launch();
+}
+
+extern "C" int radet_rle_masks_src_window(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts,
+                                          const int* mask_desc, const int* win_desc, int G, uint8_t* dst, uint8_t* dst_plain, int Hd,
+                                          int Wd, int pad_val, void* stream) {
+    if (G <= 0 || G > 65535 || n_ends < 0 || n_parts < 0 || Hd <= 0 || Wd <= 0 || Wd > RLE_MAX_W || !win_desc) return RADET_ERR_ARG;
+    const int nwords = (Wd + 3) / 4;
+    const int threads = nwords >= 256 ? 256 : ((nwords + 63) / 64) * 64;
+    hipLaunchKernelGGL(rle_masks_src_window_kernel, dim3(Hd, G), dim3(threads), 0, (hipStream_t)stream, run_ends, n_ends, part_desc,
+                       n_parts, mask_desc, win_desc, dst, dst_plain, Hd, Wd, pad_val);
     return radet_check_launch();
 }

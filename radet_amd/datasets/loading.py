@@ -19,6 +19,10 @@ tensor): a test pipeline, whose run() is one pinned upload and one radet_preproc
 Scale jitter (Resize with random scales, RandomCrop, Pad(size=)): RandomCrop plans a window of the virtual resized image and
 run() computes that window only -- radet_resize_linear_u8_window, radet_mask_transform_window, radet_rle_masks_window in
 the place of their plain counterparts -- so a batch keeps one tensor shape at the cost of the crop's pixels.
+Zoom (Expand, MinIoURandomCrop, in front of Resize): the mirror image -- the stages plan a window of the virtual SOURCE
+canvas in image coordinates, which may overhang the image (s["src_window"]); run() resizes that window straight from the
+image, the canvas fill where it overhangs (radet_resize_linear_u8_src_window, radet_mask_transform_src_window,
+radet_rle_masks_src_window in the place of their plain counterparts); no canvas is ever made.
 Options the RADet configs do not use raise NotImplementedError."""
 import glob
 import math
@@ -40,9 +44,10 @@ osp = os.path
 DEFAULT_META_KEYS = ("filename", "ori_filename", "ori_shape", "img_shape", "pad_shape", "scale_factor", "flip",
                      "flip_direction", "img_norm_cfg")
 # stage order of the device part (a pipeline lists a subsequence of it; MultiScaleFlipAug's transforms sit in its place)
-_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Resize", "RandomCrop", "RandomBackground", "CosyPoseAug", "RandomHSV",
+_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Expand", "MinIoURandomCrop", "Resize", "RandomCrop", "RandomBackground", "CosyPoseAug", "RandomHSV",
           "RandomNoise", "RandomSmooth", "RandomFlip", "GenerateDistanceMap", "LabelAssignment", "Normalize", "Pad",
           "DefaultFormatBundle", "ImageToTensor", "Collect")
+_ZOOM = ("Expand", "MinIoURandomCrop")                       # the source-window stages
 _MIX = ("RandomHSV", "RandomNoise", "RandomSmooth")          # the mixpbr stages: aug_hsv_noise + aug_box
 _COSY_ORDER = ("PillowBlur", "PillowSharpness", "PillowContrast", "PillowBrightness", "PillowColor")
 # flags of a params row (include/radet_hip.h)
@@ -283,7 +288,8 @@ class Resize:
             if self.img_scale is None:
                 raise KeyError("Resize: no img_scale given and no 'scale' in the results")
             s["scale"], s["scale_idx"] = self._random_scale(nprnd)
-        h, w = s["img"].shape[:2]
+        # (after Expand / MinIoURandomCrop the image is the source window they planned)
+        h, w = s["src_window"][2:4] if "src_window" in s else s["img"].shape[:2]
         if self.keep_ratio:
             nw, nh = rescale_size((w, h), s["scale"])
         else:
@@ -298,6 +304,153 @@ class Resize:
                 b[:, 0::2] = np.clip(b[:, 0::2], 0, nw)
                 b[:, 1::2] = np.clip(b[:, 1::2], 0, nh)
             s[key] = b
+
+
+def _zoom_size(s):
+    """the size of the image that Expand / MinIoURandomCrop see: the source window planned so far, or the image as loaded"""
+    return tuple(s["src_window"][2:4]) if "src_window" in s else tuple(int(v) for v in s["img"].shape[:2])
+
+
+def _set_src_window(s, y0, x0, h, w, fill):
+    s["src_window"] = (int(y0), int(x0), int(h), int(w), tuple(fill))
+    # (without a Resize the window is the output; pad_shape follows it so that a pipeline without Pad collects the window)
+    s["resize_hw"] = (int(h), int(w))
+    s["pad_shape"] = (int(h), int(w), 3)
+
+
+@PIPELINES.register_module()
+class Expand:
+    """The reference's Expand (transforms.py:914-996), planned: zoom-out.  The image is placed at (left, top) of a canvas of
+    int(h * ratio) x int(w * ratio) filled with `mean`; draws on the sample's NumPy generator in the reference's order:
+    uniform(0, 1) against prob, the ratio, left, top.  Boxes shift by (left, top).  No pixel is touched and no canvas is
+    made: s["src_window"] = (y0, x0, h, w, fill_bgr), the canvas as a window of the image in image coordinates (its origin
+    is negative), which ImagePipeline.run samples directly.  img_shape stays what it was, as in the reference.  The draws
+    are kept in s["expand"] = (ratio, left, top)."""
+
+    def __init__(self, mean=(0, 0, 0), to_rgb=True, ratio_range=(1, 4), seg_ignore_label=None, prob=0.5):
+        if seg_ignore_label is not None:
+            _refuse("Expand(seg_ignore_label=...) (semantic segmentation maps)")
+        if len(mean) != 3:
+            raise ValueError(f"Expand: mean is one value per channel of a 3-channel image, got {mean!r}")
+        if len(ratio_range) != 2 or not 1 <= ratio_range[0] <= ratio_range[1]:
+            raise ValueError(f"Expand: ratio_range is (min_ratio, max_ratio) with 1 <= min_ratio <= max_ratio, got {ratio_range!r}")
+        self.to_rgb, self.ratio_range, self.prob = to_rgb, tuple(ratio_range), prob
+        # the image is BGR where Expand stands, so a mean given in RGB order is reversed
+        self.mean = tuple(mean)[::-1] if to_rgb else tuple(mean)
+        self.min_ratio, self.max_ratio = self.ratio_range
+        if not all(0 <= v < 256 for v in self.mean):
+            raise ValueError(f"Expand: mean {mean!r} does not fit the uint8 image")
+        # what NumPy's cast of the mean to the uint8 canvas stores: truncated, not rounded
+        self.fill = tuple(int(v) for v in np.asarray(self.mean, np.float64).astype(np.uint8))
+
+    def plan(self, s, rnd, nprnd):
+        if nprnd.uniform(0, 1) > self.prob:
+            return
+        if s.get("seg_fields"):
+            _refuse("Expand on a sample with seg_fields")
+        if "src_window" in s:
+            _refuse("Expand after another source-window stage")
+        h, w = _zoom_size(s)
+        ratio = nprnd.uniform(self.min_ratio, self.max_ratio)
+        left = int(nprnd.uniform(0, w * ratio - w))
+        top = int(nprnd.uniform(0, h * ratio - h))
+        for key in s.get("bbox_fields", []):
+            s[key] = s[key] + np.tile((left, top), 2).astype(s[key].dtype)
+        _set_src_window(s, -top, -left, int(h * ratio), int(w * ratio), self.fill)
+        s["expand"] = (ratio, left, top)
+
+
+def patch_overlaps(patch, boxes, eps=1e-6):
+    """bbox_overlaps (radet/core/evaluation/bbox_overlaps.py, mode 'iou') of one patch against k boxes, float32 [k]: the
+    areas, the intersection and the union in float32, the union raised to eps before the division.  (cocoeval.box_iou_matrix
+    computes in float64 and has no eps: not bit-equal, so it is not used here.)"""
+    p, b = np.asarray(patch).astype(np.float32), boxes.astype(np.float32).reshape(-1, 4)
+    if not len(b):
+        return np.zeros(0, np.float32)
+    area_p = (p[2] - p[0]) * (p[3] - p[1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    iw = np.maximum(np.minimum(p[2], b[:, 2]) - np.maximum(p[0], b[:, 0]), 0)
+    ih = np.maximum(np.minimum(p[3], b[:, 3]) - np.maximum(p[1], b[:, 1]), 0)
+    overlap = iw * ih
+    union = np.maximum(area_p + area_b - overlap, eps)
+    return (overlap / union).astype(np.float32)
+
+
+def _centres_in_patch(boxes, patch):
+    centre = (boxes[:, :2] + boxes[:, 2:]) / 2
+    return (centre[:, 0] > patch[0]) & (centre[:, 1] > patch[1]) & (centre[:, 0] < patch[2]) & (centre[:, 1] < patch[3])
+
+
+@PIPELINES.register_module()
+class MinIoURandomCrop:
+    """The reference's MinIoURandomCrop (transforms.py:1006-1136), planned: zoom-in.  Draws on the sample's NumPy generator
+    in the reference's order: choice over (1, *min_ious, 0) -- mode 1 leaves the sample as it is -- then up to 50 trials of
+    new_w, new_h, (aspect test), left, top, where left and top are uniform(w - new_w) and uniform(h - new_h) with NumPy's
+    high = 1.0, as the reference calls them; after 50 failed trials a new mode.  A patch passes when its IoU with every
+    box of every bbox field reaches the mode and the centre of at least one box lies inside it; per field the boxes whose
+    centre lies inside are kept, clipped to the patch and shifted, labels and masks with them.  No pixel is touched: the
+    patch goes into s["src_window"] (composed with Expand's, when that came first).  The draws are kept in s["crop_mode"]
+    and s["crop_patch"] = (x0, y0, x1, y1) in the coordinates of the image the stage saw."""
+    bbox2label = {"gt_bboxes": "gt_labels", "gt_bboxes_ignore": "gt_labels_ignore"}
+    bbox2mask = {"gt_bboxes": "gt_masks", "gt_bboxes_ignore": "gt_masks_ignore"}
+
+    def __init__(self, min_ious=(0.1, 0.3, 0.5, 0.7, 0.9), min_crop_size=0.3, bbox_clip_border=True):
+        self.min_ious, self.sample_mode = tuple(min_ious), (1, *min_ious, 0)
+        self.min_crop_size, self.bbox_clip_border = min_crop_size, bbox_clip_border
+
+    def plan(self, s, rnd, nprnd):
+        if s.get("seg_fields"):
+            _refuse("MinIoURandomCrop on a sample with seg_fields")
+        if "bbox_fields" not in s:
+            raise KeyError("MinIoURandomCrop needs bbox_fields (LoadAnnotations before it)")
+        all_boxes = np.concatenate([s[key] for key in s["bbox_fields"]], 0) if s["bbox_fields"] else np.zeros((0, 4), np.float32)
+        h, w = _zoom_size(s)
+        while True:
+            mode = nprnd.choice(self.sample_mode)
+            s["crop_mode"] = float(mode)
+            if mode == 1:
+                return
+            for _ in range(50):
+                new_w = nprnd.uniform(self.min_crop_size * w, w)
+                new_h = nprnd.uniform(self.min_crop_size * h, h)
+                if new_h / new_w < 0.5 or new_h / new_w > 2:
+                    continue
+                left = nprnd.uniform(w - new_w)                 # (one argument: low; high is NumPy's 1.0)
+                top = nprnd.uniform(h - new_h)
+                patch = np.array((int(left), int(top), int(left + new_w), int(top + new_h)))
+                if patch[2] == patch[0] or patch[3] == patch[1]:
+                    continue
+                overlaps = patch_overlaps(patch, all_boxes)
+                if len(overlaps) > 0 and overlaps.min() < mode:
+                    continue
+                if len(overlaps) > 0:
+                    if not _centres_in_patch(all_boxes, patch).any():
+                        continue
+                    for key in s["bbox_fields"]:
+                        b = s[key].copy()
+                        keep = _centres_in_patch(b, patch)
+                        b = b[keep]
+                        if self.bbox_clip_border:
+                            b[:, 2:] = b[:, 2:].clip(max=patch[2:])
+                            b[:, :2] = b[:, :2].clip(min=patch[:2])
+                        b -= np.tile(patch[:2], 2)
+                        s[key] = b
+                        label_key, mask_key = self.bbox2label.get(key), self.bbox2mask.get(key)
+                        if label_key in s:
+                            s[label_key] = s[label_key][keep]
+                        if mask_key in s:
+                            s[mask_key] = s[mask_key][keep.nonzero()[0]]
+                        if mask_key is not None and mask_key + "_rle" in s:
+                            parts, src_hw = s[mask_key + "_rle"]
+                            s[mask_key + "_rle"] = ([parts[k] for k in keep.nonzero()[0]], src_hw)
+                # (left <= max(w - new_w, 1), so int(left + new_w) <= w: the patch lies inside the image it is cut from)
+                px0, py0, px1, py1 = (int(v) for v in patch)
+                ph, pw = py1 - py0, px1 - px0
+                y0, x0, fill = (*s["src_window"][:2], s["src_window"][4]) if "src_window" in s else (0, 0, (0, 0, 0))
+                _set_src_window(s, y0 + py0, x0 + px0, ph, pw, fill)
+                s["crop_patch"] = (px0, py0, px1, py1)
+                s["img_shape"] = (ph, pw, 3)
+                return
 
 
 @PIPELINES.register_module()
@@ -702,6 +855,13 @@ class ImagePipeline:
             names[0] = "LoadImageFromFile"
             self._check_frame_pipeline(flat, sample_cache)
         pos = [(_ORDER.index(n) if n in _ORDER else -1) for n in names]
+        for n in (n for n in names if n in _ZOOM):
+            if "Resize" in names and names.index(n) > names.index("Resize"):
+                _refuse(f"{n} after Resize in {names} (the zoom stages plan a window of the source image: they stand before Resize)")
+            if "RandomCrop" in names:
+                _refuse(f"{n} together with RandomCrop (a source window and a window of the resized image in one pipeline)")
+            if any(isinstance(t, MultiScaleFlipAug) for t in flat):
+                _refuse(f"{n} in a MultiScaleFlipAug (test) pipeline")
         if "RandomCrop" in names and (-1 not in pos and pos != sorted(set(pos)) or any(isinstance(t, MultiScaleFlipAug) for t in flat)):
             _refuse(f"RandomCrop at position {names.index('RandomCrop')} of {names} (it stands directly after Resize: after "
                     f"{_ORDER[:_ORDER.index('RandomCrop')][-3:]}, before every stage of {_ORDER[_ORDER.index('RandomCrop') + 1:]}; "
@@ -855,11 +1015,13 @@ class ImagePipeline:
                 what = "; ".join(f"{p}: " + ", ".join(v for k, v in jpeg.ERRORS.items() if e & k) for p, e in bad)
                 raise ValueError(f"device JPEG decode failed (the pixels of that batch are undefined): {what}")
 
-    def _resize_packed(self, arrays, dst_hw, dev, align=1, src=None, windows=None):
+    def _resize_packed(self, arrays, dst_hw, dev, align=1, src=None, windows=None, src_windows=None):
         """u8 HWC images of any sizes -> one packed device buffer of the dst sizes (one resize launch); every image starts at
         a multiple of `align` pixels.  src: (packed device buffer, pixel offsets) when the images are there already.
         windows: per image (Hr, Wr, y0, x0) -- dst_hw is then the size of the window at (y0, x0) of the Hr x Wr resized
-        image, and only that window is computed (radet_resize_linear_u8_window)"""
+        image, and only that window is computed (radet_resize_linear_u8_window).  src_windows: per image (y0, x0, h, w,
+        fill) -- the window of the source, in its coordinates, that is resized to dst_hw; outside the source it reads as
+        the fill colour (radet_resize_linear_u8_src_window)"""
         src, src_offs = src if src is not None else (torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(dev), None)
         sdesc, ddesc, so, do = [], [], 0, 0
         for k, (a, (h, w)) in enumerate(zip(arrays, dst_hw)):
@@ -870,6 +1032,12 @@ class ImagePipeline:
             do += -(-h * w // align) * align
         dst = torch.empty(do * 3, dtype=torch.uint8, device=dev)
         n = len(arrays)
+        if src_windows is not None:
+            wdesc = [(*d, y0, x0, h, w, f[0] | f[1] << 8 | f[2] << 16) for d, (y0, x0, h, w, f) in zip(ddesc, src_windows)]
+            desc = torch.from_numpy(np.concatenate([np.array(sdesc, np.int32).reshape(-1), np.array(wdesc, np.int32).reshape(-1)])).to(dev)
+            K.resize_linear_u8_src_window(src, desc[:3 * n].view(n, 3), dst, desc[3 * n:].view(n, K.RESIZE_SRC_WIN_DESC_INTS), n,
+                                          max(h * w for h, w in dst_hw), 3)
+            return dst, [d[0] for d in ddesc]
         if windows is not None:
             # (one upload: the source rows, then the window rows)
             wdesc = [(*d, *win) for d, win in zip(ddesc, windows)]
@@ -897,6 +1065,16 @@ class ImagePipeline:
             for (Hr, Wr, y0, x0), (h, w) in zip(win, hw):
                 if not (0 <= y0 <= Hr - h and 0 <= x0 <= Wr - w and h > 0 and w > 0):
                     raise ValueError(f"crop window {h} x {w} at ({y0}, {x0}) of a resized image of {Hr} x {Wr}")
+        # Expand / MinIoURandomCrop: the batch's images are windows (y0, x0, h, w, fill) of their sources, in the source's
+        # coordinates, resized to hw (a sample of the batch without one is the window that is exactly its image)
+        swin = None
+        if any("src_window" in s for s in planned):
+            if win is not None:
+                raise ValueError("a batch with source windows (Expand / MinIoURandomCrop) and crop windows (RandomCrop)")
+            swin = [s["src_window"] if "src_window" in s else (0, 0, *s["img"].shape[:2], (0, 0, 0)) for s in planned]
+            for y0, x0, h, w, _ in swin:
+                if h <= 0 or w <= 0 or not all(-2 ** 30 < v < 2 ** 30 for v in (y0, x0, h, w)):
+                    raise ValueError(f"source window {h} x {w} at ({y0}, {x0})")
         for h, w in hw:
             if h > K.AUG_MAX_W or w > K.AUG_MAX_W:
                 raise ValueError(f"image of {h} x {w}: the augmentation kernels take sides up to {K.AUG_MAX_W}")
@@ -910,11 +1088,12 @@ class ImagePipeline:
             # sample_cache='device': cached files are gathered into that buffer, new ones leave it for the arena
             src, soffs = (self._cached_packed(planned, with_bg, sources, dev, align=4 if self.mix else 1)
                           if self.sample_cache is not None else self._decode_packed(sources, dev, align=4 if self.mix else 1))
-            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, src=(src, soffs[:B]), windows=win)
+            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, src=(src, soffs[:B]), windows=win,
+                                            src_windows=swin)
             bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev, src=(src, soffs[B:]))
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         else:
-            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, windows=win)
+            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, windows=win, src_windows=swin)
             bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev)
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         bg_off = dict(zip(with_bg, bg_offs))
@@ -922,7 +1101,7 @@ class ImagePipeline:
         # of that size, which are the head's for every sample of the batch whatever scale was drawn (with Pad(size_divisor=)
         # the points follow img_shape as in the reference)
         ahw = [tuple(s["pad_shape"][:2]) if s.get("pad_fixed_size") is not None else hw[i] for i, s in enumerate(planned)]
-        masks, flipped_masks = self._masks(planned, hw, dev, win, ahw)
+        masks, flipped_masks = self._masks(planned, hw, dev, win, ahw, swin)
 
         P = np.zeros((B, K.AUG_PARAM_INTS), np.int32)
         for i, s in enumerate(planned):
@@ -1108,12 +1287,16 @@ class ImagePipeline:
             P[i, 3] = fl
         return P
 
-    def _masks(self, planned, hw, dev, win=None, ahw=None):
+    def _masks(self, planned, hw, dev, win=None, ahw=None, swin=None):
         """normalised (mask / max), nearest-resized instance masks per sample (for the merge) and the same after the
         sample's flip (for the assigner): one normalise + resize pass per group of equal sizes, one flip pass per group.
         win: per sample (Hr, Wr, y0, x0), hw then being the size of the sample's window of its Hr x Wr resized masks; ahw:
-        per sample the size of the assigner's masks where it is not hw (Pad(size=)) -- either makes this _window_masks"""
+        per sample the size of the assigner's masks where it is not hw (Pad(size=)) -- either makes this _window_masks.
+        swin: per sample the source window (y0, x0, h, w, fill) that is resized to hw: _window_masks over source windows"""
         masks, flipped = [None] * len(planned), [None] * len(planned)
+        if swin is not None:
+            self._window_masks(planned, hw, dev, None, hw if ahw is None else ahw, masks, flipped, swin)
+            return masks, flipped
         if win is None and ahw is not None and list(ahw) != list(hw):
             win = [(*hw[i], 0, 0) for i in range(len(planned))]
         if win is not None:
@@ -1172,7 +1355,7 @@ class ImagePipeline:
                 masks[i] = plain[o:o + c] if planned[i].get("flip") else flipped[i]
                 o += c
 
-    def _window_masks(self, planned, hw, dev, win, ahw, masks, flipped):
+    def _window_masks(self, planned, hw, dev, win, ahw, masks, flipped, swin=None):
         """_masks for a batch whose samples are windows of their virtual resized images.  The second list (the assigner's
         masks: flipped with the sample, zero-padded to ahw) comes straight from the source masks, per group of equal source
         and assigner sizes -- one launch whatever scales and window sizes the samples drew: radet_mask_max +
@@ -1181,7 +1364,9 @@ class ImagePipeline:
         output for an unflipped sample; when a merged sample is flipped, bitmaps take a second pass over the stack and the
         run-list launch writes both orientations.  These masks have the assigner's size: for a sample smaller than the
         pad the merge reads their top-left corner (the mask pitch word of its params row).  The launches of a batch do not
-        depend on the scales and window sizes its samples drew.  Nothing waits for the device."""
+        depend on the scales and window sizes its samples drew.  Nothing waits for the device.
+        swin (instead of win): the samples are source windows (y0, x0, h, w, fill) resized to hw -- the same launches with
+        radet_mask_transform_src_window / radet_rle_masks_src_window and their rows {Hr, Wr, y0, x0, h, w, flip}."""
         groups, rle_groups = {}, {}
         for i, s in enumerate(planned):
             if "gt_masks_rle" in s and "gt_masks" in s:
@@ -1192,8 +1377,14 @@ class ImagePipeline:
                 rle_groups.setdefault((tuple(s["gt_masks_rle"][1]), ahw[i]), []).append(i)
 
         def rows_of(idx, counts, with_flip):
+            if swin is not None:
+                rows = np.array([[*hw[i], *swin[i][:4], with_flip and bool(planned[i].get("flip"))] for i in idx], np.int32)
+                return np.repeat(rows.reshape(-1, K.MASK_SRC_WIN_INTS), counts, axis=0)
             rows = np.array([[*win[i], *hw[i], with_flip and bool(planned[i].get("flip"))] for i in idx], np.int32)
             return np.repeat(rows.reshape(-1, K.MASK_WIN_INTS), counts, axis=0)
+
+        mask_transform = K.mask_transform_window if swin is None else K.mask_transform_src_window
+        rle_masks = K.rle_masks_window if swin is None else K.rle_masks_src_window
 
         def hand_out(idx, counts, out, plain):
             o = 0
@@ -1213,8 +1404,8 @@ class ImagePipeline:
             src = torch.from_numpy(np.concatenate([planned[i]["gt_masks"] for i in idx])).to(dev)
             rows = torch.from_numpy(np.concatenate([rows_of(idx, counts, True)] + ([rows_of(idx, counts, False)] if both else []))).to(dev)
             mx = K.mask_max(src)
-            out = K.mask_transform_window(src, rows[:G], out_hw, norm_max=mx)
-            plain = K.mask_transform_window(src, rows[G:], out_hw, norm_max=mx) if both else None
+            out = mask_transform(src, rows[:G], out_hw, norm_max=mx)
+            plain = mask_transform(src, rows[G:], out_hw, norm_max=mx) if both else None
             hand_out(idx, counts, out, plain)
         for (src_hw, out_hw), idx in rle_groups.items():
             per_mask = [m for i in idx for m in planned[i]["gt_masks_rle"][0]]
@@ -1229,8 +1420,8 @@ class ImagePipeline:
                                                       rows_of(idx, counts, False).reshape(-1)]))
             packed = packed.pin_memory().to(dev, non_blocking=True)
             a, b, c = ends.size, ends.size + prows.size, ends.size + prows.size + mrows.size
-            res = K.rle_masks_window(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:c].view(-1, K.RLE_MASK_INTS),
-                                     packed[c:].view(-1, K.MASK_WIN_INTS), out_hw, with_plain=both)
+            res = rle_masks(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:c].view(-1, K.RLE_MASK_INTS),
+                            packed[c:].view(-1, K.MASK_WIN_INTS), out_hw, with_plain=both)
             out, plain = res if both else (res, None)
             hand_out(idx, counts, out, plain)
 

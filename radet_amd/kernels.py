@@ -1548,6 +1548,30 @@ def mask_transform_window(src, win_desc, out_hw, pad_val=0, normalize=False, nor
     return dst
 
 
+MASK_SRC_WIN_INTS = 7                     # include/radet_hip.h
+
+
+def mask_transform_src_window(src, win_desc, out_hw, pad_val=0, normalize=False, norm_max=None):
+    """src: u8[G,Hs,Ws] device tensor -> u8[G,Hd,Wd]: per mask the window of the SOURCE mask that its win_desc row names
+    (i32 [G, MASK_SRC_WIN_INTS] on the device: {Hr, Wr, wy0, wx0, wh, ww, flip}; the window may overhang the mask, zeros
+    outside it) nearest-resized to Hr x Wr, flipped, padded to out_hw -- np.pad / slice, then mask_transform, in one pass.
+    normalize / norm_max: by the maximum of the whole source mask, as mask_transform_window"""
+    G, Hs, Ws = src.shape
+    Hd, Wd = out_hw
+    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=src.device)
+    if G == 0:
+        return dst
+    assert tuple(win_desc.shape) == (G, MASK_SRC_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
+    mx = norm_max
+    if mx is not None:
+        assert tuple(mx.shape) == (G,) and mx.dtype == torch.int32 and mx.is_contiguous()
+    elif normalize:
+        mx = mask_max(src)
+    _lib.call("radet_mask_transform_src_window", _ptr(src), _ptr(dst), _ptr(mx), _ptr(win_desc), G, Hs, Ws, Hd, Wd, int(pad_val),
+              _stream())
+    return dst
+
+
 RLE_MASK_INTS, RLE_PART_INTS = 5, 2       # include/radet_hip.h
 RLE_MAX_W = 8192
 
@@ -1579,6 +1603,20 @@ def rle_masks_window(run_ends, part_desc, mask_desc, win_desc, out_hw, pad_val=0
     if G:
         assert tuple(win_desc.shape) == (G, MASK_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
         _lib.call("radet_rle_masks_window", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc),
+                  _ptr(win_desc), G, _ptr(dst), _ptr(plain), Hd, Wd, int(pad_val), _stream())
+    return (dst, plain) if with_plain else dst
+
+
+def rle_masks_src_window(run_ends, part_desc, mask_desc, win_desc, out_hw, pad_val=0, with_plain=False):
+    """rle_masks for per-mask windows of the source masks (win_desc as for mask_transform_src_window; the flip is
+    mask_desc's); a sample outside the source image decodes as 0"""
+    G = mask_desc.shape[0]
+    Hd, Wd = out_hw
+    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=mask_desc.device)
+    plain = torch.empty_like(dst) if with_plain else None
+    if G:
+        assert tuple(win_desc.shape) == (G, MASK_SRC_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
+        _lib.call("radet_rle_masks_src_window", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc),
                   _ptr(win_desc), G, _ptr(dst), _ptr(plain), Hd, Wd, int(pad_val), _stream())
     return (dst, plain) if with_plain else dst
 
@@ -1640,6 +1678,16 @@ def resize_linear_u8_window(src, sdesc, dst, wdesc, n, max_dst_px, channels=3):
     """resize_linear_u8 writing only a window of each virtual resized image: wdesc i32 [n, RESIZE_WIN_DESC_INTS] on the
     device, {packed pixel offset, window h, w, resized Hr, Wr, window origin y0, x0}"""
     _lib.call("radet_resize_linear_u8_window", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(wdesc), n, max_dst_px, channels, _stream())
+
+
+RESIZE_SRC_WIN_DESC_INTS = 8              # include/radet_hip.h
+
+
+def resize_linear_u8_src_window(src, sdesc, dst, wdesc, n, max_dst_px, channels=3):
+    """resize_linear_u8 of a window of each source image (it may overhang the image: a fill colour outside): wdesc i32
+    [n, RESIZE_SRC_WIN_DESC_INTS] on the device, {packed pixel offset, output Hr, Wr, window origin wy0, wx0 in the
+    source's coordinates, window wh, ww, fill c0 | c1 << 8 | c2 << 16}"""
+    _lib.call("radet_resize_linear_u8_src_window", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(wdesc), n, max_dst_px, channels, _stream())
 
 
 def resize_linear_f(src, sdesc, dst, ddesc, n, max_dst_px):
