@@ -1,0 +1,5 @@
+# r50_ycbv_pbr.py trained with in-plane rotation: the model, losses and schedule of that file, the data pipeline of
+# base/datasets/bop_detection_rotate.py (Rotate(30 degrees, prob 0.5) directly after Resize: constant 480 x 640 batches).
+_base_ = ['./r50_ycbv_pbr.py', '../base/datasets/bop_detection_rotate.py']
+
+data = dict(samples_per_gpu=16, workers_per_gpu=8)

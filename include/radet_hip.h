@@ -621,6 +621,35 @@ int radet_crop_canvases(const uint8_t* src, size_t src_bytes, const unsigned lon
 int radet_paste_maps(const void* maps, size_t map_px, int is_f64, const int* desc, int nbox, int H, int W, float* out,
                      void* stream);
 
+/* ---- affine augmentation (csrc/warp.hip): Rotate / Shear / Translate of radet/datasets/pipelines/auto_augment.py, i.e.
+ *      cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT, output size = input size) in its classic fixed-point form, for nimg
+ *      packed u8 HWC images of mixed sizes (channels == 3) or single planes such as instance masks (channels == 1) in one
+ *      launch.  desc (device) = nimg rows of WARP_DESC_INTS ints:
+ *      [WARP_DESC_SRC] pixel offset of the image in src, [WARP_DESC_DST] pixel offset of the output in dst, [WARP_DESC_H],
+ *      [WARP_DESC_W], [WARP_DESC_CHANNELS] (must equal `channels`), [WARP_DESC_FILL] fill = c0 | c1 << 8 | c2 << 16 in the
+ *      image's channel order, [WARP_DESC_FLAGS] (WARP_SKIP: the image is copied unchanged), one spare word, then from
+ *      [WARP_DESC_MATRIX] the INVERSE 2 x 3 matrix {M0 .. M5} as 6 doubles (low word first): the host inverts the forward
+ *      matrix in double exactly as cv2 does.  Per output pixel (x, y), AB = 1024, round = half to even:
+ *          X0 = round((M1 y + M2) AB) + 16, Y0 = round((M4 y + M5) AB) + 16,
+ *          X = (X0 + round(M0 x AB)) >> 5, Y = (Y0 + round(M3 x AB)) >> 5, sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31,
+ *          dst = (sum of the four taps at (sx, sy) .. (sx + 1, sy + 1) times (32 - fx | fx)(32 - fy | fy) + 512) >> 10,
+ *      every double product and sum rounded on its own; a tap outside the image is the fill byte of its channel.
+ *      src_px / dst_px: the sizes of src / dst in pixels (< 2^31); a row that does not lie inside them, or with h, w <= 0 or
+ *      another channel count, is not written.  src != dst.  max_px = the largest image's pixel count; nimg <= 65535.
+ *      The caller keeps |M0| w + |M1| h + |M2| (and the second row's) below 2^21 so that the coordinates fit 32 bits. */
+#define WARP_DESC_INTS 20
+#define WARP_DESC_SRC 0
+#define WARP_DESC_DST 1
+#define WARP_DESC_H 2
+#define WARP_DESC_W 3
+#define WARP_DESC_CHANNELS 4
+#define WARP_DESC_FILL 5
+#define WARP_DESC_FLAGS 6
+#define WARP_DESC_MATRIX 8
+#define WARP_SKIP 1
+int radet_warp_affine_u8(const uint8_t* src, size_t src_px, uint8_t* dst, size_t dst_px, const int* desc, int nimg, int max_px,
+                         int channels, void* stream);
+
 /* ---- in-memory frames through the test pipeline in one launch (csrc/preprocess.hip): LoadImageFromWebcam -> Resize ->
  *      Normalize -> Pad (radet/datasets/pipelines/loading.py:88 as radet/apis/inference.py:97-102 uses it).  nimg u8 HWC BGR
  *      frames of any, mixed sizes -> out f32 [nimg,3,Hp,Wp]: what radet_resize_linear_u8 followed by radet_augment_finish

@@ -23,6 +23,9 @@ Zoom (Expand, MinIoURandomCrop, in front of Resize): the mirror image -- the sta
 canvas in image coordinates, which may overhang the image (s["src_window"]); run() resizes that window straight from the
 image, the canvas fill where it overhangs (radet_resize_linear_u8_src_window, radet_mask_transform_src_window,
 radet_rle_masks_src_window in the place of their plain counterparts); no canvas is ever made.
+Affine augmentation (Rotate, Shear, Translate, or one AutoAugment over them, directly after Resize): the stages plan boxes
+and leave forward matrices in s["affine"]; run() warps the resized frames and the resized, unflipped masks once per
+entry (radet_warp_affine_u8: cv2.warpAffine's classic fixed-point bilinear path), in front of the merge and the flip.
 Options the RADet configs do not use raise NotImplementedError."""
 import glob
 import math
@@ -44,10 +47,11 @@ osp = os.path
 DEFAULT_META_KEYS = ("filename", "ori_filename", "ori_shape", "img_shape", "pad_shape", "scale_factor", "flip",
                      "flip_direction", "img_norm_cfg")
 # stage order of the device part (a pipeline lists a subsequence of it; MultiScaleFlipAug's transforms sit in its place)
-_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Expand", "MinIoURandomCrop", "Resize", "RandomCrop", "RandomBackground", "CosyPoseAug", "RandomHSV",
+_ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Expand", "MinIoURandomCrop", "Resize", "RandomCrop", "Affine", "RandomBackground", "CosyPoseAug", "RandomHSV",
           "RandomNoise", "RandomSmooth", "RandomFlip", "GenerateDistanceMap", "LabelAssignment", "Normalize", "Pad",
           "DefaultFormatBundle", "ImageToTensor", "Collect")
 _ZOOM = ("Expand", "MinIoURandomCrop")                       # the source-window stages
+_AFFINE = ("Rotate", "Shear", "Translate", "AutoAugment")    # the warp stages: one block in the "Affine" slot of _ORDER
 _MIX = ("RandomHSV", "RandomNoise", "RandomSmooth")          # the mixpbr stages: aug_hsv_noise + aug_box
 _COSY_ORDER = ("PillowBlur", "PillowSharpness", "PillowContrast", "PillowBrightness", "PillowColor")
 # flags of a params row (include/radet_hip.h)
@@ -522,6 +526,257 @@ class RandomCrop:
         s["img_shape"] = s["pad_shape"] = (ch, cw, 3)
 
 
+# ---------------------------------------------------------------------------------------------------- affine
+_MAX_LEVEL = 10
+_AFFINE_MAX_ENTRIES = 4
+
+
+def rotation_matrix(center, angle, scale):
+    """cv2.getRotationMatrix2D(center, angle, scale): float64 [2, 3]"""
+    a = math.radians(angle)
+    alpha, beta = math.cos(a) * scale, math.sin(a) * scale
+    cx, cy = float(center[0]), float(center[1])
+    return np.array([[alpha, beta, (1 - alpha) * cx - beta * cy], [-beta, alpha, beta * cx + (1 - alpha) * cy]], np.float64)
+
+
+def shear_matrix(magnitude, direction):
+    """mmcv.imshear's matrix: float32 entries, widened to float64 as cv2.warpAffine does"""
+    m = np.float32([[1, magnitude, 0], [0, 1, 0]]) if direction == "horizontal" else np.float32([[1, 0, 0], [magnitude, 1, 0]])
+    return m.astype(np.float64)
+
+
+def translate_matrix(offset, direction):
+    """mmcv.imtranslate's matrix: float32 entries, widened to float64"""
+    m = np.float32([[1, 0, offset], [0, 1, 0]]) if direction == "horizontal" else np.float32([[1, 0, 0], [0, 1, offset]])
+    return m.astype(np.float64)
+
+
+def _fill_arg(name, img_fill_val):
+    """img_fill_val as the reference takes it -> the three bytes cv2 stores for that borderValue (rounded half to even)"""
+    if isinstance(img_fill_val, (float, int)):
+        vals = (float(img_fill_val),) * 3
+    elif isinstance(img_fill_val, tuple) and len(img_fill_val) == 3:
+        vals = tuple(float(v) for v in img_fill_val)
+    else:
+        raise ValueError(f"{name}: img_fill_val is a number or a tuple of 3, got {img_fill_val!r}")
+    if not all(0 <= v <= 255 for v in vals):
+        raise ValueError(f"{name}: img_fill_val {img_fill_val!r} outside [0, 255]")
+    return vals, tuple(int(np.rint(v)) for v in vals)
+
+
+class _AffineStage:
+    """What Rotate, Shear and Translate share: the gate and sign draws on the sample's NumPy generator (rand() > prob,
+    then rand() < random_negative_prob, the reference's calls in its order), the filter of boxes that the move left
+    without extent, and the record: a stage that fires appends (forward 2 x 3 matrix float64, fill bytes in the image's
+    channel order) to s["affine"] and (stage name, signed angle / magnitude / offset) to s["affine_draws"];
+    ImagePipeline.run warps the resized frame and its masks once per entry."""
+    bbox2label = {"gt_bboxes": "gt_labels", "gt_bboxes_ignore": "gt_labels_ignore"}
+    bbox2mask = {"gt_bboxes": "gt_masks", "gt_bboxes_ignore": "gt_masks_ignore"}
+
+    def _common(self, level, img_fill_val, seg_ignore_label, prob, random_negative_prob):
+        name = type(self).__name__
+        if not isinstance(level, (int, float)) or not 0 <= level <= _MAX_LEVEL:
+            raise ValueError(f"{name}: level is a number in [0, {_MAX_LEVEL}], got {level!r}")
+        if not 0 <= prob <= 1.0:
+            raise ValueError(f"{name}: prob is in [0, 1], got {prob!r}")
+        self.level, self.prob, self.random_negative_prob = level, prob, random_negative_prob
+        self.img_fill_val, self.fill = _fill_arg(name, img_fill_val)
+        self.seg_ignore_label = seg_ignore_label
+
+    def _negative(self, value, nprnd):
+        return -value if nprnd.rand() < self.random_negative_prob else value
+
+    def _size(self, s):
+        if s.get("seg_fields"):
+            _refuse(f"{type(self).__name__} on a sample with seg_fields (semantic segmentation maps)")
+        return int(s["img_shape"][0]), int(s["img_shape"][1])
+
+    def _record(self, s, matrix, h, w):
+        entries = s.setdefault("affine", [])
+        if len(entries) >= _AFFINE_MAX_ENTRIES:
+            _refuse(f"more than {_AFFINE_MAX_ENTRIES} affine stages firing on one sample")
+        if not K.warp_fits(K.invert_affine(matrix), h, w):
+            _refuse(f"{type(self).__name__}: matrix {matrix.tolist()} on an image of {h} x {w} (its inverse leaves the warp "
+                    f"kernel's 32-bit fixed point)")
+        entries.append((np.asarray(matrix, np.float64), self.fill))
+
+    def _filter_invalid(self, s, min_size=0):
+        for key in s.get("bbox_fields", []):
+            b = s[key]
+            keep = np.nonzero((b[:, 2] - b[:, 0] > min_size) & (b[:, 3] - b[:, 1] > min_size))[0]
+            s[key] = b[keep]
+            label_key, mask_key = self.bbox2label.get(key), self.bbox2mask.get(key)
+            if label_key in s:
+                s[label_key] = s[label_key][keep]
+            if mask_key in s:
+                s[mask_key] = s[mask_key][keep]
+            if mask_key is not None and mask_key + "_rle" in s:
+                parts, src_hw = s[mask_key + "_rle"]
+                s[mask_key + "_rle"] = ([parts[k] for k in keep], src_hw)
+
+    def worst_matrices(self, h, w):
+        """the matrices of both signs on an h x w image (the build-time check of the fixed-point range)"""
+        raise NotImplementedError
+
+
+def _box_corners(b):
+    """[4, 2, n, 1]: the corners (min, min), (max, min), (min, max), (max, max) of n boxes, in the boxes' dtype"""
+    x0, y0, x1, y1 = np.split(b, b.shape[-1], axis=-1)
+    return np.stack([[x0, y0], [x1, y0], [x0, y1], [x1, y1]])
+
+
+def _corner_extent(xs, ys, h, w, dtype):
+    """the box around moved corners (xs, ys: [n, 4]), clipped to the image as the reference clips it"""
+    x0, y0 = np.clip(np.min(xs, axis=-1), a_min=0, a_max=w), np.clip(np.min(ys, axis=-1), a_min=0, a_max=h)
+    x1, y1 = np.clip(np.max(xs, axis=-1), a_min=x0, a_max=w), np.clip(np.max(ys, axis=-1), a_min=y0, a_max=h)
+    return np.stack([x0, y0, x1, y1], axis=-1).astype(dtype)
+
+
+@PIPELINES.register_module()
+class Rotate(_AffineStage):
+    """The reference's Rotate (auto_augment.py:329-540), planned: angle = level / 10 * max_rotate_angle, negated by the sign
+    draw; matrix cv2.getRotationMatrix2D(center, -angle, scale) about ((w - 1) / 2, (h - 1) / 2) of the image as it is at
+    that point unless `center` is given; boxes: the float64 matrix times the homogeneous corners, the extent, clipped."""
+
+    def __init__(self, level, scale=1, center=None, img_fill_val=128, seg_ignore_label=255, prob=0.5, max_rotate_angle=30,
+                 random_negative_prob=0.5):
+        self._common(level, img_fill_val, seg_ignore_label, prob, random_negative_prob)
+        if not isinstance(scale, (int, float)):
+            raise ValueError(f"Rotate: scale is a number, got {scale!r}")
+        if scale == 0:
+            _refuse("Rotate(scale=0) (a singular matrix: nothing of the image is left)")
+        if isinstance(center, (int, float)):
+            center = (center, center)
+        elif center is not None and not (isinstance(center, tuple) and len(center) == 2):
+            raise ValueError(f"Rotate: center is None, a number or a tuple of 2, got {center!r}")
+        if not isinstance(max_rotate_angle, (int, float)):
+            raise ValueError(f"Rotate: max_rotate_angle is a number, got {max_rotate_angle!r}")
+        self.scale, self.center, self.max_rotate_angle = scale, center, max_rotate_angle
+        self.angle = (level / _MAX_LEVEL) * max_rotate_angle
+
+    def _matrix(self, angle, h, w):
+        center = self.center if self.center is not None else ((w - 1) * 0.5, (h - 1) * 0.5)
+        return rotation_matrix(center, -angle, self.scale)
+
+    def worst_matrices(self, h, w):
+        return [self._matrix(self.angle, h, w), self._matrix(-self.angle, h, w)]
+
+    def plan(self, s, rnd, nprnd):
+        if nprnd.rand() > self.prob:
+            return
+        h, w = self._size(s)
+        angle = self._negative(self.angle, nprnd)
+        matrix = self._matrix(angle, h, w)
+        self._record(s, matrix, h, w)
+        for key in s.get("bbox_fields", []):
+            c = _box_corners(s[key])
+            c = np.concatenate((c, np.ones((4, 1, c.shape[2], 1), c.dtype)), axis=1).transpose((2, 0, 1, 3))
+            moved = np.matmul(matrix, c)[..., 0]                              # [n, 4, 2], float64
+            s[key] = _corner_extent(moved[:, :, 0], moved[:, :, 1], h, w, s[key].dtype)
+        self._filter_invalid(s)
+        s.setdefault("affine_draws", []).append(("Rotate", float(angle)))
+
+
+@PIPELINES.register_module()
+class Shear(_AffineStage):
+    """The reference's Shear (auto_augment.py:112-325), planned: magnitude = level / 10 * max_shear_magnitude, negated by
+    the sign draw; boxes: a float32 2 x 2 matrix times the corners, the extent, clipped"""
+
+    def __init__(self, level, img_fill_val=128, seg_ignore_label=255, prob=0.5, direction="horizontal", max_shear_magnitude=0.3,
+                 random_negative_prob=0.5, interpolation="bilinear"):
+        self._common(level, img_fill_val, seg_ignore_label, prob, random_negative_prob)
+        if direction not in ("horizontal", "vertical"):
+            raise ValueError(f"Shear: direction is 'horizontal' or 'vertical', got {direction!r}")
+        if not isinstance(max_shear_magnitude, float) or not 0. <= max_shear_magnitude <= 1.:
+            raise ValueError(f"Shear: max_shear_magnitude is a float in [0, 1], got {max_shear_magnitude!r}")
+        if interpolation != "bilinear":
+            _refuse(f"Shear(interpolation={interpolation!r}) (the warp kernel is cv2's bilinear one)")
+        self.direction, self.max_shear_magnitude, self.interpolation = direction, max_shear_magnitude, interpolation
+        self.magnitude = (level / _MAX_LEVEL) * max_shear_magnitude
+
+    def worst_matrices(self, h, w):
+        return [shear_matrix(self.magnitude, self.direction), shear_matrix(-self.magnitude, self.direction)]
+
+    def plan(self, s, rnd, nprnd):
+        if nprnd.rand() > self.prob:
+            return
+        h, w = self._size(s)
+        magnitude = self._negative(self.magnitude, nprnd)
+        self._record(s, shear_matrix(magnitude, self.direction), h, w)
+        m22 = np.stack([[1, magnitude], [0, 1]] if self.direction == "horizontal" else [[1, 0], [magnitude, 1]]).astype(np.float32)
+        for key in s.get("bbox_fields", []):
+            c = _box_corners(s[key])[..., 0].transpose((2, 1, 0)).astype(np.float32)      # [n, 2, 4]
+            moved = np.matmul(m22[None, :, :], c)
+            s[key] = _corner_extent(moved[:, 0, :], moved[:, 1, :], h, w, s[key].dtype)
+        self._filter_invalid(s)
+        s.setdefault("affine_draws", []).append(("Shear", float(magnitude)))
+
+
+@PIPELINES.register_module()
+class Translate(_AffineStage):
+    """The reference's Translate (auto_augment.py:543-705), planned: offset = int(level / 10 * max_translate_offset) pixels,
+    negated by the sign draw; boxes shifted and cut at the image's border, those left with an extent of at most min_size
+    dropped"""
+
+    def __init__(self, level, prob=0.5, img_fill_val=128, seg_ignore_label=255, direction="horizontal", max_translate_offset=250.,
+                 random_negative_prob=0.5, min_size=0):
+        self._common(level, img_fill_val, seg_ignore_label, prob, random_negative_prob)
+        if direction not in ("horizontal", "vertical"):
+            raise ValueError(f"Translate: direction is 'horizontal' or 'vertical', got {direction!r}")
+        if not isinstance(max_translate_offset, (int, float)):
+            raise ValueError(f"Translate: max_translate_offset is a number, got {max_translate_offset!r}")
+        self.direction, self.max_translate_offset, self.min_size = direction, max_translate_offset, min_size
+        self.offset = int((level / _MAX_LEVEL) * max_translate_offset)
+
+    def worst_matrices(self, h, w):
+        return [translate_matrix(self.offset, self.direction), translate_matrix(-self.offset, self.direction)]
+
+    def plan(self, s, rnd, nprnd):
+        if nprnd.rand() > self.prob:
+            return
+        h, w = self._size(s)
+        offset = self._negative(self.offset, nprnd)
+        self._record(s, translate_matrix(offset, self.direction), h, w)
+        for key in s.get("bbox_fields", []):
+            x0, y0, x1, y1 = np.split(s[key], s[key].shape[-1], axis=-1)
+            if self.direction == "horizontal":
+                x0, x1 = np.maximum(0, x0 + offset), np.minimum(w, x1 + offset)
+            else:
+                y0, y1 = np.maximum(0, y0 + offset), np.minimum(h, y1 + offset)
+            s[key] = np.concatenate([x0, y0, x1, y1], axis=-1)
+        self._filter_invalid(s, self.min_size)
+        s.setdefault("affine_draws", []).append(("Translate", int(offset)))
+
+
+_AFFINE_STAGES = ("Rotate", "Shear", "Translate")
+
+
+@PIPELINES.register_module()
+class AutoAugment:
+    """The reference's AutoAugment (auto_augment.py:45-108) over the affine stages: np.random.choice over the policies on
+    the sample's NumPy generator, then the stages of the chosen policy in order.  s["policy"] = the index drawn."""
+
+    def __init__(self, policies):
+        if not isinstance(policies, list) or not policies or not all(isinstance(p, list) and p for p in policies):
+            raise ValueError("AutoAugment: policies is a non-empty list of non-empty lists")
+        for policy in policies:
+            for t in policy:
+                if not isinstance(t, dict) or "type" not in t:
+                    raise ValueError("AutoAugment: each augmentation is a dict with the key 'type'")
+                if t["type"] not in _AFFINE_STAGES:
+                    _refuse(f"AutoAugment policy stage {t['type']} (policies hold {_AFFINE_STAGES} only)")
+            if len(policy) > _AFFINE_MAX_ENTRIES:
+                _refuse(f"an AutoAugment policy of {len(policy)} stages (at most {_AFFINE_MAX_ENTRIES} affine entries per sample)")
+        self.policies = [[dict(t) for t in policy] for policy in policies]
+        self.transforms = [[build_from_cfg(t, PIPELINES) for t in policy] for policy in self.policies]
+
+    def plan(self, s, rnd, nprnd):
+        k = int(nprnd.choice(len(self.transforms)))
+        s["policy"] = k
+        for t in self.transforms[k]:
+            t.plan(s, rnd, nprnd)
+
+
 @PIPELINES.register_module()
 class RandomFlip:
     def __init__(self, flip_ratio=None, direction="horizontal"):
@@ -854,7 +1109,12 @@ class ImagePipeline:
         if self.frames:
             names[0] = "LoadImageFromFile"
             self._check_frame_pipeline(flat, sample_cache)
-        pos = [(_ORDER.index(n) if n in _ORDER else -1) for n in names]
+        block = [k for k, n in enumerate(names) if n in _AFFINE]
+        if block:
+            self._check_affine(flat, names, block)
+        # (the affine block counts as one stage, "Affine", of the order)
+        slots = ["Affine" if n in _AFFINE else n for k, n in enumerate(names) if k not in block[1:]]
+        pos = [(_ORDER.index(n) if n in _ORDER else -1) for n in slots]
         for n in (n for n in names if n in _ZOOM):
             if "Resize" in names and names.index(n) > names.index("Resize"):
                 _refuse(f"{n} after Resize in {names} (the zoom stages plan a window of the source image: they stand before Resize)")
@@ -883,6 +1143,33 @@ class ImagePipeline:
         if self.mask_free is not None and getattr(dm.distance_transform, "extract_edge_func", None) is not None:
             _refuse("GenerateDistanceMap(extract_edge_func=...) in an image pipeline (a host callback)")
         self.tta = any(isinstance(t, MultiScaleFlipAug) for t in self.transforms)
+
+    @staticmethod
+    def _check_affine(flat, names, block):
+        """Rotate / Shear / Translate (in any order, repeats allowed, at most 4) or one AutoAugment: one block directly after
+        Resize.  (Seg fields need no check here: LoadAnnotations(with_seg=True) does not build.)"""
+        where = f"{[names[k] for k in block]} at positions {block} of {names}"
+        if any(isinstance(t, MultiScaleFlipAug) for t in flat):
+            _refuse(f"{names[block[0]]} in a MultiScaleFlipAug (test) pipeline")
+        for other in ("RandomCrop", *_ZOOM):
+            if other in names:
+                _refuse(f"{names[block[0]]} together with {other} (a warp composed with a window is left out)")
+        if block != list(range(block[0], block[0] + len(block))) or block[0] == 0 or names[block[0] - 1] != "Resize":
+            _refuse(f"{where} (the affine stages stand as one block directly after Resize, before RandomBackground)")
+        kinds = [names[k] for k in block]
+        if "AutoAugment" in kinds and len(kinds) > 1:
+            _refuse(f"{where} (bare Rotate / Shear / Translate stages, or one AutoAugment)")
+        if len(kinds) > _AFFINE_MAX_ENTRIES:
+            _refuse(f"{where} (at most {_AFFINE_MAX_ENTRIES} affine entries per sample)")
+        stages = []
+        for t in (flat[k] for k in block):
+            stages += [u for policy in t.transforms for u in policy] if isinstance(t, AutoAugment) else [t]
+        for t in stages:
+            # the fixed-point range of the warp kernel, on the largest image the augmentation kernels take
+            for m in t.worst_matrices(K.AUG_MAX_W, K.AUG_MAX_W):
+                if not K.warp_fits(K.invert_affine(m), K.AUG_MAX_W, K.AUG_MAX_W):
+                    _refuse(f"{type(t).__name__} with the matrix {m.tolist()} (its inverse leaves the warp kernel's 32-bit "
+                            f"fixed point on an image of {K.AUG_MAX_W} x {K.AUG_MAX_W})")
 
     @staticmethod
     def _check_frame_pipeline(flat, sample_cache):
@@ -1049,6 +1336,69 @@ class ImagePipeline:
         K.resize_linear_u8(src, desc[:n], dst, desc[n:], n, max(h * w for h, w in dst_hw), 3)
         return dst, [d[0] for d in ddesc]
 
+    @staticmethod
+    def _warp_packed(img, entries, offs, hw, dev, channels=3):
+        """The affine entries of a batch applied to its packed images: one radet_warp_affine_u8 launch per entry rank k = 0 ..
+        the longest list - 1, ping-ponging between `img` and one more buffer of its size; an image with fewer than k + 1
+        entries is copied (WARP_SKIP).  entries: per image a list of (forward 2 x 3 matrix, fill); offs / hw: per image its
+        pixel offset and size.  One descriptor upload for all ranks.  Returns the buffer that holds the result."""
+        ranks = max(len(e) for e in entries)
+        if not ranks:
+            return img
+        D = np.zeros((ranks, len(entries), K.WARP_DESC_INTS), np.int32)
+        for k in range(ranks):
+            for row, e, o, (h, w) in zip(D[k], entries, offs, hw):
+                K.warp_desc_row(row, o, o, h, w, channels, *(e[k] if k < len(e) else (None,)))
+        desc = torch.from_numpy(D).to(dev)
+        cur, other = img, torch.empty_like(img)
+        for k in range(ranks):
+            K.warp_affine_u8(cur, other, desc[k], len(entries), max(h * w for h, w in hw), channels)
+            cur, other = other, cur
+        return cur
+
+    def _affine_masks(self, planned, hw, dev, ahw):
+        """_masks for a batch in which some sample carries affine entries.  Per group of samples of equal source size,
+        resized size, assigner size and flip: the unflipped resized bitmaps (radet_mask_max + radet_mask_transform, or
+        radet_rle_masks for run lists), one warp launch per entry rank on the stack (one channel, fill 0; the masks of a
+        sample with fewer entries are copied), then flip and pad for the assigner in one radet_mask_transform pass where
+        the group needs either.  The first list (the merge's masks) is the warped, unflipped stack."""
+        masks, flipped = [None] * len(planned), [None] * len(planned)
+        groups = {}
+        for i, s in enumerate(planned):
+            if "gt_masks_rle" in s and "gt_masks" in s:
+                raise ValueError("a sample carries both gt_masks and gt_masks_rle")
+            if "gt_masks" in s:
+                groups.setdefault(("bitmap", tuple(s["gt_masks"].shape[1:]), hw[i], ahw[i], bool(s.get("flip"))), []).append(i)
+            elif "gt_masks_rle" in s:
+                groups.setdefault(("runs", tuple(s["gt_masks_rle"][1]), hw[i], ahw[i], bool(s.get("flip"))), []).append(i)
+        for (kind, src_hw, dst_hw, out_hw, flip), idx in groups.items():
+            counts = [len(planned[i]["gt_masks"] if kind == "bitmap" else planned[i]["gt_masks_rle"][0]) for i in idx]
+            G = sum(counts)
+            if not G:
+                for i in idx:
+                    masks[i] = torch.zeros(0, *dst_hw, dtype=torch.uint8, device=dev)
+                    flipped[i] = torch.zeros(0, *out_hw, dtype=torch.uint8, device=dev)
+                continue
+            if kind == "bitmap":
+                src = torch.from_numpy(np.concatenate([planned[i]["gt_masks"] for i in idx])).to(dev)
+                res = K.mask_transform(src, resized_hw=dst_hw, normalize=True)
+            else:
+                per_mask = [m for i in idx for m in planned[i]["gt_masks_rle"][0]]
+                ends, prows, mrows = rle.pack_runs(per_mask, *src_hw, np.zeros(G, bool))
+                packed = torch.from_numpy(np.concatenate([ends.view(np.int32), prows.reshape(-1), mrows.reshape(-1)]))
+                packed = packed.pin_memory().to(dev, non_blocking=True)
+                a, b = ends.size, ends.size + prows.size
+                res = K.rle_masks(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:].view(-1, K.RLE_MASK_INTS), dst_hw)
+            px = dst_hw[0] * dst_hw[1]
+            entries = [[(m, (0, 0, 0)) for m, _ in planned[i].get("affine", ())] for i, c in zip(idx, counts) for _ in range(c)]
+            res = self._warp_packed(res.view(-1), entries, [g * px for g in range(G)], [dst_hw] * G, dev, channels=1).view(G, *dst_hw)
+            fl = K.mask_transform(res, out_hw=out_hw, flip="horizontal" if flip else None) if flip or out_hw != dst_hw else res
+            o = 0
+            for i, c in zip(idx, counts):
+                masks[i], flipped[i] = res[o:o + c], fl[o:o + c]
+                o += c
+        return masks, flipped
+
     def run(self, planned, collate=False):
         """device part of a batch of planned samples; returns per-sample dicts, or one collated batch dict"""
         if self.frames:
@@ -1097,11 +1447,17 @@ class ImagePipeline:
             bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev)
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         bg_off = dict(zip(with_bg, bg_offs))
+        affine = any(s.get("affine") for s in planned)
+        if affine:
+            if win is not None or swin is not None:
+                raise ValueError("a batch with affine entries and windows (RandomCrop / Expand / MinIoURandomCrop)")
+            img = self._warp_packed(img, [s.get("affine", ()) for s in planned], offs, hw, dev)
         # Pad(size=): the assigner sees the padded sample -- its masks / maps zero-padded to the fixed size, its points those
         # of that size, which are the head's for every sample of the batch whatever scale was drawn (with Pad(size_divisor=)
         # the points follow img_shape as in the reference)
         ahw = [tuple(s["pad_shape"][:2]) if s.get("pad_fixed_size") is not None else hw[i] for i, s in enumerate(planned)]
-        masks, flipped_masks = self._masks(planned, hw, dev, win, ahw, swin)
+        masks, flipped_masks = (self._affine_masks(planned, hw, dev, ahw) if affine
+                                else self._masks(planned, hw, dev, win, ahw, swin))
 
         P = np.zeros((B, K.AUG_PARAM_INTS), np.int32)
         for i, s in enumerate(planned):

@@ -1690,6 +1690,75 @@ def resize_linear_u8_src_window(src, sdesc, dst, wdesc, n, max_dst_px, channels=
     _lib.call("radet_resize_linear_u8_src_window", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(wdesc), n, max_dst_px, channels, _stream())
 
 
+# ---------------------------------------------------------------------- affine augmentation (csrc/warp.hip)
+WARP_DESC_INTS, WARP_DESC_MATRIX, WARP_SKIP = 20, 8, 1      # include/radet_hip.h
+WARP_MAX_COORD = float(1 << 21)
+
+
+def invert_affine(M):
+    """the inverse of a 2 x 3 forward matrix as cv2.warpAffine computes it (float64, its operation order; a singular
+    matrix inverts to zeros, as there) -> float64 [6]"""
+    import numpy as np
+    m = np.array(M, np.float64).reshape(6)
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = m[4] * D, m[0] * D
+    m[0] = A11
+    m[1] *= -D
+    m[3] *= -D
+    m[4] = A22
+    b1 = -m[0] * m[2] - m[1] * m[5]
+    b2 = -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    return m
+
+
+def warp_fits(inv, h, w):
+    """whether the kernel's coordinates of an h x w image under the inverse matrix `inv` stay inside 32-bit fixed point"""
+    import numpy as np
+    m = np.abs(np.asarray(inv, np.float64).reshape(6))
+    lim = WARP_MAX_COORD - 1                                      # (room for the rounding offsets)
+    return bool(np.isfinite(m).all() and m[0] * w + m[1] * h + m[2] < lim and m[3] * w + m[4] * h + m[5] < lim)
+
+
+def warp_desc_row(row, src_off, dst_off, h, w, channels, forward=None, fill=(0, 0, 0)):
+    """fills one int32 [WARP_DESC_INTS] row; forward: the 2 x 3 forward matrix (what cv2.warpAffine is handed), None for a
+    row that is copied unchanged (WARP_SKIP)"""
+    import numpy as np
+    f = tuple(int(v) for v in fill) + (0, 0, 0)
+    row[:8] = [src_off, dst_off, h, w, channels, f[0] | f[1] << 8 | f[2] << 16, WARP_SKIP if forward is None else 0, 0]
+    inv = np.zeros(6, np.float64) if forward is None else invert_affine(forward)
+    if forward is not None and not warp_fits(inv, h, w):
+        raise ValueError(f"affine matrix {np.asarray(forward).tolist()} on an image of {h} x {w}: the warp kernel's coordinates "
+                         f"leave 32-bit fixed point")
+    row[WARP_DESC_MATRIX:] = inv.view(np.int32)
+
+
+def warp_affine_u8(src, dst, desc, n, max_px, channels=3):
+    """src / dst: packed u8 device buffers (distinct); desc i32 [n, WARP_DESC_INTS] on the device (warp_desc_row): per row
+    cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT) of an h x w x channels image in its classic fixed-point arithmetic, or a
+    copy (WARP_SKIP); bytes of dst outside the rows' images are not written"""
+    assert src.dtype == torch.uint8 and dst.dtype == torch.uint8 and src.is_contiguous() and dst.is_contiguous()
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.numel() >= n * WARP_DESC_INTS
+    _lib.call("radet_warp_affine_u8", _ptr(src), C.c_size_t(src.numel() // channels), _ptr(dst), C.c_size_t(dst.numel() // channels),
+              _ptr(desc), int(n), int(max_px), int(channels), _stream())
+
+
+def warp_affine_masks(src, forward):
+    """src: u8 [G, H, W] device masks; forward: per mask a 2 x 3 forward matrix or None (copied) -> u8 [G, H, W]: the
+    one-channel form of warp_affine_u8 with fill 0, one launch"""
+    import numpy as np
+    G, H, W = src.shape
+    dst = torch.empty_like(src)
+    if G == 0 or H * W == 0:
+        return dst
+    rows = np.zeros((G, WARP_DESC_INTS), np.int32)
+    for g, M in enumerate(forward):
+        warp_desc_row(rows[g], g * H * W, g * H * W, H, W, 1, M)
+    warp_affine_u8(src, dst, torch.from_numpy(rows).to(src.device), G, H * W, 1)
+    return dst
+
+
 def resize_linear_f(src, sdesc, dst, ddesc, n, max_dst_px):
     _lib.call("radet_resize_linear_f", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(ddesc), n, max_dst_px,
               1 if src.dtype == torch.float64 else 0, _stream())
