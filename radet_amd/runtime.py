@@ -412,15 +412,21 @@ class DetectorRuntime:
             with torch.cuda.stream(side):
                 K.unfold_grads(e.table[a * desc_bytes:], b - a, e.max_cout)
                 if bucket_hook is not None:
-                    if _lib.TAPE is not None:       # a replayed step hands the bucket over at the same point, on this stream
-                        _lib.TAPE.cut(lambda: bucket_hook(bucket), side)
-                    bucket_hook(bucket)
+                    self._hand_over(bucket_hook, bucket, side)
         else:
             K.unfold_grads(e.table[a * desc_bytes:], b - a, e.max_cout)
             if bucket_hook is not None:
-                if _lib.TAPE is not None:
-                    _lib.TAPE.cut(lambda: bucket_hook(bucket), None)
-                bucket_hook(bucket)
+                self._hand_over(bucket_hook, bucket, None)
+
+    @staticmethod
+    def _hand_over(bucket_hook, bucket, stream):
+        """bucket_hook(bucket); `stream`: the stream the caller made current for it (None: it did not switch).  While a launch
+        tape is recorded this is a cut: a replayed step hands the bucket over at the same point, on the same stream, and the
+        hook itself -- its converts and events included -- is never recorded (Tape.run_cut)."""
+        if _lib.TAPE is not None:
+            _lib.TAPE.run_cut(lambda: bucket_hook(bucket), stream)
+        else:
+            bucket_hook(bucket)
 
     # ------------------------------------------------------------------ optimiser
     def init_optimizer(self, lr=4e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=35.0, sync=True):
@@ -588,8 +594,9 @@ class DetectorRuntime:
                     ev1.record()                     # end of the backward pass on the main stream
                     self.__dict__.setdefault("comm_marks", []).append((self._ev_begin, ev0, ev1, len(self.reducer.trace)))
                 if record is not None:
-                    record.cut(self.reducer.finish, None)
-                self.reducer.finish()
+                    record.run_cut(self.reducer.finish, None)     # (un-recorded: the replayed step calls it at this cut)
+                else:
+                    self.reducer.finish()
             else:
                 self.backward(next_img=next_img)
             self.optimizer_step(lr=lr, grad_div=float(world))

@@ -8,13 +8,23 @@ The engine's step is a FIXED program over pre-allocated buffers (engine.py), so 
 k except for a handful of argument words: the batch's pointers, the learning rate, the step number.
 
 How: while `_lib.TAPE` is set, `_lib.call` appends every successful call (entry point + raw argument words) and
-`kernels.ev_record / ev_wait` append the cross-stream event operations.  `cut()` closes a segment where Python has to run
-between two launches (the gradient exchange: torch.distributed collectives).  `replay()` patches the per-step words and
-hands each segment to radet_tape_replay -- the same calls, in the same order, on the same streams, so the results are
-bit-identical to the eager step (tests/test_gpu_model.py::test_tape_replay_is_bit_identical).
+`kernels.ev_record / ev_wait` append the cross-stream event operations.  `run_cut()` closes a segment where Python has to
+run between two launches (the gradient exchange: torch.distributed collectives) and runs that Python -- the cut's callback --
+UN-RECORDED: `replay()` calls the callback again between the two segments, so whatever it launches (the bf16 buckets'
+fp32 <-> bf16 converts, events) is issued by the callback itself at every replay and must not be on the tape as well (a convert
+recorded at the head of the next segment would run a second time behind the all-reduce and overwrite the reduced bucket with
+the rank's own gradients).  `replay()` patches the per-step words and hands each segment to radet_tape_replay -- the same
+calls, in the same order, on the same streams, so the results are bit-identical to the eager step
+(tests/test_gpu_properties.py::test_tape_replay_is_bit_identical; with a gradient exchange between the segments:
+tests/test_gpu_distributed.py::test_two_ranks_taped_step_equals_eager, tests/test_gpu_model.py::test_taped_exchange_equals_eager).
 
 What a tape must not see: an allocation during the recorded step (a temporary's address would be baked in and reused after
 it is freed).  `begin()` / `end()` compare the caching allocator's allocation counter and poison the tape if it moved.
+Allocations made INSIDE a cut callback do not count: the callback makes them afresh at every replay and none of their
+addresses reaches the tape.
+
+What a taped call must do: pass every pointer that changes from step to step (the batch's tensors) as a TOP-LEVEL argument.
+`bind()` patches argument words only; a batch pointer inside a by-reference struct or a job table would be replayed stale.
 """
 import ctypes as C
 import struct
@@ -66,6 +76,7 @@ class Tape:
         self.poisoned = None         # reason why this tape must not be replayed
         self.ops = None              # the ctypes array, after end()
         self._alloc0 = None
+        self._alloc_cb = 0           # allocations made inside cut callbacks while recording (re-made at every replay)
         self.replays = 0
 
     # ------------------------------------------------------------------ recording
@@ -83,7 +94,7 @@ class Tape:
     def end(self):
         assert _lib.TAPE is self
         _lib.TAPE = None
-        if self._alloc_count(self.dev) != self._alloc0:
+        if self._alloc_count(self.dev) - self._alloc_cb != self._alloc0:
             self.poisoned = "device memory was allocated while the step was recorded (a temporary's address would be replayed)"
         n = len(self._ops)
         arr = (_lib.RadetTapeOp * max(n, 1))()
@@ -138,10 +149,34 @@ class Tape:
         """Python runs here between two replayed segments: callback() with `stream` (a torch stream) current"""
         self._cuts.append((len(self._ops), callback, stream))
 
+    @staticmethod
+    def _run(callback, stream):
+        if stream is None:
+            return callback()
+        with torch.cuda.stream(stream):
+            return callback()
+
+    def run_cut(self, callback, stream=None):
+        """cut() here and run callback() now, as replay() will run it between the two segments -- with recording suspended:
+        nothing the callback issues (C-ABI calls, event operations) is recorded, and what it allocates does not poison."""
+        assert _lib.TAPE is self
+        self.cut(callback, stream)
+        before = self._alloc_count(self.dev)
+        _lib.TAPE = None
+        try:
+            return self._run(callback, stream)
+        finally:
+            _lib.TAPE = self
+            self._alloc_cb += self._alloc_count(self.dev) - before
+
     def bind(self, name, t):
-        """every pointer argument that points into tensor `t` follows the tensor handed to replay(tensors={name: ...})"""
+        """every pointer argument that points into tensor `t` follows the tensor handed to replay(tensors={name: ...}).
+        An empty tensor owns no address (its data_ptr() is 0, which every NULL argument would match): it binds no site."""
         lo = t.data_ptr()
-        hi = lo + max(t.numel() * t.element_size(), 1)
+        if t.numel() == 0:
+            self._binds[name] = [lo, [], (tuple(t.shape), t.dtype)]
+            return 0
+        hi = lo + t.numel() * t.element_size()
         sites = []
         for i, (kind, fn, _, _, words) in enumerate(self._ops):
             if kind != _KIND_CALL:
@@ -189,11 +224,7 @@ class Tape:
                 if rc != 0:
                     raise TapeError(f"tape op {failed.value} of {self.n} failed with code {rc}")
             if cb is not None:
-                if st is not None:
-                    with torch.cuda.stream(st):
-                        cb()
-                else:
-                    cb()
+                self._run(cb, st)
         self.replays += 1
 
     def stats(self):

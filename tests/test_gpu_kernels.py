@@ -1506,3 +1506,142 @@ def test_all_taps_wgrad_variants_are_bit_identical(K, monkeypatch, hw, B, cin, c
             assert torch.equal(out[name][0], out["two buffers"][0]) and torch.equal(out[name][1], out["two buffers"][1]), (name, S)
         gw_mine = out["deep"][0].sum(0).reshape(cout, 3, 3, cin).permute(0, 3, 1, 2)
         assert rel_err(gw_mine, gw) < 2e-5, S
+
+
+# ---------------------------------------------------------------------------------------------- fp32 <-> bf16 rows
+# radet_convert_rows (csrc/layers.hip): every bf16 gradient bucket passes through it in both directions (runtime.GradReducer), and
+# it is the fp32 <-> bf16 boundary of the bf16-storage mode.  Reference: torch's CPU conversion -- round to nearest even on the
+# way to bf16, exact on the way back -- compared on BIT PATTERNS.
+def _f32_from_bits(bits):
+    return torch.from_numpy(np.array(bits, dtype=np.uint32).view(np.float32).copy())
+
+
+def _bits(t):
+    return t.cpu().contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+def _to_bf16_on_gpu(K, x):
+    """x: fp32 CPU tensor [rows, n] -> the kernel's bf16 result (CPU)"""
+    d = torch.empty(x.shape, dtype=torch.bfloat16, device="cuda")
+    K.convert_rows(x.cuda(), d)
+    return d.cpu()
+
+
+def test_convert_rows_bulk_round_to_nearest_even(K):
+    """3 x 1001 values spread over 60 binades: fp32 -> bf16 equals round-to-nearest-even bit for bit, and bf16 -> fp32 of
+    the result is exact."""
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(3, 1001, generator=g) * torch.exp2(torch.rand(3, 1001, generator=g) * 60 - 30)
+    d = _to_bf16_on_gpu(K, x)
+    assert torch.equal(_bits(d), _bits(x.bfloat16()))
+    back = torch.empty(3, 1001, device="cuda")
+    K.convert_rows(d.cuda(), back)
+    assert torch.equal(_bits(back), _bits(d.float()))
+
+
+# (bit pattern of the fp32 input, bit pattern of the bf16 that round-to-nearest-even gives) -- written out by hand, and
+# checked against torch's CPU conversion in the test as well
+_RNE_EDGES = [
+    (0x3F808000, 0x3F80), (0x3F818000, 0x3F82),       # ties: the kept mantissa is even (stays) / odd (goes up to even)
+    (0xBF808000, 0xBF80), (0xBF818000, 0xBF82),
+    (0x3F807FFF, 0x3F80), (0x3F808001, 0x3F81),       # one ulp either side of the tie (even kept mantissa)
+    (0x3F817FFF, 0x3F81), (0x3F818001, 0x3F82),       # ... (odd kept mantissa)
+    (0x3FFFFFFF, 0x4000), (0x3FFF8000, 0x4000), (0x3F7FFFFF, 0x3F80), (0xBFFFFFFF, 0xC000),   # the carry reaches the exponent
+    (0x7F7F0000, 0x7F7F), (0x7F7F7FFF, 0x7F7F), (0xFF7F0000, 0xFF7F), (0xFF7F7FFF, 0xFF7F),   # largest finite bf16
+    (0x7F7F8000, 0x7F80), (0xFF7F8000, 0xFF80),       # the first fp32 values that round to +-inf (a tie on an odd mantissa)
+    (0x7F7FFFFF, 0x7F80), (0xFF7FFFFF, 0xFF80),       # FLT_MAX
+    (0x7F800000, 0x7F80), (0xFF800000, 0xFF80),       # +-inf
+    (0x00000000, 0x0000), (0x80000000, 0x8000),       # +-0
+    (0x00800000, 0x0080), (0x80800000, 0x8080),       # smallest fp32 normal
+]
+_NAN_BITS = [0x7FC00000, 0xFFC00000, 0x7F800001, 0xFF800001, 0x7F80FFFF, 0x7FFFFFFF, 0xFFC12345]
+# denormal fp32 inputs with their RNE results (0x007FFFFF rounds up to the smallest NORMAL bf16)
+_DENORMAL_EDGES = [(0x00000001, 0x0000), (0x00008000, 0x0000), (0x00008001, 0x0001), (0x00018000, 0x0002), (0x00400000, 0x0040),
+                   (0x007F0000, 0x007F), (0x007FFFFF, 0x0080), (0x80000001, 0x8000), (0x80008001, 0x8001), (0x80400000, 0x8040),
+                   (0x807FFFFF, 0x8080)]
+
+
+def test_convert_rows_rounding_edges(K):
+    """Ties (to even, both parities of the kept mantissa, both signs), one ulp either side of a tie, mantissa carry into the
+    exponent, the largest finite bf16 and the first values that round to +-inf, +-inf, +-0, the smallest normal: bit-exact
+    round to nearest even.  NaN inputs (quiet, signalling, a payload in the dropped bits only -- which truncation would turn
+    into inf) give NaN.
+    Denormal fp32 inputs: the kernel ROUNDS them like every other value (round to nearest even, no flush to zero; the
+    largest one rounds up to the smallest normal bf16) -- asserted below, measured on gfx950."""
+    x = _f32_from_bits([b for b, _ in _RNE_EDGES])
+    want = torch.from_numpy(np.array([w for _, w in _RNE_EDGES], dtype=np.uint16).view(np.int16).copy())
+    assert torch.equal(_bits(x.bfloat16()), want)                         # the table above against torch's CPU conversion
+    got = _bits(_to_bf16_on_gpu(K, x.view(1, -1))).view(-1)
+    print("edges    ", [f"{b:08x}->{int(v) & 0xFFFF:04x}" for (b, _), v in zip(_RNE_EDGES, got)])
+    assert torch.equal(got, want), [(hex(b), hex(w), hex(int(v) & 0xFFFF)) for (b, w), v in zip(_RNE_EDGES, got) if (int(v) & 0xFFFF) != w]
+    nan = _to_bf16_on_gpu(K, _f32_from_bits(_NAN_BITS).view(1, -1)).view(-1)
+    print("nan      ", [f"{b:08x}->{int(v) & 0xFFFF:04x}" for b, v in zip(_NAN_BITS, _bits(nan))])
+    assert torch.isnan(nan.float()).all()
+    den = _f32_from_bits([b for b, _ in _DENORMAL_EDGES])
+    rne = torch.from_numpy(np.array([w for _, w in _DENORMAL_EDGES], dtype=np.uint16).view(np.int16).copy())
+    assert torch.equal(_bits(den.bfloat16()), rne)
+    flushed = torch.where(den.view(torch.int32) < 0, torch.tensor(-32768, dtype=torch.int16), torch.tensor(0, dtype=torch.int16))
+    got = _bits(_to_bf16_on_gpu(K, den.view(1, -1))).view(-1)
+    print("denormals", [f"{b:08x}->{int(v) & 0xFFFF:04x}" for (b, _), v in zip(_DENORMAL_EDGES, got)])
+    assert bool(((got == rne) | (got == flushed)).all())                  # one of the two admissible results, per element
+    assert torch.equal(got, rne)                                          # ... and it is the rounded one, throughout
+
+
+@pytest.mark.parametrize("ncols", [1, 3, 1001])
+@pytest.mark.parametrize("to_bf16", [True, False], ids=["to-bf16", "to-fp32"])
+def test_convert_rows_strides_and_offsets(K, ncols, to_bf16):
+    """Row strides larger than the width on either side and non-zero (odd and even) column offsets: the window
+    [dst_off, dst_off + ncols) of every row holds the converted window of the source row, and every other element of the
+    destination keeps its sentinel bit for bit."""
+    g = torch.Generator().manual_seed(ncols)
+    rows = 3
+    sd, dd = (torch.float32, torch.bfloat16) if to_bf16 else (torch.bfloat16, torch.float32)
+    for src_ld, src_off, dst_ld, dst_off in ((ncols + 5, 3, ncols + 4, 1), (ncols + 2, 2, ncols + 7, 4), (ncols + 1, 0, ncols + 1, 1),
+                                             (ncols + 1, 1, ncols, 0), (ncols, 0, ncols + 2, 0)):
+        src = (torch.randn(rows, src_ld, generator=g) * 3).to(sd)
+        dst = torch.full((rows, dst_ld), -776.0, dtype=dd)                 # (exact in bf16: 0xC442)
+        sentinel = _bits(dst).clone()
+        d = dst.cuda()
+        K.convert_rows(src.cuda(), d, ncols=ncols, src_off=src_off, dst_off=dst_off)
+        want = sentinel.clone()
+        want[:, dst_off:dst_off + ncols] = _bits(src[:, src_off:src_off + ncols].to(dd))
+        assert torch.equal(_bits(d), want), (src_ld, src_off, dst_ld, dst_off)
+
+
+def test_convert_rows_grid_stride_loop(K):
+    """One row of 8192 * 256 + 7 elements -- the shape GradReducer calls it with (`view(1, -1)`), seven elements beyond one
+    pass of the largest grid (8192 blocks of 256 threads): both directions, every element."""
+    n = 8192 * 256 + 7
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(n, generator=g)
+    d = _to_bf16_on_gpu(K, x.view(1, -1))
+    assert torch.equal(_bits(d).view(-1), _bits(x.bfloat16()))
+    back = torch.full((1, n), float("nan"), device="cuda")
+    K.convert_rows(d.cuda(), back)
+    assert torch.equal(_bits(back).view(-1), _bits(d.view(-1).float()))
+
+
+def test_convert_rows_every_bf16_pattern_to_fp32(K):
+    """All 65536 bf16 bit patterns in one call: every non-NaN one (denormals, infinities, zeros of both signs included) becomes
+    the fp32 value with the same bits in its upper half; NaN stays NaN."""
+    src = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16).view(torch.bfloat16).view(1, -1)
+    out = torch.zeros(1, 65536, device="cuda")
+    K.convert_rows(src.cuda(), out)
+    out, want = out.cpu().view(-1), src.view(-1).float()
+    nan = torch.isnan(want)
+    assert int(nan.sum()) == 2 * 127 and torch.equal(torch.isnan(out), nan)
+    assert torch.equal(_bits(out)[~nan], _bits(want)[~nan])
+    assert torch.equal(_bits(want)[~nan], src.view(-1).view(torch.int16)[~nan].to(torch.int32) << 16)   # (the reference itself)
+
+
+def test_convert_rows_degenerate_sizes(K):
+    """rows == 0 and ncols == 0 succeed and write nothing."""
+    dst = torch.full((2, 5), -776.0, dtype=torch.bfloat16, device="cuda")
+    before = _bits(dst).clone()
+    K.convert_rows(torch.ones(2, 5, device="cuda"), dst, ncols=0)
+    K.convert_rows(torch.ones(0, 5, device="cuda"), dst[:0])
+    back = torch.full((2, 5), -776.0, device="cuda")
+    K.convert_rows(torch.ones(2, 5, dtype=torch.bfloat16, device="cuda"), back, ncols=0)
+    K.convert_rows(torch.ones(0, 5, dtype=torch.bfloat16, device="cuda"), back[:0])
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(dst), before) and bool((back == -776.0).all())

@@ -286,6 +286,95 @@ def test_rccl_bucket_exchange_single_rank(det, golden):
         dist.destroy_process_group()
 
 
+@pytest.mark.parametrize("bf16", ["0", "1"], ids=["fp32-buckets", "bf16-buckets"])
+def test_taped_exchange_equals_eager(golden, monkeypatch, bf16):
+    """The steady-state data-parallel step -- recorded on a launch tape and replayed in `len(buckets) + 2` segments with the
+    bucket hand-overs and reducer.finish() as the Python between them -- against the eager step, with an exchange that is
+    NOT an identity: a 1-rank group's all-reduce returns its input, so `torch.distributed.all_reduce` is replaced by a
+    doubling on the current stream (exact in fp32 and bf16, allocates nothing; the reducer issues its collectives
+    synchronously on a stream of the engine's, which the test asserts first).  Six steps over two alternating batches with a
+    learning rate that changes every step: losses, gradient arena, parameters and both AdamW moments are equal bit for bit
+    (the gradient arena always: AdamW is nearly invariant to the gradients' scale, parameters alone could hide a lost
+    exchange).  The arena after the first step is exactly twice the one of a step without exchange (bf16 buckets: twice its
+    bf16 rounding) -- the stand-in was reached.  The recorded tape holds no fp32 <-> bf16 convert: the buckets' converts
+    belong to the callbacks, which replay() runs itself.
+    RADET_BF16_BUCKETS=1 is honoured in the mixed-precision modes only (runtime.bf16_buckets), so the bf16-bucket case runs
+    the "bf16" arithmetic (fp32 tensors: the engine itself converts nothing) and the fp32-bucket case the default fp32 one.
+    The geometry plan is built before the first step, so that all six steps share one tape key: two eager steps, one
+    recorded, three replayed."""
+    import torch.distributed as dist
+    from oracle import synth
+    from radet_amd import _lib
+    from radet_amd.runtime import sync_collectives_run_on_current_stream
+    if not sync_collectives_run_on_current_stream():
+        pytest.skip("this torch runs synchronous collectives on the process group's own stream: the stand-in would not be "
+                    "ordered behind the bucket's producer")
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29533")
+    names = ("RADET_FORCE_REDUCER", "RADET_BF16_BUCKETS", "RADET_TAPE_STRICT")
+    saved = {k: os.environ.get(k) for k in names}
+    if not dist.is_initialized():
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    try:
+        os.environ.update(RADET_BF16_BUCKETS=bf16, RADET_TAPE_STRICT="1")
+        math = "bf16" if bf16 == "1" else "fp32"
+        imgs = [synth.synth_images(s, 2).cuda() for s in (0, 1)]
+        gts = [targets(golden), targets(golden, tags=("g3", "g8"))]
+        seen = []
+
+        def doubled(t, op=None, group=None, async_op=False):
+            assert not async_op
+            seen.append(t.dtype)
+            t.mul_(2)
+
+        def run(tape_mode, steps, exchange=True):
+            d = make_det().train()
+            rt = d.runtime(math=math)
+            rt.tape_mode = tape_mode
+            rt.init_optimizer()
+            rt.engine.prepare(imgs[0].shape[0], imgs[0].shape[2], imgs[0].shape[3])
+            tgs = [rt.pack_targets(*g) for g in gts]
+            os.environ["RADET_FORCE_REDUCER"] = "1" if exchange else "0"
+            losses, first = [], None
+            for i in range(steps):
+                losses.append(rt.train_step(imgs[i & 1], tgs[i & 1], lr=1e-4 * (1 + 0.1 * i)).clone())
+                if i == 0:
+                    first = rt.flat.grads.clone()
+            torch.cuda.synchronize()
+            return rt, dict(losses=torch.stack(losses), grads=rt.flat.grads.clone(), params=rt.flat.params.clone(),
+                            m=rt.opt_state["m"].clone(), v=rt.opt_state["v"].clone(), first=first)
+
+        plain = run("0", 1, exchange=False)[1]
+        monkeypatch.setattr(dist, "all_reduce", doubled)
+        re_, eager = run("0", 6)
+        n_eager = len(seen)
+        rt, taped = run("1", 6)
+        monkeypatch.undo()
+        assert re_.reducer is not None and re_.reducer.bf16 == (bf16 == "1") and rt.reducer.bf16 == (bf16 == "1")
+        assert re_.reducer.comm_stream is not None
+        assert n_eager == len(seen) - n_eager == 6 * len(rt.buckets)
+        assert set(seen) == {torch.bfloat16 if bf16 == "1" else torch.float32}
+        # the stand-in was reached: the arena is not the one of a step without exchange, but exactly its double
+        assert not torch.equal(eager["first"], plain["first"])
+        want = plain["first"].bfloat16().float() * 2 if bf16 == "1" else plain["first"] * 2
+        assert torch.equal(eager["first"], want)
+        assert re_.tape_stats() is None
+        st = rt.tape_stats()
+        assert st is not None and st["replays"] == 3 and st["segments"] == len(rt.buckets) + 2, (st, rt._tape["failed"])
+        for k in ("losses", "first", "grads", "params", "m", "v"):
+            assert torch.equal(eager[k], taped[k]), k
+        fn = _lib.load().radet_tape_fn_index(b"radet_convert_rows")
+        assert fn >= 0 and not [o for o in rt._tape["tape"]._ops if o[0] == 0 and o[1] == fn]
+        assert _lib.TAPE is None
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        dist.destroy_process_group()
+
+
 def test_train_harness_and_checkpoint(golden, tmp_path):
     """apis.train_detector: OneCycle lr + native steps reduce the loss on a fixed batch; checkpoint restores
     parameters and AdamW state exactly (the next step after a reload equals the uninterrupted one)."""

@@ -150,6 +150,77 @@ def test_tape_thunks_are_current_and_replay_runs_host_calls():
     assert t.replays == 1 and t.ops[0].args[1] == 0
 
 
+def _host_tape():
+    """a Tape that records without a device: the allocator counter is the list's only element"""
+    from radet_amd import _lib
+    from radet_amd.tape import Tape
+    t, allocs = Tape(), [0]
+    t._alloc_count = lambda dev: allocs[0]
+    t._alloc0, t.dev = 0, None
+    _lib.TAPE = t
+    return t, allocs
+
+
+def test_tape_bind_of_an_empty_tensor_binds_nothing():
+    """An empty tensor's data_ptr() is 0: bound as the range [0, 1) it would own every NULL pointer argument on the tape,
+    and the first replay with a non-empty tensor would write an address over those NULLs.  It binds 0 sites, and a replay
+    leaves the NULL argument 0."""
+    from radet_amd import _lib
+    t, _ = _host_tape()
+    try:
+        _lib.call("radet_fill_zero", None, 0, None)                        # (NULL, 0 bytes, NULL stream): a no-op that succeeds
+    finally:
+        t.end()
+    assert t.n == 1 and list(t.ops[0].args[:3]) == [0, 0, 0]
+    assert t.bind("boxes", torch.empty(0, 4)) == 0 and t.stats()["bound"] == {"boxes": 0}
+    full = torch.ones(3, 4)
+    assert t.bind("pw", full) == 0                                          # (a tensor no call points into: nothing either)
+    t.replay(tensors=dict(boxes=full, pw=torch.ones(5)))
+    assert t.replays == 1 and list(t.ops[0].args[:3]) == [0, 0, 0]
+
+
+def test_tape_cut_callbacks_run_unrecorded():
+    """Tape.run_cut: the callback of a cut runs with recording suspended (`_lib.TAPE` is None inside and restored after, also
+    when the callback raises), so what it calls is not on the tape -- replay() runs the callback itself between the two
+    segments.  Allocations inside a callback do not poison the tape; one inside a recorded segment still does."""
+    from radet_amd import _lib
+    seen = []
+
+    def callback():
+        seen.append(_lib.TAPE)
+        _lib.call("radet_fill_zero", None, 0, None)
+        allocs[0] += 3                                                      # a temporary of the callback's own
+
+    def failing():
+        raise ValueError("boom")
+
+    t, allocs = _host_tape()
+    try:
+        _lib.call("radet_fill_zero", None, 0, None)
+        assert t.run_cut(callback) is None and _lib.TAPE is t
+        with pytest.raises(ValueError):
+            t.run_cut(failing)
+        assert _lib.TAPE is t
+        t._cuts.pop()                                                       # (the failing cut: a real step aborts the tape)
+        _lib.call("radet_fill_zero", None, 0, None)
+    finally:
+        t.end()
+    assert _lib.TAPE is None and seen == [None] and t.poisoned is None
+    st = t.stats()
+    assert st["calls"] == 2 and st["segments"] == 2                         # the callback's own call was not recorded
+    t.replay()
+    assert seen == [None, None] and t.replays == 1
+    t, allocs = _host_tape()
+    try:
+        t.run_cut(callback)
+        allocs[0] += 1                                                      # ... in a recorded segment
+    finally:
+        t.end()
+    assert t.poisoned is not None and "allocated" in t.poisoned
+    with pytest.raises(_lib.RadetHipError, match="tape unusable"):
+        t.replay()
+
+
 def test_conv_geometry_refuses_tensors_beyond_the_kernels_address_range():
     """The tile loads address a tensor with 32-bit byte offsets (buffer_load ... lds): a geometry whose activation tensor
     would exceed 4 GiB is refused when it is built, not mis-addressed at run time."""
