@@ -650,6 +650,36 @@ int radet_paste_maps(const void* maps, size_t map_px, int is_f64, const int* des
 int radet_warp_affine_u8(const uint8_t* src, size_t src_px, uint8_t* dst, size_t dst_px, const int* desc, int nimg, int max_px,
                          int channels, void* stream);
 
+/* ---- CutOut (csrc/cutout.hip; radet/datasets/pipelines/transforms.py:1734-1804): the holes of nimg images filled in place
+ *      in one launch.  desc (device) = nimg rows of CUTOUT_DESC_INTS ints:
+ *      [CUTOUT_DESC_OFF] radet_cutout_u8: pixel offset of the image in the packed u8 HWC buffer; radet_cutout_f32: index of
+ *      the image in out f32 [nbatch,3,Hp,Wp], [CUTOUT_DESC_H], [CUTOUT_DESC_W], [CUTOUT_DESC_FILL] fill = c0 | c1 << 8 |
+ *      c2 << 16 in the u8 image's channel order (BGR), [CUTOUT_DESC_FIRST] the image's first row of `holes`,
+ *      [CUTOUT_DESC_COUNT] the number of its rows, [CUTOUT_DESC_FLAGS] (CUTOUT_SKIP: the image is left alone; f32 only:
+ *      CUTOUT_FLIP the sample is flipped horizontally, CUTOUT_TO_RGB the planes are RGB), one spare word.
+ *      holes (device) = nholes rows {x1, y1, x2, y2}: half-open rectangles in the coordinates of the unflipped image, of
+ *      any values; each is clipped to the image.  max_holes = the largest count, max_area = the largest hole's pixels.
+ *      radet_cutout_u8 stores the fill bytes; radet_cutout_f32 stores per plane what radet_augment_finish writes for a u8
+ *      pixel equal to the fill with no blend flag set ((q - m) * s in fp32), at columns w - x2 .. w - x1 - 1 of a flipped
+ *      sample.  Nothing outside the holes is written.  A row whose image does not lie inside the buffer (img_px pixels;
+ *      nbatch images of Hp x Wp) or whose holes do not lie inside the table is not written.  channels must be 3;
+ *      nimg, max_holes <= 65535. */
+#define CUTOUT_DESC_INTS 8
+#define CUTOUT_DESC_OFF 0
+#define CUTOUT_DESC_H 1
+#define CUTOUT_DESC_W 2
+#define CUTOUT_DESC_FILL 3
+#define CUTOUT_DESC_FIRST 4
+#define CUTOUT_DESC_COUNT 5
+#define CUTOUT_DESC_FLAGS 6
+#define CUTOUT_SKIP 1
+#define CUTOUT_FLIP 2
+#define CUTOUT_TO_RGB 4
+int radet_cutout_u8(uint8_t* img, size_t img_px, const int* desc, int nimg, const int* holes, int nholes, int max_holes,
+                    int max_area, int channels, void* stream);
+int radet_cutout_f32(float* out, int nbatch, int Hp, int Wp, const int* desc, int nimg, const int* holes, int nholes, int max_holes,
+                     int max_area, float m0, float m1, float m2, float s0, float s1, float s2, void* stream);
+
 /* ---- in-memory frames through the test pipeline in one launch (csrc/preprocess.hip): LoadImageFromWebcam -> Resize ->
  *      Normalize -> Pad (radet/datasets/pipelines/loading.py:88 as radet/apis/inference.py:97-102 uses it).  nimg u8 HWC BGR
  *      frames of any, mixed sizes -> out f32 [nimg,3,Hp,Wp]: what radet_resize_linear_u8 followed by radet_augment_finish

@@ -106,6 +106,8 @@ SIGNATURES = {
     "radet_resize_linear_u8_src_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_resize_linear_f": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_warp_affine_u8": (_i, [_p, _sz, _p, _sz, _p, _i, _i, _i, _p]),
+    "radet_cutout_u8": (_i, [_p, _sz, _p, _i, _p, _i, _i, _i, _i, _p]),
+    "radet_cutout_f32": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p]),
     "radet_gaussian_blur9_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "radet_sobel_edge": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "radet_stem_conv_bn_relu_h": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),

@@ -26,7 +26,11 @@ radet_rle_masks_src_window in the place of their plain counterparts); no canvas 
 Affine augmentation (Rotate, Shear, Translate, or one AutoAugment over them, directly after Resize): the stages plan boxes
 and leave forward matrices in s["affine"]; run() warps the resized frames and the resized, unflipped masks once per
 entry (radet_warp_affine_u8: cv2.warpAffine's classic fixed-point bilinear path), in front of the merge and the flip.
+CutOut (in that block, bare or in AutoAugment policies, or behind the photometric stages in front of RandomFlip): the stage
+plans its holes; run() fills them per entry rank on the packed u8 frames (radet_cutout_u8, next to the warp launch of that
+rank) or, for the late position, in the finished f32 batch (radet_cutout_f32 after radet_augment_finish).
 Options the RADet configs do not use raise NotImplementedError."""
+import collections
 import glob
 import math
 import os
@@ -48,10 +52,11 @@ DEFAULT_META_KEYS = ("filename", "ori_filename", "ori_shape", "img_shape", "pad_
                      "flip_direction", "img_norm_cfg")
 # stage order of the device part (a pipeline lists a subsequence of it; MultiScaleFlipAug's transforms sit in its place)
 _ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Expand", "MinIoURandomCrop", "Resize", "RandomCrop", "Affine", "RandomBackground", "CosyPoseAug", "RandomHSV",
-          "RandomNoise", "RandomSmooth", "RandomFlip", "GenerateDistanceMap", "LabelAssignment", "Normalize", "Pad",
+          "RandomNoise", "RandomSmooth", "CutOut", "RandomFlip", "GenerateDistanceMap", "LabelAssignment", "Normalize", "Pad",
           "DefaultFormatBundle", "ImageToTensor", "Collect")
 _ZOOM = ("Expand", "MinIoURandomCrop")                       # the source-window stages
 _AFFINE = ("Rotate", "Shear", "Translate", "AutoAugment")    # the warp stages: one block in the "Affine" slot of _ORDER
+_BLOCK = _AFFINE + ("CutOut",)                               # what may stand in that block (a CutOut elsewhere is a late one)
 _MIX = ("RandomHSV", "RandomNoise", "RandomSmooth")          # the mixpbr stages: aug_hsv_noise + aug_box
 _COSY_ORDER = ("PillowBlur", "PillowSharpness", "PillowContrast", "PillowBrightness", "PillowColor")
 # flags of a params row (include/radet_hip.h)
@@ -529,6 +534,22 @@ class RandomCrop:
 # ---------------------------------------------------------------------------------------------------- affine
 _MAX_LEVEL = 10
 _AFFINE_MAX_ENTRIES = 4
+CUTOUT_MAX_HOLES = 64
+
+
+CutHoles = collections.namedtuple("CutHoles", "rects fill")   # one fired CutOut: int32 [n, 4] rows {x1, y1, x2, y2}, fill bytes (BGR)
+
+
+def _block_entries(s):
+    """the number of entries (fired warp and CutOut stages) of the sample's block so far"""
+    return len(s["block_ops"]) if "block_ops" in s else len(s.get("affine", ()))
+
+
+def _block_list(s):
+    """the entries of the sample's block in the order they ran: (matrix, fill) of s["affine"] and CutHoles of s["cutout"]"""
+    if "block_ops" not in s:
+        return list(s.get("affine", ()))
+    return [s["affine" if kind == "warp" else "cutout"][j] for kind, j in s["block_ops"]]
 
 
 def rotation_matrix(center, angle, scale):
@@ -593,8 +614,10 @@ class _AffineStage:
 
     def _record(self, s, matrix, h, w):
         entries = s.setdefault("affine", [])
-        if len(entries) >= _AFFINE_MAX_ENTRIES:
+        if _block_entries(s) >= _AFFINE_MAX_ENTRIES:
             _refuse(f"more than {_AFFINE_MAX_ENTRIES} affine stages firing on one sample")
+        if "block_ops" in s:                             # (a CutOut fired before this stage: the order across kinds counts)
+            s["block_ops"].append(("warp", len(entries)))
         if not K.warp_fits(K.invert_affine(matrix), h, w):
             _refuse(f"{type(self).__name__}: matrix {matrix.tolist()} on an image of {h} x {w} (its inverse leaves the warp "
                     f"kernel's 32-bit fixed point)")
@@ -749,12 +772,92 @@ class Translate(_AffineStage):
 
 
 _AFFINE_STAGES = ("Rotate", "Shear", "Translate")
+_POLICY_STAGES = _AFFINE_STAGES + ("CutOut",)
+
+
+def _fill_in_arg(fill_in):
+    """fill_in of CutOut -> three bytes: the reference assigns it into the u8 image, which would wrap or truncate silently
+    anything that is not an integer in [0, 255]"""
+    ok = isinstance(fill_in, (tuple, list)) and len(fill_in) == 3 and all(
+        isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and 0 <= v <= 255 and v == int(v) for v in fill_in)
+    if not ok:
+        raise ValueError(f"CutOut: fill_in is three integers in [0, 255] in the image's channel order (BGR), got {fill_in!r}")
+    return tuple(int(v) for v in fill_in)
+
+
+@PIPELINES.register_module()
+class CutOut:
+    """The reference's CutOut (transforms.py:1734-1804), planned: the draws on the sample's NumPy generator in the reference's
+    order -- randint(n_holes[0], n_holes[1] + 1) holes, per hole randint(0, w), randint(0, h), randint(0, len(candidates)) --
+    on the h x w of s["img_shape"]; a hole is the candidate as given (cutout_shape: (w, h) in pixels) or int(ratio * w),
+    int(ratio * h) (cutout_ratio), from (x1, y1) to clip(x1 + cw, 0, w), clip(y1 + ch, 0, h).  Boxes, labels and masks are
+    untouched, as in the reference.  No pixel is touched here.  In the block after Resize (next to Rotate / Shear /
+    Translate, bare or in an AutoAugment policy) a stage that drew holes is one entry of the block: it appends CutHoles(int32
+    [n, 4] rows {x1, y1, x2, y2}, fill bytes in BGR) to s["cutout"] and ("cutout", its index there) to s["block_ops"], the
+    list of the block's entries in the order they ran (("warp", index into s["affine"]) for the warp stages; s["affine"]
+    itself keeps holding the warp entries only).  Behind the photometric stages (`late`, set by ImagePipeline) the holes go
+    to s["cutout_late"] = (rows, fill) and are cut into the finished batch.  A stage that drew no hole records nothing."""
+    late = False
+
+    def __init__(self, n_holes, cutout_shape=None, cutout_ratio=None, fill_in=(0, 0, 0)):
+        if (cutout_shape is None) == (cutout_ratio is None):
+            raise ValueError("CutOut: either cutout_shape or cutout_ratio is given, not both")
+        if isinstance(n_holes, (tuple, list)):
+            if not (len(n_holes) == 2 and all(isinstance(v, (int, np.integer)) for v in n_holes) and 0 <= n_holes[0] < n_holes[1]):
+                raise ValueError(f"CutOut: n_holes is an int or (min, max) with 0 <= min < max, got {n_holes!r}")
+            n_holes = (int(n_holes[0]), int(n_holes[1]))
+        elif isinstance(n_holes, (int, np.integer)) and not isinstance(n_holes, bool) and n_holes >= 0:
+            n_holes = (int(n_holes), int(n_holes))
+        else:
+            raise ValueError(f"CutOut: n_holes is an int or (min, max) with 0 <= min < max, got {n_holes!r}")
+        if n_holes[1] > CUTOUT_MAX_HOLES:
+            _refuse(f"CutOut(n_holes={n_holes}) (more than CUTOUT_MAX_HOLES = {CUTOUT_MAX_HOLES} holes per stage)")
+        self.with_ratio = cutout_ratio is not None
+        given = cutout_ratio if self.with_ratio else cutout_shape
+        if not isinstance(given, (list, tuple)):
+            raise ValueError(f"CutOut: cutout_shape / cutout_ratio is a tuple of 2 or a list of such tuples, got {given!r}")
+        candidates = given if isinstance(given, list) else [given]
+        kinds = (int, float, np.integer, np.floating) if self.with_ratio else (int, np.integer)
+        if not candidates or not all(isinstance(c, (tuple, list)) and len(c) == 2 and all(
+                isinstance(v, kinds) and not isinstance(v, bool) for v in c) for c in candidates):
+            raise ValueError(f"CutOut: each candidate is (w, h), {'two numbers' if self.with_ratio else 'two ints'}, got {given!r}")
+        self.n_holes, self.candidates, self.fill_in = n_holes, [tuple(c) for c in candidates], fill_in
+        self.fill = _fill_in_arg(fill_in)
+
+    def draw(self, h, w, nprnd):
+        """the reference's draws on an h x w image -> int32 [n, 4] rows {x1, y1, x2, y2}"""
+        n = nprnd.randint(self.n_holes[0], self.n_holes[1] + 1)
+        rects = np.zeros((n, 4), np.int32)
+        for r in rects:
+            x1 = nprnd.randint(0, w)
+            y1 = nprnd.randint(0, h)
+            cw, ch = self.candidates[nprnd.randint(0, len(self.candidates))]
+            if self.with_ratio:
+                cw, ch = int(cw * w), int(ch * h)
+            r[:] = [x1, y1, np.clip(x1 + cw, 0, w), np.clip(y1 + ch, 0, h)]
+        return rects
+
+    def plan(self, s, rnd, nprnd):
+        if s.get("seg_fields"):
+            _refuse("CutOut on a sample with seg_fields (semantic segmentation maps)")
+        rects = self.draw(int(s["img_shape"][0]), int(s["img_shape"][1]), nprnd)
+        if not len(rects):
+            return
+        if self.late:
+            s["cutout_late"] = CutHoles(rects, self.fill)
+            return
+        if _block_entries(s) >= _AFFINE_MAX_ENTRIES:
+            _refuse(f"more than {_AFFINE_MAX_ENTRIES} affine stages firing on one sample")
+        ops = s.setdefault("block_ops", [("warp", k) for k in range(len(s.get("affine", ())))])
+        holes = s.setdefault("cutout", [])
+        ops.append(("cutout", len(holes)))
+        holes.append(CutHoles(rects, self.fill))
 
 
 @PIPELINES.register_module()
 class AutoAugment:
-    """The reference's AutoAugment (auto_augment.py:45-108) over the affine stages: np.random.choice over the policies on
-    the sample's NumPy generator, then the stages of the chosen policy in order.  s["policy"] = the index drawn."""
+    """The reference's AutoAugment (auto_augment.py:45-108) over the affine stages and CutOut: np.random.choice over the
+    policies on the sample's NumPy generator, then the stages of the chosen policy in order.  s["policy"] = the index drawn."""
 
     def __init__(self, policies):
         if not isinstance(policies, list) or not policies or not all(isinstance(p, list) and p for p in policies):
@@ -763,8 +866,8 @@ class AutoAugment:
             for t in policy:
                 if not isinstance(t, dict) or "type" not in t:
                     raise ValueError("AutoAugment: each augmentation is a dict with the key 'type'")
-                if t["type"] not in _AFFINE_STAGES:
-                    _refuse(f"AutoAugment policy stage {t['type']} (policies hold {_AFFINE_STAGES} only)")
+                if t["type"] not in _POLICY_STAGES:
+                    _refuse(f"AutoAugment policy stage {t['type']} (policies hold {_POLICY_STAGES} only)")
             if len(policy) > _AFFINE_MAX_ENTRIES:
                 _refuse(f"an AutoAugment policy of {len(policy)} stages (at most {_AFFINE_MAX_ENTRIES} affine entries per sample)")
         self.policies = [[dict(t) for t in policy] for policy in policies]
@@ -1109,11 +1212,23 @@ class ImagePipeline:
         if self.frames:
             names[0] = "LoadImageFromFile"
             self._check_frame_pipeline(flat, sample_cache)
-        block = [k for k, n in enumerate(names) if n in _AFFINE]
+        # the block after Resize: the warp stages, and the CutOut stages that stand in one run with them from Resize on (or
+        # from the RandomCrop behind it); a CutOut anywhere else is a late one, which has its own slot of the order
+        start = names.index("Resize") + 1 if "Resize" in names else len(names)
+        start += start < len(names) and names[start] == "RandomCrop"
+        stop = start
+        while stop < len(names) and names[stop] in _BLOCK:
+            stop += 1
+        block = [k for k, n in enumerate(names) if n in _AFFINE or (n == "CutOut" and start <= k < stop)]
+        late = [k for k, n in enumerate(names) if n == "CutOut" and k not in block]
+        if "CutOut" in names and any(isinstance(t, MultiScaleFlipAug) for t in flat):
+            _refuse("CutOut in a MultiScaleFlipAug (test) pipeline")
+        for k in late:
+            flat[k].late = True
         if block:
             self._check_affine(flat, names, block)
-        # (the affine block counts as one stage, "Affine", of the order)
-        slots = ["Affine" if n in _AFFINE else n for k, n in enumerate(names) if k not in block[1:]]
+        # (the block counts as one stage, "Affine", of the order)
+        slots = ["Affine" if k in block else n for k, n in enumerate(names) if k not in block[1:]]
         pos = [(_ORDER.index(n) if n in _ORDER else -1) for n in slots]
         for n in (n for n in names if n in _ZOOM):
             if "Resize" in names and names.index(n) > names.index("Resize"):
@@ -1142,29 +1257,37 @@ class ImagePipeline:
         self.mask_free = dm if dm is not None and not dm.with_gt_mask else None
         if self.mask_free is not None and getattr(dm.distance_transform, "extract_edge_func", None) is not None:
             _refuse("GenerateDistanceMap(extract_edge_func=...) in an image pipeline (a host callback)")
+        if late and self.mask_free is not None:
+            _refuse("a CutOut behind the photometric stages together with GenerateDistanceMap(with_gt_mask=False) (the mask-free "
+                    "crops are cut from the u8 image in front of the blends: they would not see the holes)")
         self.tta = any(isinstance(t, MultiScaleFlipAug) for t in self.transforms)
 
     @staticmethod
     def _check_affine(flat, names, block):
-        """Rotate / Shear / Translate (in any order, repeats allowed, at most 4) or one AutoAugment: one block directly after
-        Resize.  (Seg fields need no check here: LoadAnnotations(with_seg=True) does not build.)"""
+        """Rotate / Shear / Translate / CutOut (in any order, repeats allowed, at most 4) or one AutoAugment over them: one
+        block directly after Resize.  A block without a warp stage is pointwise: it may follow RandomCrop and stand in a
+        pipeline with the zoom stages.  (Seg fields need no check here: LoadAnnotations(with_seg=True) does not build.)"""
         where = f"{[names[k] for k in block]} at positions {block} of {names}"
+        stages = []
+        for t in (flat[k] for k in block):
+            stages += [u for policy in t.transforms for u in policy] if isinstance(t, AutoAugment) else [t]
+        warps = [k for k in block if isinstance(flat[k], _AffineStage)
+                 or (isinstance(flat[k], AutoAugment) and any(isinstance(u, _AffineStage) for p in flat[k].transforms for u in p))]
+        first = names[warps[0]] if warps else names[block[0]]
         if any(isinstance(t, MultiScaleFlipAug) for t in flat):
-            _refuse(f"{names[block[0]]} in a MultiScaleFlipAug (test) pipeline")
-        for other in ("RandomCrop", *_ZOOM):
+            _refuse(f"{first} in a MultiScaleFlipAug (test) pipeline")
+        for other in ("RandomCrop", *_ZOOM) if warps else ():
             if other in names:
-                _refuse(f"{names[block[0]]} together with {other} (a warp composed with a window is left out)")
-        if block != list(range(block[0], block[0] + len(block))) or block[0] == 0 or names[block[0] - 1] != "Resize":
+                _refuse(f"{first} together with {other} (a warp composed with a window is left out)")
+        before = ("Resize",) if warps else ("Resize", "RandomCrop")
+        if block != list(range(block[0], block[0] + len(block))) or block[0] == 0 or names[block[0] - 1] not in before:
             _refuse(f"{where} (the affine stages stand as one block directly after Resize, before RandomBackground)")
         kinds = [names[k] for k in block]
         if "AutoAugment" in kinds and len(kinds) > 1:
             _refuse(f"{where} (bare Rotate / Shear / Translate stages, or one AutoAugment)")
         if len(kinds) > _AFFINE_MAX_ENTRIES:
             _refuse(f"{where} (at most {_AFFINE_MAX_ENTRIES} affine entries per sample)")
-        stages = []
-        for t in (flat[k] for k in block):
-            stages += [u for policy in t.transforms for u in policy] if isinstance(t, AutoAugment) else [t]
-        for t in stages:
+        for t in (t for t in stages if isinstance(t, _AffineStage)):
             # the fixed-point range of the warp kernel, on the largest image the augmentation kernels take
             for m in t.worst_matrices(K.AUG_MAX_W, K.AUG_MAX_W):
                 if not K.warp_fits(K.invert_affine(m), K.AUG_MAX_W, K.AUG_MAX_W):
@@ -1338,23 +1461,68 @@ class ImagePipeline:
 
     @staticmethod
     def _warp_packed(img, entries, offs, hw, dev, channels=3):
-        """The affine entries of a batch applied to its packed images: one radet_warp_affine_u8 launch per entry rank k = 0 ..
-        the longest list - 1, ping-ponging between `img` and one more buffer of its size; an image with fewer than k + 1
-        entries is copied (WARP_SKIP).  entries: per image a list of (forward 2 x 3 matrix, fill); offs / hw: per image its
-        pixel offset and size.  One descriptor upload for all ranks.  Returns the buffer that holds the result."""
-        ranks = max(len(e) for e in entries)
+        """The block entries of a batch applied to its packed images, rank by rank (k = 0 .. the longest list - 1).  entries:
+        per image a list, in the order the entries ran, of (forward 2 x 3 matrix, fill) for a warp or CutHoles(rects, fill)
+        for a CutOut; offs / hw: per image its pixel offset and size.  At rank k: one radet_warp_affine_u8 launch if any
+        image's k-th entry is a warp, ping-ponging between `img` and one more buffer of its size -- an image whose k-th
+        entry is not a warp is copied (WARP_SKIP) --, then one radet_cutout_u8 launch, in place, if any image's k-th entry
+        is a CutOut (the other images are skip rows).  So a hole cut at a lower rank is warped with the image and one cut at
+        a higher rank is axis-aligned.  One descriptor upload for all ranks: the warp rows, then (only when some entry is a
+        CutOut) the CutOut rows and the hole table.  Returns the buffer that holds the result."""
+        ranks, n = max(len(e) for e in entries), len(entries)
         if not ranks:
             return img
-        D = np.zeros((ranks, len(entries), K.WARP_DESC_INTS), np.int32)
+        cut = any(isinstance(x, CutHoles) for e in entries for x in e)
+        W = np.zeros((ranks, n, K.WARP_DESC_INTS), np.int32)
+        D = np.zeros((ranks, n, K.CUTOUT_DESC_INTS), np.int32) if cut else None
+        holes, first, dims = [], 0, []
         for k in range(ranks):
-            for row, e, o, (h, w) in zip(D[k], entries, offs, hw):
-                K.warp_desc_row(row, o, o, h, w, channels, *(e[k] if k < len(e) else (None,)))
-        desc = torch.from_numpy(D).to(dev)
-        cur, other = img, torch.empty_like(img)
-        for k in range(ranks):
-            K.warp_affine_u8(cur, other, desc[k], len(entries), max(h * w for h, w in hw), channels)
-            cur, other = other, cur
+            kth = [(e[k] if k < len(e) else None) for e in entries]
+            for i, (x, o, (h, w)) in enumerate(zip(kth, offs, hw)):
+                K.warp_desc_row(W[k, i], o, o, h, w, channels, *((None,) if x is None or isinstance(x, CutHoles) else x))
+                if isinstance(x, CutHoles):
+                    K.cutout_desc_row(D[k, i], o, h, w, x.fill, first, len(x.rects))
+                    holes.append(np.asarray(x.rects, np.int32).reshape(-1, 4))
+                    first += len(x.rects)
+                elif cut:
+                    K.cutout_desc_row(D[k, i], o, h, w, skip=True)
+            dims.append((any(x is not None and not isinstance(x, CutHoles) for x in kth),
+                         *K.cutout_launch_dims([x.rects if isinstance(x, CutHoles) else None for x in kth], hw)))
+        parts = [W] + ([D, np.concatenate(holes)] if cut else [])
+        up = torch.from_numpy(np.concatenate([a.reshape(-1) for a in parts])).to(dev)
+        wdesc = up[:W.size].view(ranks, n, K.WARP_DESC_INTS)
+        if cut:
+            cdesc, table = up[W.size:W.size + D.size].view(ranks, n, K.CUTOUT_DESC_INTS), up[W.size + D.size:].view(-1, 4)
+        cur, other = img, None
+        for k, (warp, most, area) in enumerate(dims):
+            if warp:
+                other = torch.empty_like(img) if other is None else other
+                K.warp_affine_u8(cur, other, wdesc[k], n, max(h * w for h, w in hw), channels)
+                cur, other = other, cur
+            if most and area:
+                K.cutout_u8(cur, cdesc[k], table, n, most, area)
         return cur
+
+    @staticmethod
+    def _cutout_late(out, planned, hw, dev, mean, stdinv):
+        """the holes of the batch's late CutOut stages cut into the finished f32 batch: one upload, one radet_cutout_f32
+        launch (none when no sample drew a hole of any area)"""
+        B = len(planned)
+        D = np.zeros((B, K.CUTOUT_DESC_INTS), np.int32)
+        holes, first = [], 0
+        for i, (s, (h, w)) in enumerate(zip(planned, hw)):
+            rects, fill = s.get("cutout_late", (None, (0, 0, 0)))
+            if rects is None:
+                K.cutout_desc_row(D[i], i, h, w, skip=True)
+                continue
+            K.cutout_desc_row(D[i], i, h, w, fill, first, len(rects), flip=bool(s.get("flip")), to_rgb=bool(s["img_norm_cfg"]["to_rgb"]))
+            holes.append(np.asarray(rects, np.int32).reshape(-1, 4))
+            first += len(rects)
+        most, area = K.cutout_launch_dims([s["cutout_late"][0] if "cutout_late" in s else None for s in planned], hw)
+        if not (most and area):
+            return
+        up = torch.from_numpy(np.concatenate([D.reshape(-1), np.concatenate(holes).reshape(-1)])).to(dev)
+        K.cutout_f32(out, up[:D.size].view(B, K.CUTOUT_DESC_INTS), up[D.size:].view(-1, 4), B, most, area, mean, stdinv)
 
     def _affine_masks(self, planned, hw, dev, ahw):
         """_masks for a batch in which some sample carries affine entries.  Per group of samples of equal source size,
@@ -1448,10 +1616,12 @@ class ImagePipeline:
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         bg_off = dict(zip(with_bg, bg_offs))
         affine = any(s.get("affine") for s in planned)
-        if affine:
-            if win is not None or swin is not None:
-                raise ValueError("a batch with affine entries and windows (RandomCrop / Expand / MinIoURandomCrop)")
-            img = self._warp_packed(img, [s.get("affine", ()) for s in planned], offs, hw, dev)
+        if affine and (win is not None or swin is not None):
+            raise ValueError("a batch with affine entries and windows (RandomCrop / Expand / MinIoURandomCrop)")
+        entries = [_block_list(s) for s in planned]
+        if any(entries):
+            # (warps and holes in the order each sample's block ran them)
+            img = self._warp_packed(img, entries, offs, hw, dev)
         # Pad(size=): the assigner sees the padded sample -- its masks / maps zero-padded to the fixed size, its points those
         # of that size, which are the head's for every sample of the batch whatever scale was drawn (with Pad(size_divisor=)
         # the points follow img_shape as in the reference)
@@ -1516,6 +1686,8 @@ class ImagePipeline:
             K.augment_vblur(t1, params, t2, B, max_h, max_w)
             K.augment_sharp(t2, params, t1, lsum, B, max_h * max_w)
             K.augment_finish(t1, lsum, params, out, B, Hp, Wp, mean, stdinv)
+        if any("cutout_late" in s for s in planned):
+            self._cutout_late(out, planned, hw, dev, mean, stdinv)
 
         p2g = pw = None
         if self.assigner is not None:

@@ -1759,6 +1759,59 @@ def warp_affine_masks(src, forward):
     return dst
 
 
+# ---------------------------------------------------------------------- CutOut (csrc/cutout.hip)
+CUTOUT_DESC_INTS = 8                                        # include/radet_hip.h
+CUTOUT_SKIP, CUTOUT_FLIP, CUTOUT_TO_RGB = 1, 2, 4
+
+
+def cutout_desc_row(row, off, h, w, fill=(0, 0, 0), first=0, count=0, skip=False, flip=False, to_rgb=False):
+    """fills one int32 [CUTOUT_DESC_INTS] row.  off: the image's pixel offset in the packed u8 buffer (cutout_u8) or its
+    index in the f32 batch (cutout_f32); fill: three bytes in the u8 image's channel order (BGR); first / count: the
+    image's rows of the hole table; flip / to_rgb: cutout_f32 only"""
+    f = tuple(int(v) for v in fill)
+    flags = (CUTOUT_SKIP if skip else 0) | (CUTOUT_FLIP if flip else 0) | (CUTOUT_TO_RGB if to_rgb else 0)
+    row[:] = [off, h, w, f[0] | f[1] << 8 | f[2] << 16, first, count, flags, 0]
+
+
+def cutout_launch_dims(holes_per_image, hw):
+    """(most holes of any image, the largest clipped hole area) of a launch; holes_per_image: per image an int array [n, 4]
+    of {x1, y1, x2, y2} (None: no holes), hw: per image (h, w).  Host arithmetic only."""
+    import numpy as np
+    most = area = 0
+    for r, (h, w) in zip(holes_per_image, hw):
+        if r is None or not len(r):
+            continue
+        r = np.asarray(r, np.int64).reshape(-1, 4)
+        most = max(most, len(r))
+        rw = np.clip(r[:, 2], 0, w) - np.clip(r[:, 0], 0, w)
+        rh = np.clip(r[:, 3], 0, h) - np.clip(r[:, 1], 0, h)
+        area = max(area, int((np.maximum(rw, 0) * np.maximum(rh, 0)).max()))
+    return most, area
+
+
+def cutout_u8(img, desc, holes, n, max_holes, max_area, channels=3):
+    """img: the packed u8 BGR device buffer, changed in place; desc i32 [n, CUTOUT_DESC_INTS] and holes i32 [total, 4] on
+    the device: every hole of every row's image is filled with the row's fill bytes, in one launch (one thread per hole
+    pixel); no byte outside the holes is written"""
+    assert img.dtype == torch.uint8 and img.is_contiguous()
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.numel() >= n * CUTOUT_DESC_INTS
+    assert holes.dtype == torch.int32 and holes.is_contiguous() and holes.numel() % 4 == 0
+    _lib.call("radet_cutout_u8", _ptr(img), C.c_size_t(img.numel() // 3), _ptr(desc), int(n), _ptr(holes), holes.numel() // 4,
+              int(max_holes), int(max_area), int(channels), _stream())
+
+
+def cutout_f32(out, desc, holes, n, max_holes, max_area, mean, stdinv):
+    """out: f32 [B, 3, Hp, Wp] as augment_finish wrote it, changed in place: every hole pixel becomes what augment_finish
+    writes for a u8 pixel equal to the row's fill with no blend active (mean / stdinv: its operands), mirrored for a
+    flipped sample; one launch"""
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[1] == 3
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.numel() >= n * CUTOUT_DESC_INTS
+    assert holes.dtype == torch.int32 and holes.is_contiguous() and holes.numel() % 4 == 0
+    _lib.call("radet_cutout_f32", _ptr(out), int(out.shape[0]), int(out.shape[2]), int(out.shape[3]), _ptr(desc), int(n),
+              _ptr(holes), holes.numel() // 4, int(max_holes), int(max_area), *[float(v) for v in mean],
+              *[float(v) for v in stdinv], _stream())
+
+
 def resize_linear_f(src, sdesc, dst, ddesc, n, max_dst_px):
     _lib.call("radet_resize_linear_f", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(ddesc), n, max_dst_px,
               1 if src.dtype == torch.float64 else 0, _stream())
