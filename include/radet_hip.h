@@ -456,31 +456,30 @@ int radet_gdt(const float* cost, const int* img_desc_dev, int nimg, const int* s
  *      kernel5 (host) = centre tap + 4 taps, BORDER_REFLECT_101, round to nearest even; tmp = 3 floats per pixel), and
  *      the Sobel edge map (3x3 Gaussian, RGB2GRAY, |0.5 d/dx + 0.5 d/dy| / max; gray_ws 1 byte per pixel, max_ws
  *      one word per crop). */
-int radet_resize_linear_u8(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* dst_desc, int ncrop,
-                           int max_dst_px, int channels, void* stream);
+int radet_resize_linear_u8(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* dst_desc, const int* view_desc,
+                           int ncrop, int max_dst_px, int channels, void* stream);
 int radet_resize_linear_f(const void* src, const int* src_desc, void* dst, const int* dst_desc, int ncrop, int max_dst_px,
                           int is_f64, void* stream);
-/* radet_resize_linear_u8 for Resize followed by RandomCrop: only a window of each resized image is computed.  win_desc
- * (device) = ncrop rows of RESIZE_WIN_DESC_INTS ints {packed pixel offset, window h, w, virtual resized Hr, Wr, window
- * origin y0, x0}: the scale factors and taps are those of (src h, w) -> (Hr, Wr), output pixel (y, x) of the row is the
- * virtual pixel (y0 + y, x0 + x) -- bit for bit the full resize, sliced; h * w pixels are written at the offset.  A row
- * whose window is not inside its Hr x Wr image is not written.  max_dst_px = the largest window's pixel count. */
-#define RESIZE_WIN_DESC_INTS 7
-int radet_resize_linear_u8_window(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* win_desc, int ncrop,
-                                  int max_dst_px, int channels, void* stream);
-/* radet_resize_linear_u8 for Expand / MinIoURandomCrop followed by Resize: the image that is resized is a window of the
- * source, given in the source's own coordinates; it may overhang the source or miss it, and what lies outside reads as a
- * fill colour (Expand's canvas, which is never made).  src_desc as above; win_desc (device) = ncrop rows of
- * RESIZE_SRC_WIN_DESC_INTS ints {packed pixel offset of the output, output Hr, Wr, window origin wy0, wx0 (may be negative),
- * window wh, ww, fill = c0 | c1 << 8 | c2 << 16 in the source's channel order (channels == 1: c0)}.  Taps and coefficients
- * are those of a wh x ww image resized to Hr x Wr (the edge clamp is at the window's border); each tap is read at
- * (wy0 + ty, wx0 + tx) of the source when that lies inside it and is the fill otherwise: bit for bit "paste the source on
- * the filled canvas, slice the window, radet_resize_linear_u8".  Hr * Wr pixels are written at the offset.  A row with
- * Hr, Wr, wh or ww <= 0, an empty source, or wy0 + wh / wx0 + ww beyond int is not written.  max_dst_px = the largest
- * output's pixel count. */
-#define RESIZE_SRC_WIN_DESC_INTS 8
-int radet_resize_linear_u8_src_window(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* win_desc, int ncrop,
-                                      int max_dst_px, int channels, void* stream);
+/* The view row: per-image / per-mask geometry of radet_resize_linear_u8, radet_mask_transform and radet_rle_masks.
+ * view_desc (device, may be NULL) = one row per image or mask of RADET_VIEW_INTS ints
+ *      {Hr, Wr, wy0, wx0, wh, ww, oy, ox, h, w, flip, fill}:
+ * take the wh x ww window at (wy0, wx0) of the source, in the source's own coordinates (it may overhang the source or miss
+ * it; what lies outside reads as the fill for images, as 0 for masks), resize it to a virtual Hr x Wr, and write the h x w
+ * window at (oy, ox) of that.  view_desc == NULL is the whole source to the whole output, from the scalar arguments.
+ * Resize + RandomCrop sets (oy, ox, h, w); Expand / MinIoURandomCrop + Resize set (wy0, wx0, wh, ww, fill); no canvas and
+ * no full-size resized image is ever made.  fill = c0 | c1 << 8 | c2 << 16 in the source's channel order (images only),
+ * flip as radet_mask_transform's (bitmap masks only).
+ *   images: taps and coefficients are those of a wh x ww image resized to Hr x Wr at output pixel (oy + y, ox + x) (the
+ *      edge clamp is at the window's border); each tap is read at (wy0 + ty, wx0 + tx) of the source or is the fill: bit
+ *      for bit "paste the source on the filled canvas, slice, radet_resize_linear_u8, slice".  dst_desc stays {pixel
+ *      offset, h, w}, max_dst_px the largest h * w.
+ *   masks: dst[g][y][x] = y < h && x < w ? norm(S(wy0 + nn(oy + flip_y(y)), wx0 + nn(ox + flip_x(x)))) : pad_val, nn over
+ *      the wh x ww grid resized to Hr x Wr, S = src[g] inside the Hs x Ws source and 0 outside it, the flip inside the
+ *      h x w window (it follows the crop), norm_max still the maximum of the whole source mask.
+ *   A bad row has Hr, Wr, wh or ww <= 0, wy0 + wh or wx0 + ww beyond int, an output window that is not inside Hr x Wr, or
+ *      (masks) h > Hd or w > Wd, or (images) h, w other than its dst_desc row's or an empty source.  An image with a bad
+ *      row is not written; a mask with a bad row is pad_val only. */
+#define RADET_VIEW_INTS 12
 int radet_gaussian_blur9_u8(const uint8_t* src, const int* desc, uint8_t* dst, float* tmp, const float* kernel5, int ncrop,
                             int max_px, void* stream);
 int radet_sobel_edge(const uint8_t* src, const int* desc, float* edge, uint8_t* gray_ws, uint32_t* max_ws, int ncrop,
@@ -492,31 +491,9 @@ int radet_sobel_edge(const uint8_t* src, const int* desc, float* edge, uint8_t* 
  *      dst[g][y][x] = y < Hr && x < Wr ? norm(src[g][nn(flip_y(y))][nn(flip_x(x))]) : pad_val, dst is [G,Hd,Wd];
  *      flip: 0 none, 1 horizontal, 2 vertical, 3 diagonal; norm_max (from radet_mask_max) or NULL = no normalisation */
 int radet_mask_max(const uint8_t* masks, uint32_t* maxes /* [G] */, int G, size_t hw, void* stream);
-int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, int G, int Hs, int Ws, int Hr, int Wr,
-                         int Hd, int Wd, int flip, int pad_val, void* stream);
-/* the window variants (Resize followed by RandomCrop): per mask a window of its virtual resized mask, one geometry per mask.
- * win_desc (device) i32 [G][MASK_WIN_INTS] = {virtual resized Hr, Wr, window origin y0, x0, window h, w, flip}:
- *      dst[g][y][x] = y < h && x < w ? norm(src[g][nn(y0 + flip_y(y))][nn(x0 + flip_x(x))]) : pad_val, nn over the Hr x Wr
- *      grid, the flip inside the window (it follows the crop), norm_max still the maximum of the whole source mask: what
- *      radet_mask_transform to [Hr, Wr] gives, sliced and then flipped.  h <= Hd, w <= Wd; a row whose window is not inside
- *      its Hr x Wr mask writes pad_val only.  radet_rle_masks_window: the same window of what radet_rle_masks decodes; the
- *      flip is mask_desc's (the flip word of win_desc is not read), dst_plain as there. */
-#define MASK_WIN_INTS 7
-int radet_mask_transform_window(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, const int* win_desc, int G, int Hs,
-                                int Ws, int Hd, int Wd, int pad_val, void* stream);
-/* the source-window variants (Expand / MinIoURandomCrop followed by Resize): per mask a window of the SOURCE mask is what
- * gets resized.  win_desc (device) i32 [G][MASK_SRC_WIN_INTS] = {resized Hr, Wr, window origin wy0, wx0 in the source's
- * coordinates (may be negative), window wh, ww, flip}:
- *      dst[g][y][x] = y < Hr && x < Wr ? norm(S(wy0 + nn(flip_y(y)), wx0 + nn(flip_x(x)))) : pad_val, nn over the wh x ww
- *      window grid resized to Hr x Wr, S(sy, sx) = src[g][sy][sx] inside the Hs x Ws source and 0 outside it
- *      (BitmapMasks.expand pads with zeros), norm_max still the maximum of the whole source mask: what np.pad / slicing the
- *      source and radet_mask_transform give.  Hr <= Hd, Wr <= Wd; a row that breaks that, or with wh or ww <= 0, writes
- *      pad_val only.  radet_rle_masks_src_window (declared below): the same window of what radet_rle_masks decodes -- a
- *      sample outside the source is 0, not a lookup in a neighbouring column's runs; the flip is mask_desc's (the flip
- *      word of win_desc is not read), dst_plain as there. */
-#define MASK_SRC_WIN_INTS 7
-int radet_mask_transform_src_window(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, const int* win_desc, int G, int Hs,
-                                    int Ws, int Hd, int Wd, int pad_val, void* stream);
+int radet_mask_transform(const uint8_t* src, uint8_t* dst, const uint32_t* norm_max, const int* view_desc, int G, int Hs, int Ws,
+                         int Hr, int Wr, int Hd, int Wd, int flip, int pad_val, void* stream);
+/* view_desc (i32 [G][RADET_VIEW_INTS], see above) replaces Hr, Wr and flip by one geometry per mask */
 
 /* ---- the same masks from run-length annotations (COCO RLE / rasterised polygons, radet/datasets/pipelines/loading.py:313-380
  *      `_poly2mask`), without a bitmap on the host or in HBM: one launch per group of masks of one destination geometry.
@@ -528,16 +505,14 @@ int radet_mask_transform_src_window(const uint8_t* src, uint8_t* dst, const uint
  *      dst[g][y][x] = y < Hr && x < Wr ? OR over parts of (index of the run that holds nn(flip_x(x)) * Hs + nn(y)) & 1 : pad_val.
  *      dst_plain (may be NULL) u8 [G,Hd,Wd]: the unflipped mask, written ONLY for masks whose flip bit is set (for the
  *      others dst already is that mask): both orientations from one lookup.  Rows that point outside the tables decode as
- *      empty.  Wd <= 8192, G <= 65535. */
+ *      empty.  Wd <= 8192, G <= 65535.  view_desc (i32 [G][RADET_VIEW_INTS], see above; may be NULL) replaces Hr, Wr: the
+ *      same window of what is decoded -- a sample outside the source is 0, not a lookup in a neighbouring column's runs;
+ *      the flip stays mask_desc's (the flip word of view_desc is not read) and acts inside the h x w window. */
 #define RLE_MASK_INTS 5
 #define RLE_PART_INTS 2
-int radet_rle_masks(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc, int G,
-                    uint8_t* dst, uint8_t* dst_plain, int Hr, int Wr, int Hd, int Wd, int pad_val, void* stream);
-int radet_rle_masks_window(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc,
-                           const int* win_desc, int G, uint8_t* dst, uint8_t* dst_plain, int Hd, int Wd, int pad_val, void* stream);
-int radet_rle_masks_src_window(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc,
-                               const int* win_desc, int G, uint8_t* dst, uint8_t* dst_plain, int Hd, int Wd, int pad_val,
-                               void* stream);
+int radet_rle_masks(const uint32_t* run_ends, int n_ends, const int* part_desc, int n_parts, const int* mask_desc,
+                    const int* view_desc, int G, uint8_t* dst, uint8_t* dst_plain, int Hr, int Wr, int Hd, int Wd, int pad_val,
+                    void* stream);
 
 /* ---- baseline JPEG files decoded on the device (csrc/jpeg.hip, csrc/jpeg_index.c, radet_amd/core/jpeg.py): what libjpeg's
  *      default decompressor gives for them byte for byte (slow-integer IDCT, fancy upsampling, fixed-point YCbCr -> RGB),

@@ -101,9 +101,7 @@ SIGNATURES = {
     "radet_assign_ws_bytes": (_sz, [_i, _i]),
     "radet_assign_points": (_i, [_p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
     "radet_assign_points_f": (_i, [_p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
-    "radet_resize_linear_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-    "radet_resize_linear_u8_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-    "radet_resize_linear_u8_src_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "radet_resize_linear_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_resize_linear_f": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_warp_affine_u8": (_i, [_p, _sz, _p, _sz, _p, _i, _i, _i, _p]),
     "radet_cutout_u8": (_i, [_p, _sz, _p, _i, _p, _i, _i, _i, _i, _p]),
@@ -127,12 +125,8 @@ SIGNATURES = {
     "radet_mbd": (_i, [_p, _p, _i, _p, _p, _f, _i, _i, _p, _sz, _p, _p]),
     "radet_gdt": (_i, [_p, _p, _i, _p, _p, _p, _p, _p]),
     "radet_mask_max": (_i, [_p, _p, _i, _sz, _p]),
-    "radet_mask_transform": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "radet_mask_transform_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "radet_mask_transform_src_window": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "radet_rle_masks": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "radet_rle_masks_window": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p]),
-    "radet_rle_masks_src_window": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p]),
+    "radet_mask_transform": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "radet_rle_masks": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "radet_jpeg_index": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _i]),
     "radet_jpeg_decode": (_i, [_p, _p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p]),
     "radet_augment_merge_hblur": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),

@@ -32,73 +32,43 @@ __device__ __forceinline__ int reflect101(int p, int n) {      // cv::borderInte
     return p;
 }
 
-template <int C>
+// VIEW: row n of `view` (pixel_ops.h View) names the window of the source that is resized, the virtual resized size and the
+// window of that which is written; d.h x d.w must be that window.  Taps and coefficients are those of a wh x ww image
+// resized to Hr x Wr, so the edge clamp is at the source window's border; each tap is then read at (wy0 + ty, wx0 + tx) of
+// the source or is the row's fill colour where that lies outside it: bit for bit "paste the source on a filled canvas,
+// slice the window, resize, slice", without the canvas.  A row with bad geometry or an empty source is not written.
+// Without VIEW: the whole source to the whole d.h x d.w, every tap inside the source.
+template <int C, bool VIEW>
 __global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restrict__ src, const int* __restrict__ sdesc,
-                                                        uint8_t* __restrict__ dst, const int* __restrict__ ddesc) {
+                                                        uint8_t* __restrict__ dst, const int* __restrict__ ddesc,
+                                                        const int* __restrict__ view) {
     const Crop s = load_crop(sdesc, blockIdx.y), d = load_crop(ddesc, blockIdx.y);
+    View v = {d.h, d.w, 0, 0, s.h, s.w, 0, 0, d.h, d.w, 0, 0u};
+    if (VIEW && (!load_view(view, blockIdx.y, &v) || v.h != d.h || v.w != d.w || s.h <= 0 || s.w <= 0 ||
+                 (long long)d.h * d.w > 0x7FFFFFFFLL))
+        return;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= d.h * d.w) return;
     const int dy = p / d.w, dx = p - dy * d.w;
-    const LinTaps t = lin_taps_u8(dy, dx, s.h, s.w, d.h, d.w);
-    const uint8_t* r0 = src + ((size_t)s.off + (size_t)t.y0 * s.w) * C;
-    const uint8_t* r1 = src + ((size_t)s.off + (size_t)t.y1 * s.w) * C;
+    const LinTaps t = lin_taps_u8(v.oy + dy, v.ox + dx, v.wh, v.ww, v.Hr, v.Wr);
     uint8_t* o = dst + ((size_t)d.off + p) * C;
+    if (!VIEW) {
+        const uint8_t* r0 = src + ((size_t)s.off + (size_t)t.y0 * s.w) * C;
+        const uint8_t* r1 = src + ((size_t)s.off + (size_t)t.y1 * s.w) * C;
 #pragma unroll
-    for (int c = 0; c < C; ++c)
-        o[c] = (uint8_t)lin_blend_u8(r0[t.sx * C + c], r0[t.x1 * C + c], r1[t.sx * C + c], r1[t.x1 * C + c], t);
-}
-
-// The window variant (Resize + RandomCrop): only the h x w window at (y0, x0) of the virtual Hr x Wr resized image is
-// written, packed at the row's offset.  Output pixel (y, x) is the virtual pixel (y0 + y, x0 + x): same taps, same blend
-// as above, so the result is that of the full resize sliced.  A row whose window does not lie inside its virtual image
-// is not written.
-template <int C>
-__global__ __launch_bounds__(256) void resize_u8_window_kernel(const uint8_t* __restrict__ src, const int* __restrict__ sdesc,
-                                                               uint8_t* __restrict__ dst, const int* __restrict__ wdesc) {
-    const Crop s = load_crop(sdesc, blockIdx.y);
-    const int* d = wdesc + RESIZE_WIN_DESC_INTS * blockIdx.y;
-    const int h = d[1], w = d[2], Hr = d[3], Wr = d[4], y0 = d[5], x0 = d[6];
-    if (h <= 0 || w <= 0 || y0 < 0 || x0 < 0 || y0 > Hr - h || x0 > Wr - w || s.h <= 0 || s.w <= 0) return;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= h * w) return;
-    const int dy = p / w, dx = p - dy * w;
-    const LinTaps t = lin_taps_u8(y0 + dy, x0 + dx, s.h, s.w, Hr, Wr);
-    const uint8_t* r0 = src + ((size_t)s.off + (size_t)t.y0 * s.w) * C;
-    const uint8_t* r1 = src + ((size_t)s.off + (size_t)t.y1 * s.w) * C;
-    uint8_t* o = dst + ((size_t)d[0] + p) * C;
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-        o[c] = (uint8_t)lin_blend_u8(r0[t.sx * C + c], r0[t.x1 * C + c], r1[t.sx * C + c], r1[t.x1 * C + c], t);
-}
-
-// The source-window variant (Expand / MinIoURandomCrop in front of Resize): the image that is resized is the wh x ww
-// window at (wy0, wx0) of the source in the source's own coordinates; the window may overhang the source or miss it, and
-// what lies outside reads as the row's fill colour.  Taps and coefficients are those of a wh x ww image -> Hr x Wr, so
-// the edge clamp happens at the window's border; each tap is then fetched at (wy0 + ty, wx0 + tx) of the source or is
-// the fill: bit for bit "paste the source on a filled canvas, slice the window, resize", without the canvas.
-template <int C>
-__global__ __launch_bounds__(256) void resize_u8_src_window_kernel(const uint8_t* __restrict__ src, const int* __restrict__ sdesc,
-                                                                   uint8_t* __restrict__ dst, const int* __restrict__ wdesc) {
-    const Crop s = load_crop(sdesc, blockIdx.y);
-    const int* d = wdesc + RESIZE_SRC_WIN_DESC_INTS * blockIdx.y;
-    const int Hr = d[1], Wr = d[2], wy0 = d[3], wx0 = d[4], wh = d[5], ww = d[6];
-    const unsigned fill = (unsigned)d[7];
-    if (Hr <= 0 || Wr <= 0 || wh <= 0 || ww <= 0 || s.h <= 0 || s.w <= 0) return;
-    if ((long long)wy0 + wh > 0x7FFFFFFFLL || (long long)wx0 + ww > 0x7FFFFFFFLL) return;    // (canvas coordinates fit in int)
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if ((long long)p >= (long long)Hr * Wr) return;
-    const int dy = p / Wr, dx = p - dy * Wr;
-    const LinTaps t = lin_taps_u8(dy, dx, wh, ww, Hr, Wr);
-    const int y0 = wy0 + t.y0, y1 = wy0 + t.y1, x0 = wx0 + t.sx, x1 = wx0 + t.x1;
+        for (int c = 0; c < C; ++c)
+            o[c] = (uint8_t)lin_blend_u8(r0[t.sx * C + c], r0[t.x1 * C + c], r1[t.sx * C + c], r1[t.x1 * C + c], t);
+        return;
+    }
+    const int y0 = v.wy0 + t.y0, y1 = v.wy0 + t.y1, x0 = v.wx0 + t.sx, x1 = v.wx0 + t.x1;
     const bool iy0 = (unsigned)y0 < (unsigned)s.h, iy1 = (unsigned)y1 < (unsigned)s.h;
     const bool ix0 = (unsigned)x0 < (unsigned)s.w, ix1 = (unsigned)x1 < (unsigned)s.w;
     const uint8_t* r0 = src + ((size_t)s.off + (size_t)(iy0 ? y0 : 0) * s.w) * C;
     const uint8_t* r1 = src + ((size_t)s.off + (size_t)(iy1 ? y1 : 0) * s.w) * C;
     const int c0 = (ix0 ? x0 : 0) * C, c1 = (ix1 ? x1 : 0) * C;
-    uint8_t* o = dst + ((size_t)d[0] + p) * C;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        const int f = (int)((fill >> (8 * c)) & 0xFFu);
+        const int f = (int)((v.fill >> (8 * c)) & 0xFFu);
         const int p00 = iy0 && ix0 ? r0[c0 + c] : f, p01 = iy0 && ix1 ? r0[c1 + c] : f;
         const int p10 = iy1 && ix0 ? r1[c0 + c] : f, p11 = iy1 && ix1 ? r1[c1 + c] : f;
         o[c] = (uint8_t)lin_blend_u8(p00, p01, p10, p11, t);
@@ -266,40 +236,23 @@ __global__ __launch_bounds__(256) void paste_maps_kernel(const T* __restrict__ m
 
 static inline dim3 crop_grid(int max_px, int n) { return dim3((max_px + 255) / 256, n); }
 
-extern "C" int radet_resize_linear_u8(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* dst_desc, int ncrop,
-                                      int max_dst_px, int channels, void* stream) {
-    if (ncrop < 0 || max_dst_px < 0 || (channels != 1 && channels != 3)) return RADET_ERR_ARG;
-    if (ncrop == 0 || max_dst_px == 0) return RADET_OK;
-    if (channels == 3)
-        hipLaunchKernelGGL(resize_u8_kernel<3>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc, dst, dst_desc);
+template <int C>
+static void launch_resize_u8(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* dst_desc, const int* view_desc,
+                             int ncrop, int max_dst_px, hipStream_t st) {
+    if (view_desc)
+        hipLaunchKernelGGL((resize_u8_kernel<C, true>), crop_grid(max_dst_px, ncrop), dim3(256), 0, st, src, src_desc, dst, dst_desc, view_desc);
     else
-        hipLaunchKernelGGL(resize_u8_kernel<1>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc, dst, dst_desc);
-    return radet_check_launch();
+        hipLaunchKernelGGL((resize_u8_kernel<C, false>), crop_grid(max_dst_px, ncrop), dim3(256), 0, st, src, src_desc, dst, dst_desc, view_desc);
 }
 
-extern "C" int radet_resize_linear_u8_window(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* win_desc, int ncrop,
-                                             int max_dst_px, int channels, void* stream) {
+extern "C" int radet_resize_linear_u8(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* dst_desc,
+                                      const int* view_desc, int ncrop, int max_dst_px, int channels, void* stream) {
     if (ncrop < 0 || max_dst_px < 0 || (channels != 1 && channels != 3)) return RADET_ERR_ARG;
     if (ncrop == 0 || max_dst_px == 0) return RADET_OK;
     if (channels == 3)
-        hipLaunchKernelGGL(resize_u8_window_kernel<3>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc, dst,
-                           win_desc);
+        launch_resize_u8<3>(src, src_desc, dst, dst_desc, view_desc, ncrop, max_dst_px, (hipStream_t)stream);
     else
-        hipLaunchKernelGGL(resize_u8_window_kernel<1>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc, dst,
-                           win_desc);
-    return radet_check_launch();
-}
-
-extern "C" int radet_resize_linear_u8_src_window(const uint8_t* src, const int* src_desc, uint8_t* dst, const int* win_desc, int ncrop,
-                                                 int max_dst_px, int channels, void* stream) {
-    if (ncrop < 0 || max_dst_px < 0 || (channels != 1 && channels != 3)) return RADET_ERR_ARG;
-    if (ncrop == 0 || max_dst_px == 0) return RADET_OK;
-    if (channels == 3)
-        hipLaunchKernelGGL(resize_u8_src_window_kernel<3>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc,
-                           dst, win_desc);
-    else
-        hipLaunchKernelGGL(resize_u8_src_window_kernel<1>, crop_grid(max_dst_px, ncrop), dim3(256), 0, (hipStream_t)stream, src, src_desc,
-                           dst, win_desc);
+        launch_resize_u8<1>(src, src_desc, dst, dst_desc, view_desc, ncrop, max_dst_px, (hipStream_t)stream);
     return radet_check_launch();
 }
 

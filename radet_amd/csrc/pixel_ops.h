@@ -1,8 +1,10 @@
 // Per-pixel device helpers shared by imgproc.hip (radet_resize_linear_u8 / _f), augment.hip (radet_augment_finish) and
 // preprocess.hip (radet_preprocess_frames): one definition of the 8-bit INTER_LINEAR arithmetic and of the Normalize / pad
-// store, so that the one-launch frame preparation equals resize -> finish bit for bit by construction.
+// store, so that the one-launch frame preparation equals resize -> finish bit for bit by construction; and the view row
+// that imgproc.hip and masks.hip share.
 #pragma once
 #include "common.h"
+#include "../../include/radet_hip.h"
 
 // source index + fraction of destination index d (cv::resize, INTER_LINEAR): f = (d + 0.5) * scale - 0.5 in float
 __device__ __forceinline__ void lin_coord(int d, double scale, int n, bool clamp_frac, int* s, float* f) {
@@ -48,6 +50,18 @@ __device__ __forceinline__ int lin_blend_u8(int p00, int p01, int p10, int p11, 
     const int h1 = p10 * t.a0 + p11 * t.a1;
     const int v = (((t.b0 * (h0 >> 4)) >> 16) + ((t.b1 * (h1 >> 4)) >> 16) + 2) >> 2;
     return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+// One view row (include/radet_hip.h RADET_VIEW_INTS): the wh x ww window at (wy0, wx0) of the source, resized to a virtual
+// Hr x Wr, of which the h x w window at (oy, ox) is written.  load_view is false for a row with bad geometry.
+struct View { int Hr, Wr, wy0, wx0, wh, ww, oy, ox, h, w, flip; unsigned fill; };
+
+__device__ __forceinline__ bool load_view(const int* __restrict__ rows, size_t n, View* v) {
+    const int* d = rows + n * RADET_VIEW_INTS;
+    *v = {d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], (unsigned)d[11]};
+    return v->Hr > 0 && v->Wr > 0 && v->wh > 0 && v->ww > 0 && (long long)v->wy0 + v->wh <= 0x7FFFFFFFLL &&
+           (long long)v->wx0 + v->ww <= 0x7FFFFFFFLL && v->oy >= 0 && v->ox >= 0 && v->h >= 0 && v->w >= 0 &&
+           v->oy <= v->Hr - v->h && v->ox <= v->Wr - v->w;
 }
 
 // Normalize of one u8 BGR pixel v into the three planes at o (optional BGR->RGB, (q - mean) * stdinv in fp32), and Pad's zeros

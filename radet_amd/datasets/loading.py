@@ -16,13 +16,13 @@ sample_cache='device' decoded frames and backgrounds stay in HBM after their fir
 with one radet_copy_segments launch (sample_cache.py).  A single sample (`BOPDataset.__getitem__`) is a batch
 of one.  A pipeline whose first stage is LoadImageFromWebcam takes frames that are in memory already (ndarray or device
 tensor): a test pipeline, whose run() is one pinned upload and one radet_preprocess_frames launch (_run_frames).
-Scale jitter (Resize with random scales, RandomCrop, Pad(size=)): RandomCrop plans a window of the virtual resized image and
-run() computes that window only -- radet_resize_linear_u8_window, radet_mask_transform_window, radet_rle_masks_window in
-the place of their plain counterparts -- so a batch keeps one tensor shape at the cost of the crop's pixels.
-Zoom (Expand, MinIoURandomCrop, in front of Resize): the mirror image -- the stages plan a window of the virtual SOURCE
-canvas in image coordinates, which may overhang the image (s["src_window"]); run() resizes that window straight from the
-image, the canvas fill where it overhangs (radet_resize_linear_u8_src_window, radet_mask_transform_src_window,
-radet_rle_masks_src_window in the place of their plain counterparts); no canvas is ever made.
+Windows: every sample has one view (sample_view; the view row of include/radet_hip.h) -- the window of the source that is
+resized, the virtual resized size, and the window of that which is computed -- and the resize and both mask kernels take
+one such row per image or mask.  Scale jitter (Resize with random scales, RandomCrop, Pad(size=)): RandomCrop plans the
+output window (s["crop_window"]) and run() computes that window only, so a batch keeps one tensor shape at the cost of the
+crop's pixels.  Zoom (Expand, MinIoURandomCrop, in front of Resize): the stages plan the source window in image coordinates,
+which may overhang the image (s["src_window"]); run() resizes that window straight from the image, the canvas fill where
+it overhangs; no canvas is ever made.
 Affine augmentation (Rotate, Shear, Translate, or one AutoAugment over them, directly after Resize): the stages plan boxes
 and leave forward matrices in s["affine"]; run() warps the resized frames and the resized, unflipped masks once per
 entry (radet_warp_affine_u8: cv2.warpAffine's classic fixed-point bilinear path), in front of the merge and the flip.
@@ -325,6 +325,18 @@ def _set_src_window(s, y0, x0, h, w, fill):
     # (without a Resize the window is the output; pad_shape follows it so that a pipeline without Pad collects the window)
     s["resize_hw"] = (int(h), int(w))
     s["pad_shape"] = (int(h), int(w), 3)
+
+
+def sample_view(s, src_hw=None):
+    """A planned sample's view row {Hr, Wr, wy0, wx0, wh, ww, oy, ox, h, w, flip = 0, fill} (include/radet_hip.h
+    RADET_VIEW_INTS): s["src_window"] is the window of the source that is resized (without one: the whole source, which is
+    the image, or src_hw for a mask of that size), s["resize_hw"] the virtual resized size, s["crop_window"] the window of
+    that which is computed (without one: all of it)."""
+    Hs, Ws = s["img"].shape[:2] if src_hw is None else src_hw
+    wy0, wx0, wh, ww, fill = s.get("src_window", (0, 0, Hs, Ws, (0, 0, 0)))
+    Hr, Wr = s.get("resize_hw", (wh, ww))
+    oy, ox, h, w = s.get("crop_window", (0, 0, Hr, Wr))
+    return tuple(int(v) for v in (Hr, Wr, wy0, wx0, wh, ww, oy, ox, h, w, 0, fill[0] | fill[1] << 8 | fill[2] << 16))
 
 
 @PIPELINES.register_module()
@@ -1425,13 +1437,10 @@ class ImagePipeline:
                 what = "; ".join(f"{p}: " + ", ".join(v for k, v in jpeg.ERRORS.items() if e & k) for p, e in bad)
                 raise ValueError(f"device JPEG decode failed (the pixels of that batch are undefined): {what}")
 
-    def _resize_packed(self, arrays, dst_hw, dev, align=1, src=None, windows=None, src_windows=None):
-        """u8 HWC images of any sizes -> one packed device buffer of the dst sizes (one resize launch); every image starts at
-        a multiple of `align` pixels.  src: (packed device buffer, pixel offsets) when the images are there already.
-        windows: per image (Hr, Wr, y0, x0) -- dst_hw is then the size of the window at (y0, x0) of the Hr x Wr resized
-        image, and only that window is computed (radet_resize_linear_u8_window).  src_windows: per image (y0, x0, h, w,
-        fill) -- the window of the source, in its coordinates, that is resized to dst_hw; outside the source it reads as
-        the fill colour (radet_resize_linear_u8_src_window)"""
+    def _resize_packed(self, arrays, dst_hw, dev, align=1, src=None, views=None):
+        """u8 HWC images of any sizes -> one packed device buffer of the dst sizes (one upload, one resize launch); every
+        image starts at a multiple of `align` pixels.  src: (packed device buffer, pixel offsets) when the images are there
+        already.  views: per image its view row (sample_view) -- dst_hw is then the size of the row's output window"""
         src, src_offs = src if src is not None else (torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(dev), None)
         sdesc, ddesc, so, do = [], [], 0, 0
         for k, (a, (h, w)) in enumerate(zip(arrays, dst_hw)):
@@ -1442,21 +1451,12 @@ class ImagePipeline:
             do += -(-h * w // align) * align
         dst = torch.empty(do * 3, dtype=torch.uint8, device=dev)
         n = len(arrays)
-        if src_windows is not None:
-            wdesc = [(*d, y0, x0, h, w, f[0] | f[1] << 8 | f[2] << 16) for d, (y0, x0, h, w, f) in zip(ddesc, src_windows)]
-            desc = torch.from_numpy(np.concatenate([np.array(sdesc, np.int32).reshape(-1), np.array(wdesc, np.int32).reshape(-1)])).to(dev)
-            K.resize_linear_u8_src_window(src, desc[:3 * n].view(n, 3), dst, desc[3 * n:].view(n, K.RESIZE_SRC_WIN_DESC_INTS), n,
-                                          max(h * w for h, w in dst_hw), 3)
-            return dst, [d[0] for d in ddesc]
-        if windows is not None:
-            # (one upload: the source rows, then the window rows)
-            wdesc = [(*d, *win) for d, win in zip(ddesc, windows)]
-            desc = torch.from_numpy(np.concatenate([np.array(sdesc, np.int32).reshape(-1), np.array(wdesc, np.int32).reshape(-1)])).to(dev)
-            K.resize_linear_u8_window(src, desc[:3 * n].view(n, 3), dst, desc[3 * n:].view(n, K.RESIZE_WIN_DESC_INTS), n,
-                                      max(h * w for h, w in dst_hw), 3)
-            return dst, [d[0] for d in ddesc]
-        desc = torch.from_numpy(np.array(sdesc + ddesc, np.int32).reshape(-1, 3)).to(dev)
-        K.resize_linear_u8(src, desc[:n], dst, desc[n:], n, max(h * w for h, w in dst_hw), 3)
+        desc = np.array(sdesc + ddesc, np.int32).reshape(-1)
+        if views is not None:
+            desc = np.concatenate([desc, np.array(views, np.int32).reshape(-1)])
+        desc = torch.from_numpy(desc).to(dev)
+        K.resize_linear_u8(src, desc[:3 * n].view(n, 3), dst, desc[3 * n:6 * n].view(n, 3), n, max(h * w for h, w in dst_hw), 3,
+                           views=desc[6 * n:].view(n, K.VIEW_INTS) if views is not None else None)
         return dst, [d[0] for d in ddesc]
 
     @staticmethod
@@ -1524,6 +1524,32 @@ class ImagePipeline:
         up = torch.from_numpy(np.concatenate([D.reshape(-1), np.concatenate(holes).reshape(-1)])).to(dev)
         K.cutout_f32(out, up[:D.size].view(B, K.CUTOUT_DESC_INTS), up[D.size:].view(-1, 4), B, most, area, mean, stdinv)
 
+    @staticmethod
+    def _mask_groups(planned, keys):
+        """the samples that carry masks, grouped by (kind: "bitmap" / "runs", source size, keys[i]), bitmaps first: per group
+        (kind, source size, key, sample indices, masks per sample)"""
+        groups = {}
+        for i, s in enumerate(planned):
+            if "gt_masks_rle" in s and "gt_masks" in s:
+                raise ValueError("a sample carries both gt_masks and gt_masks_rle")
+            if "gt_masks" in s:
+                groups.setdefault(("bitmap", tuple(s["gt_masks"].shape[1:]), keys[i]), []).append(i)
+            elif "gt_masks_rle" in s:
+                groups.setdefault(("runs", tuple(s["gt_masks_rle"][1]), keys[i]), []).append(i)
+        return [(*key, idx, [len(planned[i]["gt_masks"] if key[0] == "bitmap" else planned[i]["gt_masks_rle"][0]) for i in idx])
+                for key, idx in sorted(groups.items(), key=lambda kv: kv[0][0] != "bitmap")]
+
+    @staticmethod
+    def _upload_runs(planned, idx, src_hw, flips, dev, rows=None):
+        """the run lists of the samples idx (and their view rows) in one pinned upload: radet_rle_masks' three arrays, and
+        the rows' device copy"""
+        ends, prows, mrows = rle.pack_runs([m for i in idx for m in planned[i]["gt_masks_rle"][0]], *src_hw, flips)
+        parts = [ends.view(np.int32), prows.reshape(-1), mrows.reshape(-1)] + ([] if rows is None else [rows.reshape(-1)])
+        packed = torch.from_numpy(np.concatenate(parts)).pin_memory().to(dev, non_blocking=True)
+        a, b, c = ends.size, ends.size + prows.size, ends.size + prows.size + mrows.size
+        return (packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:c].view(-1, K.RLE_MASK_INTS),
+                None if rows is None else packed[c:].view(-1, K.VIEW_INTS))
+
     def _affine_masks(self, planned, hw, dev, ahw):
         """_masks for a batch in which some sample carries affine entries.  Per group of samples of equal source size,
         resized size, assigner size and flip: the unflipped resized bitmaps (radet_mask_max + radet_mask_transform, or
@@ -1531,16 +1557,8 @@ class ImagePipeline:
         sample with fewer entries are copied), then flip and pad for the assigner in one radet_mask_transform pass where
         the group needs either.  The first list (the merge's masks) is the warped, unflipped stack."""
         masks, flipped = [None] * len(planned), [None] * len(planned)
-        groups = {}
-        for i, s in enumerate(planned):
-            if "gt_masks_rle" in s and "gt_masks" in s:
-                raise ValueError("a sample carries both gt_masks and gt_masks_rle")
-            if "gt_masks" in s:
-                groups.setdefault(("bitmap", tuple(s["gt_masks"].shape[1:]), hw[i], ahw[i], bool(s.get("flip"))), []).append(i)
-            elif "gt_masks_rle" in s:
-                groups.setdefault(("runs", tuple(s["gt_masks_rle"][1]), hw[i], ahw[i], bool(s.get("flip"))), []).append(i)
-        for (kind, src_hw, dst_hw, out_hw, flip), idx in groups.items():
-            counts = [len(planned[i]["gt_masks"] if kind == "bitmap" else planned[i]["gt_masks_rle"][0]) for i in idx]
+        keys = [(hw[i], ahw[i], bool(s.get("flip"))) for i, s in enumerate(planned)]
+        for kind, src_hw, (dst_hw, out_hw, flip), idx, counts in self._mask_groups(planned, keys):
             G = sum(counts)
             if not G:
                 for i in idx:
@@ -1551,12 +1569,7 @@ class ImagePipeline:
                 src = torch.from_numpy(np.concatenate([planned[i]["gt_masks"] for i in idx])).to(dev)
                 res = K.mask_transform(src, resized_hw=dst_hw, normalize=True)
             else:
-                per_mask = [m for i in idx for m in planned[i]["gt_masks_rle"][0]]
-                ends, prows, mrows = rle.pack_runs(per_mask, *src_hw, np.zeros(G, bool))
-                packed = torch.from_numpy(np.concatenate([ends.view(np.int32), prows.reshape(-1), mrows.reshape(-1)]))
-                packed = packed.pin_memory().to(dev, non_blocking=True)
-                a, b = ends.size, ends.size + prows.size
-                res = K.rle_masks(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:].view(-1, K.RLE_MASK_INTS), dst_hw)
+                res = K.rle_masks(*self._upload_runs(planned, idx, src_hw, np.zeros(G, bool), dev)[:3], dst_hw)
             px = dst_hw[0] * dst_hw[1]
             entries = [[(m, (0, 0, 0)) for m, _ in planned[i].get("affine", ())] for i, c in zip(idx, counts) for _ in range(c)]
             res = self._warp_packed(res.view(-1), entries, [g * px for g in range(G)], [dst_hw] * G, dev, channels=1).view(G, *dst_hw)
@@ -1573,26 +1586,19 @@ class ImagePipeline:
             return self._run_frames(planned, collate)
         dev = self._dev()
         B = len(planned)
-        hw = [tuple(s.get("resize_hw", s["img"].shape[:2])) for s in planned]
-        # RandomCrop: the batch's images are windows (Hr, Wr, y0, x0) of the virtual resized images; hw is the crop size
-        # from here on (a sample of the batch without a window is the window that holds its whole image)
-        win = None
-        if any("crop_window" in s for s in planned):
-            win = [(*hw[i], *s["crop_window"][:2]) if "crop_window" in s else (*hw[i], 0, 0) for i, s in enumerate(planned)]
-            hw = [tuple(s["crop_window"][2:]) if "crop_window" in s else hw[i] for i, s in enumerate(planned)]
-            for (Hr, Wr, y0, x0), (h, w) in zip(win, hw):
-                if not (0 <= y0 <= Hr - h and 0 <= x0 <= Wr - w and h > 0 and w > 0):
-                    raise ValueError(f"crop window {h} x {w} at ({y0}, {x0}) of a resized image of {Hr} x {Wr}")
-        # Expand / MinIoURandomCrop: the batch's images are windows (y0, x0, h, w, fill) of their sources, in the source's
-        # coordinates, resized to hw (a sample of the batch without one is the window that is exactly its image)
-        swin = None
-        if any("src_window" in s for s in planned):
-            if win is not None:
-                raise ValueError("a batch with source windows (Expand / MinIoURandomCrop) and crop windows (RandomCrop)")
-            swin = [s["src_window"] if "src_window" in s else (0, 0, *s["img"].shape[:2], (0, 0, 0)) for s in planned]
-            for y0, x0, h, w, _ in swin:
-                if h <= 0 or w <= 0 or not all(-2 ** 30 < v < 2 ** 30 for v in (y0, x0, h, w)):
-                    raise ValueError(f"source window {h} x {w} at ({y0}, {x0})")
+        # each sample's view: RandomCrop planned the output window of the virtual resized image, Expand / MinIoURandomCrop the
+        # window of the source (it may overhang the image) that is resized; hw is the size of what is computed
+        views = [sample_view(s) for s in planned]
+        hw = [v[8:10] for v in views]
+        crop, zoom = any("crop_window" in s for s in planned), any("src_window" in s for s in planned)
+        if crop and zoom:
+            raise ValueError("a batch with source windows (Expand / MinIoURandomCrop) and crop windows (RandomCrop)")
+        for Hr, Wr, wy0, wx0, wh, ww, oy, ox, h, w, _, _ in views:
+            if crop and not (0 <= oy <= Hr - h and 0 <= ox <= Wr - w and h > 0 and w > 0):
+                raise ValueError(f"crop window {h} x {w} at ({oy}, {ox}) of a resized image of {Hr} x {Wr}")
+            if zoom and (wh <= 0 or ww <= 0 or not all(-2 ** 30 < v < 2 ** 30 for v in (wy0, wx0, wh, ww))):
+                raise ValueError(f"source window {wh} x {ww} at ({wy0}, {wx0})")
+        windowed = crop or zoom                                   # (a batch without windows: the resize launch takes no rows)
         for h, w in hw:
             if h > K.AUG_MAX_W or w > K.AUG_MAX_W:
                 raise ValueError(f"image of {h} x {w}: the augmentation kernels take sides up to {K.AUG_MAX_W}")
@@ -1606,17 +1612,17 @@ class ImagePipeline:
             # sample_cache='device': cached files are gathered into that buffer, new ones leave it for the arena
             src, soffs = (self._cached_packed(planned, with_bg, sources, dev, align=4 if self.mix else 1)
                           if self.sample_cache is not None else self._decode_packed(sources, dev, align=4 if self.mix else 1))
-            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, src=(src, soffs[:B]), windows=win,
-                                            src_windows=swin)
+            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, src=(src, soffs[:B]),
+                                            views=views if windowed else None)
             bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev, src=(src, soffs[B:]))
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         else:
-            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, windows=win, src_windows=swin)
+            img, offs = self._resize_packed(sources[:B], hw, dev, align=4 if self.mix else 1, views=views if windowed else None)
             bg, bg_offs = (self._resize_packed(sources[B:], [hw[i] for i in with_bg], dev)
                            if with_bg else (torch.zeros(1, dtype=torch.uint8, device=dev), []))
         bg_off = dict(zip(with_bg, bg_offs))
         affine = any(s.get("affine") for s in planned)
-        if affine and (win is not None or swin is not None):
+        if affine and windowed:
             raise ValueError("a batch with affine entries and windows (RandomCrop / Expand / MinIoURandomCrop)")
         entries = [_block_list(s) for s in planned]
         if any(entries):
@@ -1626,8 +1632,7 @@ class ImagePipeline:
         # of that size, which are the head's for every sample of the batch whatever scale was drawn (with Pad(size_divisor=)
         # the points follow img_shape as in the reference)
         ahw = [tuple(s["pad_shape"][:2]) if s.get("pad_fixed_size") is not None else hw[i] for i, s in enumerate(planned)]
-        masks, flipped_masks = (self._affine_masks(planned, hw, dev, ahw) if affine
-                                else self._masks(planned, hw, dev, win, ahw, swin))
+        masks, flipped_masks = self._affine_masks(planned, hw, dev, ahw) if affine else self._masks(planned, hw, dev, ahw)
 
         P = np.zeros((B, K.AUG_PARAM_INTS), np.int32)
         for i, s in enumerate(planned):
@@ -1815,143 +1820,45 @@ class ImagePipeline:
             P[i, 3] = fl
         return P
 
-    def _masks(self, planned, hw, dev, win=None, ahw=None, swin=None):
-        """normalised (mask / max), nearest-resized instance masks per sample (for the merge) and the same after the
-        sample's flip (for the assigner): one normalise + resize pass per group of equal sizes, one flip pass per group.
-        win: per sample (Hr, Wr, y0, x0), hw then being the size of the sample's window of its Hr x Wr resized masks; ahw:
-        per sample the size of the assigner's masks where it is not hw (Pad(size=)) -- either makes this _window_masks.
-        swin: per sample the source window (y0, x0, h, w, fill) that is resized to hw: _window_masks over source windows"""
+    def _masks(self, planned, hw, dev, ahw=None):
+        """Normalised (mask / max), nearest-resized instance masks per sample.  The second list (the assigner's masks: flipped
+        with the sample, zero-padded to ahw, which is hw without Pad(size=)) comes straight from the source masks, per group
+        of equal source and assigner sizes, with one view row per mask (sample_view over the mask's own size) -- one launch
+        whatever scales and windows the samples drew: radet_mask_max + radet_mask_transform for bitmaps, radet_rle_masks
+        for run lists.  The first list (the merge's masks: unflipped; read for samples with a background) is the same
+        output for an unflipped sample; when a merged sample is flipped, bitmaps take a second pass over the stack, and the
+        run-list launch writes both orientations of every flipped mask anyway.  A flipped sample whose group took no second
+        pass has no entry there.  These masks have the assigner's size: for a sample smaller than the pad the merge reads
+        their top-left corner (the mask pitch word of its params row).  Nothing waits for the device."""
         masks, flipped = [None] * len(planned), [None] * len(planned)
-        if swin is not None:
-            self._window_masks(planned, hw, dev, None, hw if ahw is None else ahw, masks, flipped, swin)
-            return masks, flipped
-        if win is None and ahw is not None and list(ahw) != list(hw):
-            win = [(*hw[i], 0, 0) for i in range(len(planned))]
-        if win is not None:
-            self._window_masks(planned, hw, dev, win, hw if ahw is None else ahw, masks, flipped)
-            return masks, flipped
-        groups = {}
-        for i, s in enumerate(planned):
-            if "gt_masks" in s:
-                groups.setdefault((s["gt_masks"].shape[1:], hw[i]), []).append(i)
-        for (src_hw, dst_hw), idx in groups.items():
-            counts = [planned[i]["gt_masks"].shape[0] for i in idx]
-            if not sum(counts):
-                for i in idx:
-                    masks[i] = flipped[i] = torch.zeros(0, *dst_hw, dtype=torch.uint8, device=dev)
-                continue
-            src = torch.from_numpy(np.concatenate([planned[i]["gt_masks"] for i in idx])).to(dev)
-            res = K.mask_transform(src, resized_hw=dst_hw, normalize=True)
-            fl = K.mask_transform(res, flip="horizontal") if any(planned[i].get("flip") for i in idx) else None
-            o = 0
-            for i, c in zip(idx, counts):
-                masks[i] = res[o:o + c]
-                flipped[i] = fl[o:o + c] if planned[i].get("flip") else masks[i]
-                o += c
-        self._rle_masks(planned, hw, dev, masks, flipped)
-        return masks, flipped
-
-    @staticmethod
-    def _rle_masks(planned, hw, dev, masks, flipped):
-        """the same two lists for the samples whose masks arrive as run lists (LoadAnnotations(with_mask=True)): per group
-        of equal sizes one pinned upload of the run arrays and one radet_rle_masks launch that writes both orientations;
-        nothing waits for the device"""
-        groups = {}
-        for i, s in enumerate(planned):
-            if "gt_masks_rle" in s:
-                if "gt_masks" in s:
-                    raise ValueError("a sample carries both gt_masks and gt_masks_rle")
-                groups.setdefault((tuple(s["gt_masks_rle"][1]), hw[i]), []).append(i)
-        for (src_hw, dst_hw), idx in groups.items():
-            per_mask = [m for i in idx for m in planned[i]["gt_masks_rle"][0]]
-            counts = [len(planned[i]["gt_masks_rle"][0]) for i in idx]
-            if not per_mask:
-                for i in idx:
-                    masks[i] = flipped[i] = torch.zeros(0, *dst_hw, dtype=torch.uint8, device=dev)
-                continue
-            flips = np.repeat([bool(planned[i].get("flip")) for i in idx], counts)
-            ends, prows, mrows = rle.pack_runs(per_mask, *src_hw, flips)
-            packed = torch.from_numpy(np.concatenate([ends.view(np.int32), prows.reshape(-1), mrows.reshape(-1)]))
-            packed = packed.pin_memory().to(dev, non_blocking=True)
-            a, b = ends.size, ends.size + prows.size
-            res = K.rle_masks(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:].view(-1, K.RLE_MASK_INTS), dst_hw,
-                              with_plain=bool(flips.any()))
-            out, plain = res if flips.any() else (res, None)
-            o = 0
-            for i, c in zip(idx, counts):
-                flipped[i] = out[o:o + c]
-                masks[i] = plain[o:o + c] if planned[i].get("flip") else flipped[i]
-                o += c
-
-    def _window_masks(self, planned, hw, dev, win, ahw, masks, flipped, swin=None):
-        """_masks for a batch whose samples are windows of their virtual resized images.  The second list (the assigner's
-        masks: flipped with the sample, zero-padded to ahw) comes straight from the source masks, per group of equal source
-        and assigner sizes -- one launch whatever scales and window sizes the samples drew: radet_mask_max +
-        radet_mask_transform_window with one row per mask for bitmaps, radet_rle_masks_window for run lists.  The first
-        list (the merge's masks: unflipped) is filled for the samples that carry a background only, with the same launch's
-        output for an unflipped sample; when a merged sample is flipped, bitmaps take a second pass over the stack and the
-        run-list launch writes both orientations.  These masks have the assigner's size: for a sample smaller than the
-        pad the merge reads their top-left corner (the mask pitch word of its params row).  The launches of a batch do not
-        depend on the scales and window sizes its samples drew.  Nothing waits for the device.
-        swin (instead of win): the samples are source windows (y0, x0, h, w, fill) resized to hw -- the same launches with
-        radet_mask_transform_src_window / radet_rle_masks_src_window and their rows {Hr, Wr, y0, x0, h, w, flip}."""
-        groups, rle_groups = {}, {}
-        for i, s in enumerate(planned):
-            if "gt_masks_rle" in s and "gt_masks" in s:
-                raise ValueError("a sample carries both gt_masks and gt_masks_rle")
-            if "gt_masks" in s:
-                groups.setdefault((tuple(s["gt_masks"].shape[1:]), ahw[i]), []).append(i)
-            elif "gt_masks_rle" in s:
-                rle_groups.setdefault((tuple(s["gt_masks_rle"][1]), ahw[i]), []).append(i)
-
-        def rows_of(idx, counts, with_flip):
-            if swin is not None:
-                rows = np.array([[*hw[i], *swin[i][:4], with_flip and bool(planned[i].get("flip"))] for i in idx], np.int32)
-                return np.repeat(rows.reshape(-1, K.MASK_SRC_WIN_INTS), counts, axis=0)
-            rows = np.array([[*win[i], *hw[i], with_flip and bool(planned[i].get("flip"))] for i in idx], np.int32)
-            return np.repeat(rows.reshape(-1, K.MASK_WIN_INTS), counts, axis=0)
-
-        mask_transform = K.mask_transform_window if swin is None else K.mask_transform_src_window
-        rle_masks = K.rle_masks_window if swin is None else K.rle_masks_src_window
-
-        def hand_out(idx, counts, out, plain):
-            o = 0
-            for i, c in zip(idx, counts):
-                flipped[i] = out[o:o + c]
-                if "background" in planned[i]:
-                    masks[i] = plain[o:o + c] if planned[i].get("flip") and c else out[o:o + c]
-                o += c
-
-        for (src_hw, out_hw), idx in groups.items():
-            counts = [planned[i]["gt_masks"].shape[0] for i in idx]
+        for kind, src_hw, out_hw, idx, counts in self._mask_groups(planned, hw if ahw is None else ahw):
             G = sum(counts)
-            if not G:
-                hand_out(idx, counts, torch.zeros(0, *out_hw, dtype=torch.uint8, device=dev), None)
-                continue
-            both = any(planned[i].get("flip") and "background" in planned[i] for i in idx)
-            src = torch.from_numpy(np.concatenate([planned[i]["gt_masks"] for i in idx])).to(dev)
-            rows = torch.from_numpy(np.concatenate([rows_of(idx, counts, True)] + ([rows_of(idx, counts, False)] if both else []))).to(dev)
-            mx = K.mask_max(src)
-            out = mask_transform(src, rows[:G], out_hw, norm_max=mx)
-            plain = mask_transform(src, rows[G:], out_hw, norm_max=mx) if both else None
-            hand_out(idx, counts, out, plain)
-        for (src_hw, out_hw), idx in rle_groups.items():
-            per_mask = [m for i in idx for m in planned[i]["gt_masks_rle"][0]]
-            counts = [len(planned[i]["gt_masks_rle"][0]) for i in idx]
-            if not per_mask:
-                hand_out(idx, counts, torch.zeros(0, *out_hw, dtype=torch.uint8, device=dev), None)
-                continue
             flips = np.repeat([bool(planned[i].get("flip")) for i in idx], counts)
-            both = any(planned[i].get("flip") and "background" in planned[i] for i in idx)
-            ends, prows, mrows = rle.pack_runs(per_mask, *src_hw, flips)
-            packed = torch.from_numpy(np.concatenate([ends.view(np.int32), prows.reshape(-1), mrows.reshape(-1),
-                                                      rows_of(idx, counts, False).reshape(-1)]))
-            packed = packed.pin_memory().to(dev, non_blocking=True)
-            a, b, c = ends.size, ends.size + prows.size, ends.size + prows.size + mrows.size
-            res = rle_masks(packed[:a], packed[a:b].view(-1, K.RLE_PART_INTS), packed[b:c].view(-1, K.RLE_MASK_INTS),
-                            packed[c:].view(-1, K.MASK_WIN_INTS), out_hw, with_plain=both)
-            out, plain = res if both else (res, None)
-            hand_out(idx, counts, out, plain)
+            rows = np.repeat(np.array([sample_view(planned[i], src_hw) for i in idx], np.int32).reshape(-1, K.VIEW_INTS), counts, axis=0)
+            if not G:
+                out = plain = torch.zeros(0, *out_hw, dtype=torch.uint8, device=dev)
+            elif kind == "bitmap":
+                both = any(planned[i].get("flip") and "background" in planned[i] for i in idx)
+                src = torch.from_numpy(np.concatenate([planned[i]["gt_masks"] for i in idx])).to(dev)
+                flipped_rows = rows.copy()
+                flipped_rows[:, 10] = flips
+                rows = torch.from_numpy(np.concatenate([flipped_rows] + ([rows] if both else []))).to(dev)
+                mx = K.mask_max(src)
+                out = K.mask_transform(src, out_hw, views=rows[:G], norm_max=mx)
+                plain = K.mask_transform(src, out_hw, views=rows[G:], norm_max=mx) if both else None
+            else:
+                *runs, rows = self._upload_runs(planned, idx, src_hw, flips, dev, rows)
+                res = K.rle_masks(*runs, out_hw, with_plain=bool(flips.any()), views=rows)
+                out, plain = res if flips.any() else (res, None)
+            o = 0
+            for i, c in zip(idx, counts):
+                flipped[i] = out[o:o + c]
+                if not (planned[i].get("flip") and c):
+                    masks[i] = flipped[i]
+                elif plain is not None:
+                    masks[i] = plain[o:o + c]
+                o += c
+        return masks, flipped
 
     def _collect(self, planned, out, p2g, pw, collate):
         samples = []

@@ -1499,24 +1499,13 @@ def assign_ws_bytes(B, N):
 FLIP = {None: 0, "none": 0, "horizontal": 1, "vertical": 2, "diagonal": 3}
 
 
-def mask_transform(src, out_hw=None, resized_hw=None, flip=None, pad_val=0, normalize=False):
-    """src: u8[G,Hs,Ws] device tensor -> u8[G,Hd,Wd]: nearest resize to resized_hw, flip, pad to out_hw (one pass)."""
-    G, Hs, Ws = src.shape
-    Hr, Wr = resized_hw or (Hs, Ws)
-    Hd, Wd = out_hw or (Hr, Wr)
-    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=src.device)
-    if G == 0:
-        return dst
-    mx = None
-    if normalize:
-        mx = torch.empty(G, dtype=torch.int32, device=src.device)
-        _lib.call("radet_mask_max", _ptr(src), _ptr(mx), G, C.c_size_t(Hs * Ws), _stream())
-    _lib.call("radet_mask_transform", _ptr(src), _ptr(dst), _ptr(mx), G, Hs, Ws, Hr, Wr, Hd, Wd, FLIP[flip], int(pad_val),
-              _stream())
-    return dst
+VIEW_INTS = 12                            # include/radet_hip.h RADET_VIEW_INTS
 
 
-MASK_WIN_INTS = 7                         # include/radet_hip.h
+def _views(views, n):
+    """view rows {Hr, Wr, wy0, wx0, wh, ww, oy, ox, h, w, flip, fill}: i32 [n, VIEW_INTS] on the device, or None"""
+    assert views is None or (tuple(views.shape) == (n, VIEW_INTS) and views.dtype == torch.int32 and views.is_contiguous())
+    return _ptr(views)
 
 
 def mask_max(src):
@@ -1527,48 +1516,24 @@ def mask_max(src):
     return mx
 
 
-def mask_transform_window(src, win_desc, out_hw, pad_val=0, normalize=False, norm_max=None):
-    """src: u8[G,Hs,Ws] device tensor -> u8[G,Hd,Wd]: per mask the window of its virtual nearest-resized mask that its
-    win_desc row names (i32 [G, MASK_WIN_INTS] on the device: {Hr, Wr, y0, x0, h, w, flip}), flipped inside the window,
-    padded to out_hw -- mask_transform(resized_hw=(Hr, Wr)) sliced, then flipped, one pass.  norm_max: the masks' maxima
-    from mask_max (several passes over one stack share them) instead of normalize=True"""
+def mask_transform(src, out_hw=None, resized_hw=None, flip=None, pad_val=0, normalize=False, views=None, norm_max=None):
+    """src: u8[G,Hs,Ws] device tensor -> u8[G,Hd,Wd]: nearest resize to resized_hw, flip, pad to out_hw (one pass).
+    views: one view row per mask instead of resized_hw and flip (out_hw is then required) -- the window of the source mask
+    (zeros outside it) that the row names, resized, the row's output window of that, flipped inside the window.
+    norm_max: the masks' maxima from mask_max (several passes over one stack share them) instead of normalize=True"""
     G, Hs, Ws = src.shape
-    Hd, Wd = out_hw
+    Hr, Wr = resized_hw or (Hs, Ws)
+    Hd, Wd = out_hw or (Hr, Wr)
     dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=src.device)
     if G == 0:
         return dst
-    assert tuple(win_desc.shape) == (G, MASK_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
     mx = norm_max
     if mx is not None:
         assert tuple(mx.shape) == (G,) and mx.dtype == torch.int32 and mx.is_contiguous()
     elif normalize:
         mx = mask_max(src)
-    _lib.call("radet_mask_transform_window", _ptr(src), _ptr(dst), _ptr(mx), _ptr(win_desc), G, Hs, Ws, Hd, Wd, int(pad_val),
-              _stream())
-    return dst
-
-
-MASK_SRC_WIN_INTS = 7                     # include/radet_hip.h
-
-
-def mask_transform_src_window(src, win_desc, out_hw, pad_val=0, normalize=False, norm_max=None):
-    """src: u8[G,Hs,Ws] device tensor -> u8[G,Hd,Wd]: per mask the window of the SOURCE mask that its win_desc row names
-    (i32 [G, MASK_SRC_WIN_INTS] on the device: {Hr, Wr, wy0, wx0, wh, ww, flip}; the window may overhang the mask, zeros
-    outside it) nearest-resized to Hr x Wr, flipped, padded to out_hw -- np.pad / slice, then mask_transform, in one pass.
-    normalize / norm_max: by the maximum of the whole source mask, as mask_transform_window"""
-    G, Hs, Ws = src.shape
-    Hd, Wd = out_hw
-    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=src.device)
-    if G == 0:
-        return dst
-    assert tuple(win_desc.shape) == (G, MASK_SRC_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
-    mx = norm_max
-    if mx is not None:
-        assert tuple(mx.shape) == (G,) and mx.dtype == torch.int32 and mx.is_contiguous()
-    elif normalize:
-        mx = mask_max(src)
-    _lib.call("radet_mask_transform_src_window", _ptr(src), _ptr(dst), _ptr(mx), _ptr(win_desc), G, Hs, Ws, Hd, Wd, int(pad_val),
-              _stream())
+    _lib.call("radet_mask_transform", _ptr(src), _ptr(dst), _ptr(mx), _views(views, G), G, Hs, Ws, Hr, Wr, Hd, Wd, FLIP[flip],
+              int(pad_val), _stream())
     return dst
 
 
@@ -1576,48 +1541,21 @@ RLE_MASK_INTS, RLE_PART_INTS = 5, 2       # include/radet_hip.h
 RLE_MAX_W = 8192
 
 
-def rle_masks(run_ends, part_desc, mask_desc, out_hw, resized_hw=None, pad_val=0, with_plain=False):
+def rle_masks(run_ends, part_desc, mask_desc, out_hw, resized_hw=None, pad_val=0, with_plain=False, views=None):
     """Run-length masks -> u8[G,Hd,Wd] in one launch (radet_amd.core.rle.pack_runs makes the three arrays): what
     mask_transform(normalize=True) gives for the decoded bitmaps, each mask with the flip of its descriptor row.
     run_ends: int32 / uint32 bit patterns [R]; part_desc i32 [P, 2]; mask_desc i32 [G, 5], all on the device.
     with_plain: also returns the unflipped masks -- defined only for masks whose flip bit is set (the others are
-    unflipped in the first result)."""
+    unflipped in the first result).  views: one view row per mask instead of resized_hw, as mask_transform's (the flip
+    stays mask_desc's, applied inside the output window; a sample outside the source image decodes as 0)."""
     G = mask_desc.shape[0]
     Hd, Wd = out_hw
     Hr, Wr = resized_hw or (Hd, Wd)
     dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=mask_desc.device)
     plain = torch.empty_like(dst) if with_plain else None
     if G:
-        _lib.call("radet_rle_masks", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc), G,
-                  _ptr(dst), _ptr(plain), Hr, Wr, Hd, Wd, int(pad_val), _stream())
-    return (dst, plain) if with_plain else dst
-
-
-def rle_masks_window(run_ends, part_desc, mask_desc, win_desc, out_hw, pad_val=0, with_plain=False):
-    """rle_masks for per-mask windows of the virtual resized masks (win_desc as for mask_transform_window; the flip is
-    mask_desc's, applied inside the window)"""
-    G = mask_desc.shape[0]
-    Hd, Wd = out_hw
-    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=mask_desc.device)
-    plain = torch.empty_like(dst) if with_plain else None
-    if G:
-        assert tuple(win_desc.shape) == (G, MASK_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
-        _lib.call("radet_rle_masks_window", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc),
-                  _ptr(win_desc), G, _ptr(dst), _ptr(plain), Hd, Wd, int(pad_val), _stream())
-    return (dst, plain) if with_plain else dst
-
-
-def rle_masks_src_window(run_ends, part_desc, mask_desc, win_desc, out_hw, pad_val=0, with_plain=False):
-    """rle_masks for per-mask windows of the source masks (win_desc as for mask_transform_src_window; the flip is
-    mask_desc's); a sample outside the source image decodes as 0"""
-    G = mask_desc.shape[0]
-    Hd, Wd = out_hw
-    dst = torch.empty(G, Hd, Wd, dtype=torch.uint8, device=mask_desc.device)
-    plain = torch.empty_like(dst) if with_plain else None
-    if G:
-        assert tuple(win_desc.shape) == (G, MASK_SRC_WIN_INTS) and win_desc.dtype == torch.int32 and win_desc.is_contiguous()
-        _lib.call("radet_rle_masks_src_window", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc),
-                  _ptr(win_desc), G, _ptr(dst), _ptr(plain), Hd, Wd, int(pad_val), _stream())
+        _lib.call("radet_rle_masks", _ptr(run_ends), run_ends.numel(), _ptr(part_desc), part_desc.shape[0], _ptr(mask_desc),
+                  _views(views, G), G, _ptr(dst), _ptr(plain), Hr, Wr, Hd, Wd, int(pad_val), _stream())
     return (dst, plain) if with_plain else dst
 
 
@@ -1667,27 +1605,12 @@ def gauss9_kernel():
     return (C.c_float * 5)(*[float(v) for v in cf[4:]])
 
 
-def resize_linear_u8(src, sdesc, dst, ddesc, n, max_dst_px, channels=3):
-    _lib.call("radet_resize_linear_u8", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(ddesc), n, max_dst_px, channels, _stream())
-
-
-RESIZE_WIN_DESC_INTS = 7                  # include/radet_hip.h
-
-
-def resize_linear_u8_window(src, sdesc, dst, wdesc, n, max_dst_px, channels=3):
-    """resize_linear_u8 writing only a window of each virtual resized image: wdesc i32 [n, RESIZE_WIN_DESC_INTS] on the
-    device, {packed pixel offset, window h, w, resized Hr, Wr, window origin y0, x0}"""
-    _lib.call("radet_resize_linear_u8_window", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(wdesc), n, max_dst_px, channels, _stream())
-
-
-RESIZE_SRC_WIN_DESC_INTS = 8              # include/radet_hip.h
-
-
-def resize_linear_u8_src_window(src, sdesc, dst, wdesc, n, max_dst_px, channels=3):
-    """resize_linear_u8 of a window of each source image (it may overhang the image: a fill colour outside): wdesc i32
-    [n, RESIZE_SRC_WIN_DESC_INTS] on the device, {packed pixel offset, output Hr, Wr, window origin wy0, wx0 in the
-    source's coordinates, window wh, ww, fill c0 | c1 << 8 | c2 << 16}"""
-    _lib.call("radet_resize_linear_u8_src_window", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(wdesc), n, max_dst_px, channels, _stream())
+def resize_linear_u8(src, sdesc, dst, ddesc, n, max_dst_px, channels=3, views=None):
+    """packed u8 images -> packed u8 images of the sizes of ddesc.  views: one view row per image -- the window of the
+    source (the row's fill colour outside it) that is resized, and the window of the virtual resized image that is written;
+    its h, w are ddesc's"""
+    _lib.call("radet_resize_linear_u8", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(ddesc), _views(views, n), n, max_dst_px, channels,
+              _stream())
 
 
 # ---------------------------------------------------------------------- affine augmentation (csrc/warp.hip)

@@ -1,5 +1,5 @@
-"""Scale-jitter training on the GPU: the window variants of the resize and of both mask kernels against "full transform,
-then slice" (the plain kernels and oracle/masks.py), the loader on Resize(ratio_range) + RandomCrop + Pad(size) against a host
+"""Scale-jitter training on the GPU: output windows (view rows) of the resize and of both mask kernels against "full transform,
+then slice" (the same kernels without rows and oracle/masks.py), the loader on Resize(ratio_range) + RandomCrop + Pad(size) against a host
 restatement of the reference's order fed the same per-sample seeds, the launch log, and a training run on the jitter
 config.  Every comparison is array_equal / torch.equal."""
 import json
@@ -60,6 +60,12 @@ def _plain_resize(K, src, hw):
     return dst.cpu().numpy().reshape(h, w, 3)
 
 
+def view_rows(src_hw, cases):
+    """the view rows of (Hr, Wr, y0, x0, h, w[, flip]) cases: the whole src_hw source resized to Hr x Wr, the h x w window at
+    (y0, x0) of that"""
+    return np.array([(Hr, Wr, 0, 0, *src_hw, y0, x0, h, w, *(fl or [0]), 0) for Hr, Wr, y0, x0, h, w, *fl in cases], np.int32)
+
+
 def _window_resize(K, srcs, rows, align, guard=64):
     """one launch: rows = (source index, Hr, Wr, y0, x0, h, w); returns the per-row outputs and checks the guard bytes"""
     dev = _dev()
@@ -71,10 +77,11 @@ def _window_resize(K, srcs, rows, align, guard=64):
         o += -(-h * w // align) * align
     total = o + guard
     dst = torch.full((total * 3,), GUARD, dtype=torch.uint8, device=dev)
-    K.resize_linear_u8_window(torch.from_numpy(np.concatenate([s.reshape(-1) for s in srcs])).to(dev),
-                              torch.tensor(np.array(sdesc), dtype=torch.int32, device=dev), dst,
-                              torch.tensor(np.array(wdesc), dtype=torch.int32, device=dev), len(rows),
-                              max(r[5] * r[6] for r in rows), 3)
+    views = np.concatenate([view_rows(srcs[k].shape[:2], [case]) for k, *case in rows])
+    K.resize_linear_u8(torch.from_numpy(np.concatenate([s.reshape(-1) for s in srcs])).to(dev),
+                       torch.tensor(np.array(sdesc), dtype=torch.int32, device=dev), dst,
+                       torch.tensor(np.array([d[:3] for d in wdesc]), dtype=torch.int32, device=dev), len(rows),
+                       max(r[5] * r[6] for r in rows), 3, views=torch.from_numpy(views).to(dev))
     host = dst.cpu().numpy()
     written = np.zeros(total * 3, bool)
     outs = []
@@ -163,17 +170,17 @@ def test_mask_transform_window_equals_transform_then_slice(bitmaps):
     assert host[(39, 53)][0].max() == 0 and host[(39, 53)][1].max() == 1 and host[(39, 53)][2].max() == 1
     # one launch over all cases: every mask of the stack carries its own window; the output is padded to one size
     out_hw = (max(c[4] for c in cases) + 3, max(c[5] for c in cases) + 2)
-    rows = torch.tensor(np.repeat(np.array(cases, np.int32), G, axis=0), device=dev)
-    got = K.mask_transform_window(src.repeat(len(cases), 1, 1), rows, out_hw, pad_val=9, normalize=True).cpu().numpy()
+    rows = torch.tensor(np.repeat(view_rows((MH, MW), cases), G, axis=0), device=dev)
+    got = K.mask_transform(src.repeat(len(cases), 1, 1), out_hw, views=rows, pad_val=9, normalize=True).cpu().numpy()
     for n, case in enumerate(cases):
         np.testing.assert_array_equal(got[n * G:(n + 1) * G], _want(host[case[:2]], case, out_hw, 9), err_msg=str(case))
     # unpadded, without normalisation (the flip pass over windows that are already cut)
     case = (39, 53, 5, 7, 20, 33, 1)
-    got = K.mask_transform_window(src, torch.tensor([case] * G, dtype=torch.int32, device=dev), (20, 33)).cpu().numpy()
+    got = K.mask_transform(src, (20, 33), views=torch.from_numpy(view_rows((MH, MW), [case] * G)).to(dev)).cpu().numpy()
     np.testing.assert_array_equal(got, _want(om.transform(bitmaps, resized_hw=(39, 53)), case, (20, 33)))
     # a window that leaves its virtual mask, or the destination: pad_val only
     bad = [(39, 53, 30, 0, 20, 33, 0), (39, 53, 0, 0, 21, 33, 0), (39, 53, -1, 0, 20, 33, 0)]
-    got = K.mask_transform_window(src, torch.tensor(bad, dtype=torch.int32, device=dev), (20, 33), pad_val=5)
+    got = K.mask_transform(src, (20, 33), views=torch.from_numpy(view_rows((MH, MW), bad)).to(dev), pad_val=5)
     assert bool((got == 5).all())
 
 
@@ -194,10 +201,10 @@ def test_rle_masks_window_equals_transform_then_slice():
     out_hw = (max(c[4] for c in cases) + 3, max(c[5] for c in cases) + 2)
     flips = np.repeat([bool(c[6]) for c in cases], G)
     ends, prows, mrows = rle.pack_runs([p for _ in cases for p in parts], MH, MW, flips)
-    wrows = np.repeat(np.array(cases, np.int32), G, axis=0)
-    wrows[:, 6] = 0                                            # (the flip is the mask row's)
-    got, plain = K.rle_masks_window(torch.from_numpy(ends.view(np.int32)).to(dev), torch.from_numpy(prows).to(dev),
-                                    torch.from_numpy(mrows).to(dev), torch.from_numpy(wrows).to(dev), out_hw, pad_val=9, with_plain=True)
+    wrows = np.repeat(view_rows((MH, MW), cases), G, axis=0)
+    wrows[:, 10] = 0                                           # (the flip is the mask row's)
+    got, plain = K.rle_masks(torch.from_numpy(ends.view(np.int32)).to(dev), torch.from_numpy(prows).to(dev),
+                             torch.from_numpy(mrows).to(dev), out_hw, views=torch.from_numpy(wrows).to(dev), pad_val=9, with_plain=True)
     got, plain = got.cpu().numpy(), plain.cpu().numpy()
     for n, case in enumerate(cases):
         np.testing.assert_array_equal(got[n * G:(n + 1) * G], _want(host[case[:2]], case, out_hw, 9), err_msg=str(case))
@@ -387,8 +394,7 @@ def test_cached_epoch_equals_the_first(tree):
 
 
 def test_launch_log(tree):
-    """a jitter batch launches as many kernels as the same files through the fixed-scale pipeline, the window entry points
-    where their plain counterparts stood"""
+    """a jitter batch launches what the same files launch through the fixed-scale pipeline, entry point for entry point"""
     from radet_amd import _lib
     from radet_amd.datasets.loader import sample_generators
     from radet_amd.datasets import build_dataset
@@ -431,15 +437,10 @@ def test_launch_log(tree):
         finally:
             _lib.call = call
         assert out["img"].shape == (4, 3, *CROP)
-        swap = {"radet_resize_linear_u8": "radet_resize_linear_u8_window", "radet_mask_transform": "radet_mask_transform_window",
-                "radet_rle_masks": "radet_rle_masks_window"}
-        want = list(fixed_seen)
-        want[want.index("radet_resize_linear_u8")] = swap["radet_resize_linear_u8"]        # the frames; the backgrounds stay plain
-        want = [swap[n] if n in ("radet_mask_transform", "radet_rle_masks") else n for n in want]      # both mask passes
-        assert jit_seen == want, (jit_seen, fixed_seen)
+        assert jit_seen == fixed_seen, (jit_seen, fixed_seen)
         logs[ann] = jit_seen
-    assert logs["png"].count("radet_mask_transform_window") == 2 and logs["rle"].count("radet_rle_masks_window") == 1
-    assert not any("window" in n for n in fixed_seen)
+    assert logs["png"].count("radet_mask_transform") == 2 and logs["rle"].count("radet_rle_masks") == 1      # both mask passes
+    assert not any("window" in n for n in jit_seen + fixed_seen)
 
 
 @pytest.mark.parametrize("ann", ["png", "rle"])
@@ -459,9 +460,8 @@ def test_mixed_batch_launches_what_a_windowed_batch_does(tree, ann):
         ds.pipeline.run(plans, collate=True)
     finally:
         _lib.call = call
-    mask_stage = (["radet_mask_max", "radet_mask_transform_window", "radet_mask_transform_window"] if ann == "png"
-                  else ["radet_rle_masks_window"])
-    assert seen == ["radet_resize_linear_u8_window", "radet_resize_linear_u8", *mask_stage, "radet_augment_merge_hblur",
+    mask_stage = ["radet_mask_max", "radet_mask_transform", "radet_mask_transform"] if ann == "png" else ["radet_rle_masks"]
+    assert seen == ["radet_resize_linear_u8", "radet_resize_linear_u8", *mask_stage, "radet_augment_merge_hblur",
                     "radet_augment_vblur", "radet_augment_sharp", "radet_augment_finish", "radet_assign_points"], seen
 
 

@@ -1,4 +1,4 @@
-"""Zoom augmentation on the GPU: the source-window variants of the resize and of both mask kernels against the materialised
+"""Zoom augmentation on the GPU: source windows (view rows) of the resize and of both mask kernels against the materialised
 host chain (NumPy canvas / np.pad, paste, slice, then oracle/imgproc.py and oracle/masks.py), the pipeline on Expand +
 MinIoURandomCrop + Resize against that chain built from each planned sample's recorded draws, and the launch log.  Every
 comparison is array_equal / torch.equal."""
@@ -88,6 +88,12 @@ def resize_want(sources):
     return [imgproc.resize_linear_u8(host_window(sources[k], win, FILL), (Wr, Hr)) for k, win, (Hr, Wr) in resize_rows(sources)]
 
 
+def view_rows(cases, fill=0):
+    """the view rows of (Hr, Wr, y0, x0, wh, ww, flip) cases: the wh x ww window at (y0, x0) of the source resized to Hr x Wr,
+    all of it written"""
+    return np.array([(Hr, Wr, y0, x0, wh, ww, 0, 0, Hr, Wr, fl, fill) for Hr, Wr, y0, x0, wh, ww, fl in cases], np.int32)
+
+
 def _src_window_resize(K, srcs, rows, align, fill=FILL, guard=64):
     """one launch over mixed rows; returns the per-row outputs and checks the guard bytes"""
     dev = _dev()
@@ -95,14 +101,15 @@ def _src_window_resize(K, srcs, rows, align, fill=FILL, guard=64):
     sdesc = [(soff[k], srcs[k].shape[0], srcs[k].shape[1]) for k, _, _ in rows]
     wdesc, o = [], guard
     for k, (y0, x0, wh, ww), (Hr, Wr) in rows:
-        wdesc.append((o, Hr, Wr, y0, x0, wh, ww, fill[0] | fill[1] << 8 | fill[2] << 16))
+        wdesc.append((o, Hr, Wr))
         o += -(-Hr * Wr // align) * align
     total = o + guard
     dst = torch.full((total * 3,), GUARD, dtype=torch.uint8, device=dev)
-    K.resize_linear_u8_src_window(torch.from_numpy(np.concatenate([s.reshape(-1) for s in srcs])).to(dev),
-                                  torch.tensor(np.array(sdesc), dtype=torch.int32, device=dev), dst,
-                                  torch.tensor(np.array(wdesc), dtype=torch.int32, device=dev), len(rows),
-                                  max(hw[0] * hw[1] for _, _, hw in rows), 3)
+    views = view_rows([(Hr, Wr, *win, 0) for _, win, (Hr, Wr) in rows], fill[0] | fill[1] << 8 | fill[2] << 16)
+    K.resize_linear_u8(torch.from_numpy(np.concatenate([s.reshape(-1) for s in srcs])).to(dev),
+                       torch.tensor(np.array(sdesc), dtype=torch.int32, device=dev), dst,
+                       torch.tensor(np.array(wdesc), dtype=torch.int32, device=dev), len(rows),
+                       max(hw[0] * hw[1] for _, _, hw in rows), 3, views=torch.from_numpy(views).to(dev))
     host = dst.cpu().numpy()
     written = np.zeros(total * 3, bool)
     outs = []
@@ -190,8 +197,8 @@ def test_mask_transform_src_window_equals_pad_slice_transform(bitmaps):
     assert normalised[3].sum() == 2 and normalised[1].max() == 1 and normalised[0].max() == 0
     src = torch.from_numpy(bitmaps.copy()).to(dev)
     out_hw = (max(c[0] for c in cases) + 3, max(c[1] for c in cases) + 2)
-    rows = torch.tensor(np.repeat(np.array(cases, np.int32), G, axis=0), device=dev)
-    got = K.mask_transform_src_window(src.repeat(len(cases), 1, 1), rows, out_hw, pad_val=9, normalize=True).cpu().numpy()
+    rows = torch.tensor(np.repeat(view_rows(cases), G, axis=0), device=dev)
+    got = K.mask_transform(src.repeat(len(cases), 1, 1), out_hw, views=rows, pad_val=9, normalize=True).cpu().numpy()
     for n, case in enumerate(cases):
         np.testing.assert_array_equal(got[n * G:(n + 1) * G], mask_want(normalised, case, out_hw, 9), err_msg=str(case))
     # the mask whose maximum lies outside the window: all zero inside, normalised by the maximum of the whole mask
@@ -200,12 +207,12 @@ def test_mask_transform_src_window_equals_pad_slice_transform(bitmaps):
     assert (got[n * G + 3, :Hr, :Wr] == 0).all() and (bitmaps[3, 2:MH - 3, 3:MW - 3] == 7).all()
     # without normalisation: the bytes themselves, zeros around them
     case = (40, 50, -3, -2, MH + 5, MW + 6, 1)
-    got = K.mask_transform_src_window(src, torch.tensor([case] * G, dtype=torch.int32, device=dev), (40, 52)).cpu().numpy()
+    got = K.mask_transform(src, (40, 52), views=torch.from_numpy(view_rows([case] * G)).to(dev)).cpu().numpy()
     np.testing.assert_array_equal(got, mask_want(bitmaps, case, (40, 52)))
     assert got.max() == 255
     # a row whose output does not fit the destination, or without a window: pad_val only
     bad = [(41, 50, 0, 0, MH, MW, 0), (40, 53, 0, 0, MH, MW, 0), (40, 50, 0, 0, 0, MW, 0), (0, 50, 0, 0, MH, MW, 0)]
-    got = K.mask_transform_src_window(src, torch.tensor(bad, dtype=torch.int32, device=dev), (40, 52), pad_val=5)
+    got = K.mask_transform(src, (40, 52), views=torch.from_numpy(view_rows(bad)).to(dev), pad_val=5)
     assert bool((got == 5).all())
 
 
@@ -230,13 +237,13 @@ def test_rle_masks_src_window_equals_the_bitmap_variant(with_plain):
     out_hw = (max(c[0] for c in cases) + 3, max(c[1] for c in cases) + 2)
     flips = np.repeat([bool(c[6]) for c in cases], G)
     ends, prows, mrows = rle.pack_runs([p for _ in cases for p in parts], MH, MW, flips)
-    wrows = np.repeat(np.array(cases, np.int32), G, axis=0)
-    bitmap = K.mask_transform_src_window(torch.from_numpy(decoded).to(dev).repeat(len(cases), 1, 1), torch.from_numpy(wrows).to(dev),
-                                         out_hw, pad_val=9, normalize=True).cpu().numpy()
-    wrows[:, 6] = 0                                            # (the flip is the mask row's)
-    res = K.rle_masks_src_window(torch.from_numpy(ends.view(np.int32)).to(dev), torch.from_numpy(prows).to(dev),
-                                 torch.from_numpy(mrows).to(dev), torch.from_numpy(wrows).to(dev), out_hw, pad_val=9,
-                                 with_plain=with_plain)
+    wrows = np.repeat(view_rows(cases), G, axis=0)
+    bitmap = K.mask_transform(torch.from_numpy(decoded).to(dev).repeat(len(cases), 1, 1), out_hw, views=torch.from_numpy(wrows).to(dev),
+                              pad_val=9, normalize=True).cpu().numpy()
+    wrows[:, 10] = 0                                           # (the flip is the mask row's)
+    res = K.rle_masks(torch.from_numpy(ends.view(np.int32)).to(dev), torch.from_numpy(prows).to(dev),
+                      torch.from_numpy(mrows).to(dev), out_hw, views=torch.from_numpy(wrows).to(dev), pad_val=9,
+                      with_plain=with_plain)
     got, plain = (res[0].cpu().numpy(), res[1].cpu().numpy()) if with_plain else (res.cpu().numpy(), None)
     np.testing.assert_array_equal(got, bitmap)
     for n, case in enumerate(cases):
@@ -391,8 +398,7 @@ def test_pipeline_equals_the_materialised_host_chain(tree, chains, variant):
 
 @pytest.mark.parametrize("ann", ["png", "rle"])
 def test_launch_log(tree, ann):
-    """a zoom batch launches as many kernels as the same files through the fixed-scale pipeline, the source-window entry
-    points where their plain counterparts stood"""
+    """a zoom batch launches what the same files launch through the fixed-scale pipeline, entry point for entry point"""
     from radet_amd import _lib
     from radet_amd.datasets.loader import sample_generators
     zoom, fixed = _dataset(tree, ann=ann), _dataset(tree, ann=ann, zoom=False)
@@ -425,14 +431,9 @@ def test_launch_log(tree, ann):
     finally:
         _lib.call = call
     assert out["img"].shape == (4, 3, *OUT)
-    swap = {"radet_resize_linear_u8": "radet_resize_linear_u8_src_window", "radet_mask_transform": "radet_mask_transform_src_window",
-            "radet_rle_masks": "radet_rle_masks_src_window"}
-    want = list(fixed_seen)
-    want[want.index("radet_resize_linear_u8")] = swap["radet_resize_linear_u8"]        # the frames; the backgrounds stay plain
-    want = [swap[n] if n in ("radet_mask_transform", "radet_rle_masks") else n for n in want]      # both mask passes
-    assert zoom_seen == want and len(zoom_seen) == len(fixed_seen), (zoom_seen, fixed_seen)
-    assert zoom_seen.count("radet_mask_transform_src_window" if ann == "png" else "radet_rle_masks_src_window") == (2 if ann == "png" else 1)
-    assert not any("window" in n for n in fixed_seen)
+    assert zoom_seen == fixed_seen, (zoom_seen, fixed_seen)
+    assert zoom_seen.count("radet_mask_transform" if ann == "png" else "radet_rle_masks") == (2 if ann == "png" else 1)   # both mask passes
+    assert not any("window" in n for n in zoom_seen + fixed_seen)
 
 
 def test_mix_and_mask_free_pipelines_take_source_windows(tree):
