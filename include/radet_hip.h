@@ -376,9 +376,26 @@ int radet_nhwc_to_nchw(const float* x, float* y, int B, int C, int H, int W, voi
  *  (row strides let the gradients land in zero-padded buffers that the dgrad GEMM consumes directly; the
  *  sparse dreg_u / diou rows of non-positive points are zero-filled here); dscales [nlvl];
  *  optional dumps (may be NULL): labels_out i64 [R], bbox_targets_out [R,4].
- *  flags bit 0: reg_u holds the head's bbox_pred AFTER Scale + ReLU (the tensor `RADetHead.loss` receives,
- *  radet_head.py:173-181; pass scales = 1): dreg_u is then the gradient w.r.t. that tensor (no ReLU mask).
+ *  flags = RADET_HEAD_LOSS_POSTACT (bit 0) | kind << RADET_HEAD_LOSS_KIND_SHIFT (bits 1-3):
+ *    POSTACT: reg_u holds the head's bbox_pred AFTER Scale + ReLU (the tensor `RADetHead.loss` receives,
+ *    radet_head.py:173-181; pass scales = 1): dreg_u is then the gradient w.r.t. that tensor (no ReLU mask).
+ *    kind: the `loss_bbox` module, one of RADET_BOX_LOSS_* (0 = GIoU, so flags 0 / 1 keep their earlier meaning);
+ *    a value without a kernel returns RADET_ERR_ARG before anything is launched.  giou_eps is that module's `eps`
+ *    whatever the kind.  The IoU branch does not depend on the kind: its target is bbox_overlaps' I / max(U, 1e-6)
+ *    (radet_head.py:267), the box weight max(iou, 1e-12) * pw.  (Kind GIoU shares that union with its loss, as it
+ *    always did: there the bound is giou_eps, the same number at GIoULoss' default.)
  *  ws: int32 workspace of radet_head_loss_ws_ints(R) ints. */
+#define RADET_HEAD_LOSS_POSTACT 1
+#define RADET_HEAD_LOSS_KIND_SHIFT 1
+#define RADET_HEAD_LOSS_KIND_MASK (7 << RADET_HEAD_LOSS_KIND_SHIFT)
+/* box regression losses (radet/models/losses/iou_loss.py): GIoULoss, IoULoss(linear=False) = -log(iou),
+ * IoULoss(linear=True) = 1 - iou, DIoULoss, CIoULoss */
+#define RADET_BOX_LOSS_GIOU 0
+#define RADET_BOX_LOSS_IOU 1
+#define RADET_BOX_LOSS_IOU_LINEAR 2
+#define RADET_BOX_LOSS_DIOU 3
+#define RADET_BOX_LOSS_CIOU 4
+#define RADET_BOX_LOSS_KINDS 5
 int radet_head_loss_ws_ints(int R);
 int radet_head_loss(const float* cls, const float* reg_u, const float* iou, const float* scales,
                     const float* gt_boxes, const int64_t* gt_labels, const int* gt_off, const int64_t* p2g,
@@ -712,6 +729,15 @@ int radet_giou_loss(const float* pred, const float* target, const float* weight,
 int radet_giou_loss_bwd(const float* pred, const float* target, const float* weight, size_t N, float eps,
                         const float* grad_elem, const float* grad_scalar, const float* avg_factor, float scale, float* dpred,
                         void* stream);
+/* The box regression losses by kind (RADET_BOX_LOSS_*; iou_loss.py:11-34,82-213), same argument layout, partial sums and
+ * gradient contract as the giou pair; kind GIoU runs the giou kernels themselves.  eps = the module's `eps` (IoU: the
+ * clamp below the log, on top of bbox_overlaps' own 1e-6; DIoU / CIoU: added to the union, c^2 and the heights);
+ * hp1 is a spare hyper-parameter, pass 0.  An unknown kind returns RADET_ERR_ARG before any launch. */
+int radet_box_loss(int kind, const float* pred, const float* target, const float* weight, size_t N, float eps, float hp1,
+                   float* loss_elem, float elem_scale, float* partials, void* stream);
+int radet_box_loss_bwd(int kind, const float* pred, const float* target, const float* weight, size_t N, float eps, float hp1,
+                       const float* grad_elem, const float* grad_scalar, const float* avg_factor, float scale, float* dpred,
+                       void* stream);
 /* multiclass_nms' score filter (radet/core/post_processing/bbox_nms.py:54-56): idx[0..count) = ascending indices i
  * with scores[i] > thr (torch.nonzero order); one workgroup, ordered ballot-prefix compaction. */
 int radet_threshold_compact(const float* scores, size_t n, float thr, int64_t* idx, int* count, void* stream);

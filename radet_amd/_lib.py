@@ -150,6 +150,8 @@ SIGNATURES = {
     "radet_bce_logits_loss_bwd": (_i, [_p, _p, _p, _i, _sz, _i, _p, _p, _p, _f, _p, _p]),
     "radet_giou_loss": (_i, [_p, _p, _p, _sz, _f, _p, _f, _p, _p]),
     "radet_giou_loss_bwd": (_i, [_p, _p, _p, _sz, _f, _p, _p, _p, _f, _p, _p]),
+    "radet_box_loss": (_i, [_i, _p, _p, _p, _sz, _f, _f, _p, _f, _p, _p]),
+    "radet_box_loss_bwd": (_i, [_i, _p, _p, _p, _sz, _f, _f, _p, _p, _p, _f, _p, _p]),
     "radet_threshold_compact": (_i, [_p, _sz, _f, _p, _p, _p]),
     "radet_sqnorm_partials": (_i, [_p, _sz, _p, _i, _p]),
     "radet_adamw_step": (_i, [_p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _i, _f, _f, _p, _i, _p, _p]),

@@ -8,6 +8,7 @@
 // -ffp-contract=off), so IoU / TBLR results equal the PyTorch-CPU ones bit for bit.
 #include "common.h"
 #include "../../include/radet_hip.h"
+#include "box_loss.h"
 
 // ------------------------------------------------------------------------------------------------ overlaps
 // iou2d_calculator.py:116-158
@@ -310,6 +311,33 @@ __global__ __launch_bounds__(256) void giou_elem_kernel(const float* __restrict_
     if (!BWD) block_partial(acc, partials);
 }
 
+// IoU (-log / linear), DIoU, CIoU losses per aligned pair (iou_loss.py:11-34,101-213; box_loss.h) and their gradient
+// w.r.t. pred: the giou kernel's layout, partial sums and gradient contract
+template <int KIND, bool BWD>
+__global__ __launch_bounds__(256) void box_loss_elem_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                            const float* __restrict__ weight, size_t N, float eps,
+                                                            float* __restrict__ out, float* __restrict__ partials,
+                                                            const float* __restrict__ grad_elem, const float* __restrict__ grad_scalar,
+                                                            const float* __restrict__ avg_factor, float scale) {
+    const float gs = BWD ? bwd_scale(grad_scalar, avg_factor, scale) : 0.f;
+    float acc = 0.f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (size_t)gridDim.x * 256) {
+        const float4 pv = *reinterpret_cast<const float4*>(pred + i * 4), tv = *reinterpret_cast<const float4*>(target + i * 4);
+        const Box4 p = {pv.x, pv.y, pv.z, pv.w}, t = {tv.x, tv.y, tv.z, tv.w};
+        const float wt = weight ? weight[i] : 1.f;
+        if (BWD) {
+            float4 g;
+            box_loss_pair<KIND, true>(p, t, eps, wt * (grad_elem ? grad_elem[i] * gs : gs), &g);
+            *reinterpret_cast<float4*>(out + i * 4) = g;
+        } else {
+            const float e = box_loss_pair<KIND, false>(p, t, eps, 0.f, nullptr) * wt;
+            if (out) out[i] = e * scale;
+            acc += e;
+        }
+    }
+    if (!BWD) block_partial(acc, partials);
+}
+
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ partials, int n,
                                                             const float* __restrict__ avg_factor, float scale,
                                                             float* __restrict__ out) {
@@ -391,6 +419,42 @@ extern "C" int radet_giou_loss_bwd(const float* pred, const float* target, const
     if (N == 0) return RADET_OK;
     hipLaunchKernelGGL(giou_elem_kernel<true>, dim3(grid_for(N)), dim3(256), 0, (hipStream_t)stream, pred, target, weight, N, eps,
                        dpred, nullptr, grad_elem, grad_scalar, avg_factor, scale);
+    return radet_check_launch();
+}
+
+#define BOX_LOSS_LAUNCH(KIND, BWD, grid, ...) \
+    hipLaunchKernelGGL((box_loss_elem_kernel<KIND, BWD>), dim3(grid), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
+
+extern "C" int radet_box_loss(int kind, const float* pred, const float* target, const float* weight, size_t N, float eps,
+                              float hp1, float* loss_elem, float elem_scale, float* partials, void* stream) {
+    (void)hp1;
+    if (kind == RADET_BOX_LOSS_GIOU) return radet_giou_loss(pred, target, weight, N, eps, loss_elem, elem_scale, partials, stream);
+    if (kind < 0 || kind >= RADET_BOX_LOSS_KINDS) return RADET_ERR_ARG;
+    const int grid = grid_for(N, LOSS_PARTIALS);
+    switch (kind) {
+        case RADET_BOX_LOSS_IOU: BOX_LOSS_LAUNCH(RADET_BOX_LOSS_IOU, false, grid, pred, target, weight, N, eps, loss_elem, partials, nullptr, nullptr, nullptr, elem_scale); break;
+        case RADET_BOX_LOSS_IOU_LINEAR: BOX_LOSS_LAUNCH(RADET_BOX_LOSS_IOU_LINEAR, false, grid, pred, target, weight, N, eps, loss_elem, partials, nullptr, nullptr, nullptr, elem_scale); break;
+        case RADET_BOX_LOSS_DIOU: BOX_LOSS_LAUNCH(RADET_BOX_LOSS_DIOU, false, grid, pred, target, weight, N, eps, loss_elem, partials, nullptr, nullptr, nullptr, elem_scale); break;
+        default: BOX_LOSS_LAUNCH(RADET_BOX_LOSS_CIOU, false, grid, pred, target, weight, N, eps, loss_elem, partials, nullptr, nullptr, nullptr, elem_scale); break;
+    }
+    return radet_check_launch();
+}
+
+extern "C" int radet_box_loss_bwd(int kind, const float* pred, const float* target, const float* weight, size_t N, float eps,
+                                  float hp1, const float* grad_elem, const float* grad_scalar, const float* avg_factor,
+                                  float scale, float* dpred, void* stream) {
+    (void)hp1;
+    if (kind == RADET_BOX_LOSS_GIOU)
+        return radet_giou_loss_bwd(pred, target, weight, N, eps, grad_elem, grad_scalar, avg_factor, scale, dpred, stream);
+    if (kind < 0 || kind >= RADET_BOX_LOSS_KINDS) return RADET_ERR_ARG;
+    if (N == 0) return RADET_OK;
+    const int grid = grid_for(N);
+    switch (kind) {
+        case RADET_BOX_LOSS_IOU: BOX_LOSS_LAUNCH(RADET_BOX_LOSS_IOU, true, grid, pred, target, weight, N, eps, dpred, nullptr, grad_elem, grad_scalar, avg_factor, scale); break;
+        case RADET_BOX_LOSS_IOU_LINEAR: BOX_LOSS_LAUNCH(RADET_BOX_LOSS_IOU_LINEAR, true, grid, pred, target, weight, N, eps, dpred, nullptr, grad_elem, grad_scalar, avg_factor, scale); break;
+        case RADET_BOX_LOSS_DIOU: BOX_LOSS_LAUNCH(RADET_BOX_LOSS_DIOU, true, grid, pred, target, weight, N, eps, dpred, nullptr, grad_elem, grad_scalar, avg_factor, scale); break;
+        default: BOX_LOSS_LAUNCH(RADET_BOX_LOSS_CIOU, true, grid, pred, target, weight, N, eps, dpred, nullptr, grad_elem, grad_scalar, avg_factor, scale); break;
+    }
     return radet_check_launch();
 }
 

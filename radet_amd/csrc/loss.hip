@@ -6,9 +6,11 @@
 //            ordered compaction of the positive rows, num_pos = sum of their weights.
 //   focal  : HBM-streaming over [R, C]; per-workgroup partial sums (deterministic two-stage reduction).
 //   pos    : 1 workgroup over the P positive rows: TBLR encode/decode, aligned IoU (detached weight),
-//            GIoU loss, BCE-with-logits on the IoU logit, analytic backward incl. Scale/ReLU of atss_reg.
+//            box loss (GIoU, or IoU / DIoU / CIoU of box_loss.h: one kernel instantiation per kind),
+//            BCE-with-logits on the IoU logit, analytic backward incl. Scale/ReLU of atss_reg.
 #include "common.h"
 #include "../../include/radet_hip.h"
+#include "box_loss.h"
 
 struct LossLevels {
     int n;
@@ -217,6 +219,11 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return r;
 }
 
+// KIND = RADET_BOX_LOSS_*: the GIoU instantiation is the kernel as it stood before the other kinds existed (the
+// IoU / DIoU / CIoU arithmetic, CIoU's atan and division chain included, lives in the other instantiations only).
+// Whatever the kind, the IoU branch's target and the box weight come from bbox_overlaps' I / max(U, 1e-6); the GIoU
+// instantiation shares that union with its loss, so there the bound is the loss's eps (the same number by default).
+template <int KIND>
 __global__ __launch_bounds__(256) void pos_loss_kernel(const float* __restrict__ reg_u, const float* __restrict__ iou_logit,
                                                        const float* __restrict__ scales,
                                                        const float* __restrict__ gt_boxes,
@@ -286,7 +293,7 @@ __global__ __launch_bounds__(256) void pos_loss_kernel(const float* __restrict__
             const float iw = fmaxf(dw, 0.f), ih = fmaxf(dh, 0.f);
             const float I = iw * ih;
             const float Uraw = area1 + area2 - I;
-            const float U = fmaxf(Uraw, eps);
+            const float U = fmaxf(Uraw, KIND == RADET_BOX_LOSS_GIOU ? eps : BOX_OVERLAPS_EPS);
             const float iou = I / U;
             const float eltx = fminf(px1, tx1), elty = fminf(py1, ty1), erbx = fmaxf(px2, tx2), erby = fmaxf(py2, ty2);
             const float dew = erbx - eltx, deh = erby - elty;
@@ -296,29 +303,38 @@ __global__ __launch_bounds__(256) void pos_loss_kernel(const float* __restrict__
             const float giou = iou - (E - U) / E;
             const float wgt = fmaxf(iou, 1e-12f) * pwt;
             const float x = iou_logit[r];
+            const Box4 pb = {px1, py1, px2, py2}, tb = {tx1, ty1, tx2, ty2};
             if (pass == 0) {
                 sw += wgt;
-                swl += wgt * (1.f - giou);
+                if constexpr (KIND == RADET_BOX_LOSS_GIOU) swl += wgt * (1.f - giou);
+                else swl += wgt * box_loss_pair<KIND, false>(pb, tb, eps, 0.f, nullptr);
                 sb += pwt * (fmaxf(x, 0.f) - x * iou + log1pf(expf(-fabsf(x))));
                 sp += pwt;
             } else {
-                // d loss_bbox / d giou
-                const float gg = -lbw * wgt * inv_sw * g1;
-                const float g_E = -gg * U / (E * E);
-                float g_U = gg / E - gg * I / (U * U);
-                float g_I = gg / U;
-                const float g_Uraw = g_U * sel_gt(Uraw, eps);
-                const float g_area1 = g_Uraw;
-                g_I -= g_Uraw;
-                const float g_dw = g_I * ih * (dw >= 0.f ? 1.f : 0.f);
-                const float g_dh = g_I * iw * (dh >= 0.f ? 1.f : 0.f);
-                const float g_Eraw = g_E * sel_gt(Eraw, eps);
-                const float g_dew = g_Eraw * eh * (dew >= 0.f ? 1.f : 0.f);
-                const float g_deh = g_Eraw * ew * (deh >= 0.f ? 1.f : 0.f);
-                float gx1 = -g_dw * sel_gt(px1, tx1) - g_dew * sel_lt(px1, tx1) - g_area1 * (py2 - py1);
-                float gy1 = -g_dh * sel_gt(py1, ty1) - g_deh * sel_lt(py1, ty1) - g_area1 * (px2 - px1);
-                float gx2 = g_dw * sel_lt(px2, tx2) + g_dew * sel_gt(px2, tx2) + g_area1 * (py2 - py1);
-                float gy2 = g_dh * sel_lt(py2, ty2) + g_deh * sel_gt(py2, ty2) + g_area1 * (px2 - px1);
+                float gx1, gy1, gx2, gy2;
+                if constexpr (KIND == RADET_BOX_LOSS_GIOU) {
+                    // d loss_bbox / d giou
+                    const float gg = -lbw * wgt * inv_sw * g1;
+                    const float g_E = -gg * U / (E * E);
+                    float g_U = gg / E - gg * I / (U * U);
+                    float g_I = gg / U;
+                    const float g_Uraw = g_U * sel_gt(Uraw, eps);
+                    const float g_area1 = g_Uraw;
+                    g_I -= g_Uraw;
+                    const float g_dw = g_I * ih * (dw >= 0.f ? 1.f : 0.f);
+                    const float g_dh = g_I * iw * (dh >= 0.f ? 1.f : 0.f);
+                    const float g_Eraw = g_E * sel_gt(Eraw, eps);
+                    const float g_dew = g_Eraw * eh * (dew >= 0.f ? 1.f : 0.f);
+                    const float g_deh = g_Eraw * ew * (deh >= 0.f ? 1.f : 0.f);
+                    gx1 = -g_dw * sel_gt(px1, tx1) - g_dew * sel_lt(px1, tx1) - g_area1 * (py2 - py1);
+                    gy1 = -g_dh * sel_gt(py1, ty1) - g_deh * sel_lt(py1, ty1) - g_area1 * (px2 - px1);
+                    gx2 = g_dw * sel_lt(px2, tx2) + g_dew * sel_gt(px2, tx2) + g_area1 * (py2 - py1);
+                    gy2 = g_dh * sel_lt(py2, ty2) + g_deh * sel_gt(py2, ty2) + g_area1 * (px2 - px1);
+                } else {
+                    float4 gb;
+                    box_loss_pair<KIND, true>(pb, tb, eps, lbw * wgt * inv_sw * g1, &gb);
+                    gx1 = gb.x; gy1 = gb.y; gx2 = gb.z; gy2 = gb.w;
+                }
                 // decode backward: top<-y1(-), bottom<-y2, left<-x1(-), right<-x2 ; times normalizer*size
                 const float k8 = 0.125f * hw8;
                 const float gp0 = -gy1 * k8, gp1 = gy2 * k8, gp2 = -gx1 * k8, gp3 = gx2 * k8;
@@ -407,6 +423,8 @@ extern "C" int radet_head_loss(const float* cls, const float* reg_u, const float
     if (rc) return rc;
     const int R = L.row_off[nlvl], N = L.pt_off[nlvl];
     if (dcls_ld < num_classes || dreg_ld < 4 || (dreg_ld & 3) || diou_ld < 1) return RADET_ERR_ARG;
+    const int kind = (flags & RADET_HEAD_LOSS_KIND_MASK) >> RADET_HEAD_LOSS_KIND_SHIFT;
+    if (kind >= RADET_BOX_LOSS_KINDS) return RADET_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(loss_prep_rows_kernel, dim3((R + LP_BLK - 1) / LP_BLK), dim3(LP_BLK), 0, st, gt_labels, gt_boxes,
                        gt_off, p2g, pw, L, B, N, R, num_classes, labels_out, bbox_targets_out, ws);
@@ -417,9 +435,18 @@ extern "C" int radet_head_loss(const float* cls, const float* reg_u, const float
     hipLaunchKernelGGL(focal_kernel, dim3(fb), dim3(256), 0, st, cls, gt_labels, gt_off, p2g, pw, L, B, N, R, num_classes,
                        alpha, gamma, grad_scale, dcls, dcls_ld, ws);
     hipLaunchKernelGGL(zero_sparse_kernel, dim3((R + 255) / 256), dim3(256), 0, st, dreg_u, dreg_ld, diou, diou_ld, R);
-    hipLaunchKernelGGL(pos_loss_kernel, dim3(1), dim3(256), 0, st, reg_u, iou, scales, gt_boxes, gt_off, p2g, pw, L, B, N,
-                       R, loss_bbox_weight, giou_eps, grad_scale, losses, dreg_u, dreg_ld, diou, diou_ld, dscales, ws,
-                       fb, flags & 1);
+#define POS_LOSS_LAUNCH(KIND)                                                                                             \
+    hipLaunchKernelGGL(pos_loss_kernel<KIND>, dim3(1), dim3(256), 0, st, reg_u, iou, scales, gt_boxes, gt_off, p2g, pw, L, B, \
+                       N, R, loss_bbox_weight, giou_eps, grad_scale, losses, dreg_u, dreg_ld, diou, diou_ld, dscales, ws, fb, \
+                       flags & RADET_HEAD_LOSS_POSTACT)
+    switch (kind) {
+        case RADET_BOX_LOSS_GIOU: POS_LOSS_LAUNCH(RADET_BOX_LOSS_GIOU); break;
+        case RADET_BOX_LOSS_IOU: POS_LOSS_LAUNCH(RADET_BOX_LOSS_IOU); break;
+        case RADET_BOX_LOSS_IOU_LINEAR: POS_LOSS_LAUNCH(RADET_BOX_LOSS_IOU_LINEAR); break;
+        case RADET_BOX_LOSS_DIOU: POS_LOSS_LAUNCH(RADET_BOX_LOSS_DIOU); break;
+        default: POS_LOSS_LAUNCH(RADET_BOX_LOSS_CIOU); break;
+    }
+#undef POS_LOSS_LAUNCH
     return radet_check_launch();
 }
 

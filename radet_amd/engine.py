@@ -1236,12 +1236,14 @@ class Engine:
         return torch.stack([t.reshape(()) for t in ts]).contiguous()
 
     def loss(self, gt_boxes, gt_labels, gt_off, p2g, pw, grad_scale=None, alpha=0.25, gamma=2.0, lbw=2.0,
-             labels_out=None, tgt_out=None):
+             labels_out=None, tgt_out=None, box_kind="giou", box_eps=1e-6):
+        """box_kind / box_eps: the head's `loss_bbox` (kernels.BOX_LOSS_KINDS) and its eps"""
         b = self.buf
         dri = b["dregiou"]
         K.head_loss(b["cls"], b["reg_u"], b["iou"], self.scales_tensor(), gt_boxes, gt_labels, gt_off, p2g, pw, self.ldesc,
-                    self.nlvl, self.B, self.num_classes, alpha, gamma, lbw, 1e-6, grad_scale, self.losses, b["dcls"],
-                    self.cls_pad, dri, 16, dri.view(-1)[4:], 16, self.dscales, self.loss_ws, labels_out, tgt_out)
+                    self.nlvl, self.B, self.num_classes, alpha, gamma, lbw, box_eps, grad_scale, self.losses, b["dcls"],
+                    self.cls_pad, dri, 16, dri.view(-1)[4:], 16, self.dscales, self.loss_ws, labels_out, tgt_out,
+                    flags=K.head_loss_flags(box_kind))
         if self.h2:       # the predictors' dgrad / wgrad scale their dy operand by its largest magnitude
             K.absmax(b["dcls"], K.amax_slot(b["dcls"]))
             K.absmax(dri, K.amax_slot(dri))

@@ -1441,6 +1441,26 @@ def giou_loss_bwd(pred, target, weight, N, eps, grad_elem, grad_scalar, avg_fact
               _ptr(grad_scalar), _ptr(avg_factor), scale, _ptr(dpred), _stream())
 
 
+# the `loss_bbox` kinds (RADET_BOX_LOSS_* of include/radet_hip.h); radet_head_loss takes one in flags bits 1-3
+BOX_LOSS_KINDS = dict(giou=0, iou=1, iou_linear=2, diou=3, ciou=4)
+HEAD_LOSS_POSTACT = 1
+HEAD_LOSS_KIND_SHIFT = 1
+
+
+def head_loss_flags(kind="giou", postact=False):
+    return (HEAD_LOSS_POSTACT if postact else 0) | (BOX_LOSS_KINDS[kind] << HEAD_LOSS_KIND_SHIFT)
+
+
+def box_loss(kind, pred, target, weight, N, eps, elem, partials, elem_scale=1.0, hp1=0.0):
+    _lib.call("radet_box_loss", BOX_LOSS_KINDS[kind], _ptr(pred), _ptr(target), _ptr(weight), C.c_size_t(N), eps, hp1,
+              _ptr(elem), elem_scale, _ptr(partials), _stream())
+
+
+def box_loss_bwd(kind, pred, target, weight, N, eps, grad_elem, grad_scalar, avg_factor, scale, dpred, hp1=0.0):
+    _lib.call("radet_box_loss_bwd", BOX_LOSS_KINDS[kind], _ptr(pred), _ptr(target), _ptr(weight), C.c_size_t(N), eps, hp1,
+              _ptr(grad_elem), _ptr(grad_scalar), _ptr(avg_factor), scale, _ptr(dpred), _stream())
+
+
 def threshold_compact(scores, thr, idx, count):
     _lib.call("radet_threshold_compact", _ptr(scores), C.c_size_t(scores.numel()), thr, _ptr(idx), _ptr(count), _stream())
 

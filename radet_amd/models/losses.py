@@ -1,8 +1,9 @@
-"""FocalLoss / GIoULoss / CrossEntropyLoss with the reference's constructors and `forward` signatures
-(radet/models/losses/{focal_loss.py:90-157, iou_loss.py:320-354, cross_entropy_loss.py:128-201}, reduction rules of
-losses/utils.py:24-51), evaluated by the stand-alone HIP loss kernels (csrc/boxops.hip) with hand-written
-backward passes (torch.autograd.Function).  Inside the detector's train step the three losses run fused in
+"""FocalLoss / IoULoss / GIoULoss / DIoULoss / CIoULoss / CrossEntropyLoss with the reference's constructors and `forward`
+signatures (radet/models/losses/{focal_loss.py:90-157, iou_loss.py:216-282,320-430, cross_entropy_loss.py:128-201},
+reduction rules of losses/utils.py:24-51), evaluated by the stand-alone HIP loss kernels (csrc/boxops.hip) with
+hand-written backward passes (torch.autograd.Function).  Inside the detector's train step the three losses run fused in
 `radet_head_loss`; these modules serve callers that use a loss on its own (e.g. `RADetHead.loss_cls(...)`).
+BoundedIoULoss is not registered: its per-coordinate [n, 4] loss cannot take the [n] weight RADetHead.loss passes.
 
 Inputs may live on the host or the GPU; the arithmetic always runs on the GPU and the result comes back on the input's
 device.  There is no CPU fallback."""
@@ -54,7 +55,8 @@ class _ElemLoss(torch.autograd.Function):
         dev = _dev()
         x = _f32(pred, dev)
         shape = tuple(pred.shape)
-        if kind == "giou":
+        box = kind in K.BOX_LOSS_KINDS
+        if box:
             N, C = x.shape[0], 1
             x = x.reshape(N, 4)
             tgt = _f32(target, dev).reshape(N, 4)
@@ -68,20 +70,22 @@ class _ElemLoss(torch.autograd.Function):
         w = None if weight is None else _f32(weight, dev)
         avg = _avg_tensor(avg_factor if reduction == "mean" else None, dev)
         reduce_, scale = _resolve(reduction, avg_factor, n_elem, loss_weight)
-        elem = None if reduce_ else torch.empty(N if kind == "giou" else (N, C), device=dev)
+        elem = None if reduce_ else torch.empty(N if box else (N, C), device=dev)
         partials = torch.empty(K.loss_partials(n_elem), device=dev) if reduce_ else None
         if kind == "focal":
             K.sigmoid_focal_loss(x, tgt, w, wcols, N, C, hp["gamma"], hp["alpha"], elem, partials, 1.0 if reduce_ else scale)
         elif kind == "bce":
             K.bce_logits_loss(x, tgt, w, wcols, N, C, elem, partials, 1.0 if reduce_ else scale)
-        else:
+        elif kind == "giou":
             K.giou_loss(x, tgt, w, N, hp["eps"], elem, partials, 1.0 if reduce_ else scale)
+        else:
+            K.box_loss(kind, x, tgt, w, N, hp["eps"], elem, partials, 1.0 if reduce_ else scale)
         if reduce_:
             out = torch.empty(1, device=dev)
             K.loss_finalize(partials, avg, scale, out)
             out = out.reshape(())
         else:
-            out = elem.reshape(shape[:-1] if kind == "giou" else shape)
+            out = elem.reshape(shape[:-1] if box else shape)
         ctx.save_for_backward(x, tgt, w if w is not None else x.new_empty(0), avg if avg is not None else x.new_empty(0))
         ctx.meta = (kind, wcols, N, C, reduce_, scale, hp, shape, src, w is not None, avg is not None)
         return out.to(src)
@@ -100,8 +104,10 @@ class _ElemLoss(torch.autograd.Function):
             K.sigmoid_focal_loss_bwd(x, tgt, w, wcols, N, C, hp["gamma"], hp["alpha"], ge, gs, avg, scale, dx)
         elif kind == "bce":
             K.bce_logits_loss_bwd(x, tgt, w, wcols, N, C, ge, gs, avg, scale, dx)
-        else:
+        elif kind == "giou":
             K.giou_loss_bwd(x, tgt, w, N, hp["eps"], ge, gs, avg, scale, dx)
+        else:
+            K.box_loss_bwd(kind, x, tgt, w, N, hp["eps"], ge, gs, avg, scale, dx)
         return (dx.reshape(shape).to(src),) + (None,) * 8
 
 
@@ -132,23 +138,69 @@ class FocalLoss(nn.Module):
                                dict(gamma=float(self.gamma), alpha=float(self.alpha)))
 
 
-@LOSSES.register_module()
-class GIoULoss(nn.Module):
+class _BoxLoss(nn.Module):
+    """The forward contract the reference's box regression losses share (iou_loss.py:328-354 and its siblings)."""
+    kind = None                # _ElemLoss kind == the fused head loss's kind (kernels.BOX_LOSS_KINDS)
+    zero_on_none = True        # all-zero weights return 0 under every reduction (IoULoss: not under 'none')
+
     def __init__(self, eps=1e-6, reduction="mean", loss_weight=1.0):
         super().__init__()
         self.eps, self.reduction, self.loss_weight = eps, reduction, loss_weight
 
+    def box_loss_kind(self):
+        return self.kind
+
     def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kwargs):
         """pred / target [n, 4] boxes (x1, y1, x2, y2), weight [n] (or [n, 4], averaged like the reference)"""
-        if weight is not None and not torch.any(weight > 0):          # iou_loss.py:335-336 (host sync there too)
-            return pred.sum() * 0.0
         assert reduction_override in (None, "none", "mean", "sum")
         reduction = reduction_override if reduction_override else self.reduction
+        if weight is not None and not torch.any(weight > 0) and (self.zero_on_none or reduction != "none"):
+            return pred.sum() * 0.0                                    # iou_loss.py:264-266,335-336 (host sync there too)
         if weight is not None and weight.dim() > 1:
             assert weight.shape == pred.shape
             weight = weight.mean(-1)
-        return _ElemLoss.apply(pred, "giou", target, weight, 1 if weight is not None else 0, reduction, avg_factor,
-                               self.loss_weight, dict(eps=float(self.eps)))
+        return _ElemLoss.apply(pred, self.box_loss_kind(), target, weight, 1 if weight is not None else 0, reduction,
+                               avg_factor, self.loss_weight, dict(eps=float(self.eps)))
+
+
+@LOSSES.register_module()
+class IoULoss(_BoxLoss):
+    """-log(iou), or 1 - iou with linear=True; iou = bbox_overlaps(is_aligned=True).clamp(min=eps)"""
+    zero_on_none = False
+
+    def __init__(self, linear=False, eps=1e-6, reduction="mean", loss_weight=1.0):
+        super().__init__(eps, reduction, loss_weight)
+        self.linear = linear
+
+    def box_loss_kind(self):
+        return "iou_linear" if self.linear else "iou"
+
+
+@LOSSES.register_module()
+class GIoULoss(_BoxLoss):
+    kind = "giou"
+
+
+@LOSSES.register_module()
+class DIoULoss(_BoxLoss):
+    kind = "diou"
+
+
+@LOSSES.register_module()
+class CIoULoss(_BoxLoss):
+    kind = "ciou"
+
+
+def fused_box_loss(module):
+    """(kind, eps) of a `loss_bbox` module for the fused head loss.  Only the registered classes themselves qualify: a
+    subclass may compute anything, and the fused step would not know."""
+    if type(module) not in (IoULoss, GIoULoss, DIoULoss, CIoULoss):
+        raise NotImplementedError(f"loss_bbox of type {type(module).__name__} has no kernel in the fused head loss "
+                                  "(IoULoss, GIoULoss, DIoULoss and CIoULoss have)")
+    if module.reduction != "mean":
+        raise NotImplementedError(f"loss_bbox {type(module).__name__}(reduction={module.reduction!r}): the fused head "
+                                  "loss implements reduction='mean' with the head's avg_factor")
+    return module.box_loss_kind(), float(module.eps)
 
 
 @LOSSES.register_module()

@@ -340,9 +340,12 @@ class DetectorRuntime:
     loss_weights = None      # device f32[3] = (loss_cls.loss_weight, 1, loss_iou.loss_weight) when either differs from 1
 
     def set_loss_from_head(self, head):
-        """Take focal alpha / gamma and the three loss weights from the head's loss modules (config values)."""
+        """Take focal alpha / gamma, the box loss's kind and eps and the three loss weights from the head's loss modules
+        (config values).  A `loss_bbox` the fused head loss has no kernel for raises NotImplementedError."""
+        from .models.losses import fused_box_loss
+        kind, eps = fused_box_loss(head.loss_bbox)
         self.loss_hparams = dict(alpha=float(head.loss_cls.alpha), gamma=float(head.loss_cls.gamma),
-                                 lbw=float(head.loss_bbox.loss_weight))
+                                 lbw=float(head.loss_bbox.loss_weight), box_kind=kind, box_eps=eps)
         wc, wi = float(head.loss_cls.loss_weight), float(head.loss_iou.loss_weight)
         self.loss_weights = None if (wc == 1.0 and wi == 1.0) else torch.tensor([wc, 1.0, wi], device=self.dev)
         return self
@@ -1039,7 +1042,7 @@ def _lists_to_rows(self, tensors, ch):
 
 class _HeadLossFn(torch.autograd.Function):
     """RADetHead.loss on NCHW head outputs (bbox_preds AFTER Scale + ReLU, as the reference passes them):
-    fused targets + focal + GIoU + IoU-BCE kernel; backward = the same kernel with the upstream gradients folded in,
+    fused targets + focal + box loss (the head's `loss_bbox` kind) + IoU-BCE kernel; backward = the same kernel with the upstream gradients folded in,
     gradients returned in the inputs' NCHW layout."""
 
     @staticmethod
@@ -1062,13 +1065,13 @@ class _HeadLossFn(torch.autograd.Function):
         R, C = lv.rows, rt.num_classes
         ldesc, nlvl = K.level_desc(lv, rt.strides)
         dev = rt.dev
-        hp = rt.loss_hparams or dict(alpha=0.25, gamma=2.0, lbw=2.0)
+        hp = {"box_kind": "giou", "box_eps": 1e-6, **(rt.loss_hparams or dict(alpha=0.25, gamma=2.0, lbw=2.0))}
         losses = torch.zeros(3, device=dev)
         dcls, dreg, diou = torch.empty(R, C, device=dev), torch.empty(R, 4, device=dev), torch.empty(R, 1, device=dev)
         ws = torch.zeros(K.head_loss_ws_ints(R), dtype=torch.int32, device=dev)
         K.head_loss(rc, rr, ri, torch.ones(nlvl, device=dev), tg["boxes"], tg["labels"], tg["off"], tg["p2g"], tg["pw"], ldesc,
-                    nlvl, lv.B, C, hp["alpha"], hp["gamma"], hp["lbw"], 1e-6, grad_scale, losses, dcls, C, dreg, 4, diou, 1,
-                    torch.zeros(nlvl, device=dev), ws, flags=1)
+                    nlvl, lv.B, C, hp["alpha"], hp["gamma"], hp["lbw"], hp["box_eps"], grad_scale, losses, dcls, C, dreg, 4, diou, 1,
+                    torch.zeros(nlvl, device=dev), ws, flags=K.head_loss_flags(hp["box_kind"], postact=True))
         return losses, dcls, dreg, diou
 
     @staticmethod
