@@ -751,6 +751,35 @@ int radet_sqnorm_partials(const float* g, size_t n, float* partials, int npartia
 int radet_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                      float eps, float weight_decay, int step, float max_norm, float grad_div,
                      const float* partials, int npartials, float* grad_norm_out, void* stream);
+/* Parameter groups (mmcv's paramwise_cfg) as a RUN TABLE over the trainable arena: run r scales the learning rate of the
+ * elements [begin, end) by lr_mult and their weight decay by decay_mult.  Runs are sorted, disjoint and cover [0, n); a
+ * boundary may fall anywhere (inside a 16-byte access too) and a run may be one element long.  The table is a DEVICE array
+ * (a replayed launch tape sees a stable pointer) of at most RADET_OPT_MAX_RUNS runs: each block stages it into 16 KiB of LDS.
+ * The kernels trust its order and coverage -- radet_amd/runtime.py:build_opt_runs validates them -- and cannot be led out of
+ * bounds by a bad one (it only selects multipliers). */
+#define RADET_OPT_MAX_RUNS 1024
+typedef struct { uint32_t begin, end; float lr_mult, decay_mult; } RadetOptRun;
+/* radet_adamw_step per run: lr_r = lr * lr_mult, decay = 1 - lr_r * (weight_decay * decay_mult), step size lr_r / bc1; the
+ * clip coefficient is the global one (all runs, as clip_grad_norm_ over all parameters).  lr_mult = 0 leaves p untouched and
+ * still updates m and v.  One run (0, n, 1, 1) is bit-identical to radet_adamw_step.  Arguments 0-15 are radet_adamw_step's.
+ * RADET_ERR_ARG: nruns outside [1, RADET_OPT_MAX_RUNS], runs == NULL, n >= 2^32, step < 1, grad_div <= 0. */
+int radet_adamw_step_runs(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int step, float max_norm, float grad_div,
+                          const float* partials, int npartials, float* grad_norm_out, const RadetOptRun* runs, int nruns,
+                          void* stream);
+/* torch.optim.SGD behind the same fused clip: d = g * coef + (weight_decay * decay_mult) * p; with momentum != 0:
+ * buf = d at step 1, else momentum * buf + (1 - dampening) * d, and d = d + momentum * buf (nesterov) or buf; then
+ * p -= (lr * lr_mult) * d.  buf is read and written only with momentum != 0 (may be NULL otherwise).  runs may be NULL with
+ * nruns = 0: every multiplier is 1.
+ * RADET_ERR_ARG: nesterov with dampening != 0 or momentum == 0 (torch raises), runs == NULL with nruns != 0 or the reverse,
+ * nruns > RADET_OPT_MAX_RUNS, n >= 2^32, step < 1, grad_div <= 0, momentum != 0 with buf == NULL. */
+int radet_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float dampening,
+                   float weight_decay, int nesterov, int step, float max_norm, float grad_div, const float* partials,
+                   int npartials, float* grad_norm_out, const RadetOptRun* runs, int nruns, void* stream);
+/* Gradient accumulation beside the gradient arena (which every backward pass overwrites): mode 0 acc = g, mode 1 acc += g,
+ * mode 2 g = acc + g with acc left as it is (the last micro-step: clip and optimizer then run on g unchanged).
+ * RADET_ERR_ARG for any other mode. */
+int radet_grad_accumulate(float* acc, float* g, size_t n, int mode, void* stream);
 
 /* ---- COCO-protocol box evaluation (radet_amd/datasets/cocoeval.py:COCOeval, the yardstick: both entry points equal it bit
  *      for bit; IEEE fp64 + - * / and comparisons only).

@@ -28,11 +28,10 @@ extern "C" int radet_sqnorm_partials(const float* g, size_t n, float* partials, 
     return radet_check_launch();
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
-                                                    float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                    float max_norm, float grad_div, const float* __restrict__ partials,
-                                                    int npartials, float* __restrict__ grad_norm_out) {
+// Every block of an optimiser kernel: sum of sqnorm_kernel's partials -> global norm -> clip coefficient with the mean
+// (1 / grad_div) folded in; block 0 also reports the norm.  Ends in a barrier.
+__device__ __forceinline__ float clip_coef(float max_norm, float grad_div, const float* __restrict__ partials, int npartials,
+                                           float* __restrict__ grad_norm_out) {
     __shared__ float s_coef;
     if (threadIdx.x < 64) {
         double a = 0.0;
@@ -50,7 +49,15 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         }
     }
     __syncthreads();
-    const float coef = s_coef;
+    return s_coef;
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
+                                                    float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                    float max_norm, float grad_div, const float* __restrict__ partials,
+                                                    int npartials, float* __restrict__ grad_norm_out) {
+    const float coef = clip_coef(max_norm, grad_div, partials, npartials, grad_norm_out);
     const float step = lr / bc1;
     const float decay = 1.f - lr * wd;
     const size_t n4 = n / 4;
@@ -95,5 +102,230 @@ extern "C" int radet_adamw_step(float* p, const float* g, float* m, float* v, si
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
                        weight_decay, bc1, sqrtf(bc2), max_norm, grad_div, partials, npartials, grad_norm_out);
+    return radet_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Parameter groups as a run table (RadetOptRun, include/radet_hip.h).  Each block stages the table into LDS once; a
+// 16-byte group finds its run in two steps: a binary search for the first element of its WAVE's 256-element span (the
+// same address in every lane: broadcast LDS reads, no divergence), then a walk over the runs that begin inside the span --
+// none for all but the few spans that hold a boundary.  A group that a boundary cuts resolves each element on its own.
+struct RunTable {
+    uint32_t begin[RADET_OPT_MAX_RUNS], end[RADET_OPT_MAX_RUNS];
+    float lr_mult[RADET_OPT_MAX_RUNS], decay_mult[RADET_OPT_MAX_RUNS];
+};
+
+__device__ __forceinline__ void stage_runs(RunTable& t, const RadetOptRun* __restrict__ runs, int nruns) {
+    for (int r = threadIdx.x; r < nruns; r += 256) {
+        const RadetOptRun u = runs[r];
+        t.begin[r] = u.begin; t.end[r] = u.end; t.lr_mult[r] = u.lr_mult; t.decay_mult[r] = u.decay_mult;
+    }
+    __syncthreads();
+}
+
+// the last run that begins at or before element e (indices stay inside [0, nruns) whatever the table holds)
+__device__ __forceinline__ int find_run(const RunTable& t, int nruns, uint32_t e) {
+    int lo = 0, hi = nruns - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t.begin[mid] <= e) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int next_run(const RunTable& t, int nruns, int r, uint32_t e) {
+    while (e >= t.end[r] && r + 1 < nruns) ++r;
+    return r;
+}
+
+// run of the 16-byte group that starts at element e0 (group index i4 = e0 / 4 of a lane-consecutive grid-stride loop)
+__device__ __forceinline__ int group_run(const RunTable& t, int nruns, uint32_t e0) {
+    const uint32_t span0 = e0 - 4u * (threadIdx.x & 63);
+    return next_run(t, nruns, find_run(t, nruns, span0), e0);
+}
+
+__global__ __launch_bounds__(256) void adamw_runs_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
+                                                         float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                         float max_norm, float grad_div, const float* __restrict__ partials,
+                                                         int npartials, float* __restrict__ grad_norm_out,
+                                                         const RadetOptRun* __restrict__ runs, int nruns) {
+    __shared__ RunTable t;
+    stage_runs(t, runs, nruns);
+    const float coef = clip_coef(max_norm, grad_div, partials, npartials, grad_norm_out);
+    const size_t n4 = n / 4;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+#define ADAMW_RUN(R, P, G, M, V)                                              \
+    {                                                                         \
+        const float lr_r = lr * t.lr_mult[R];                                 \
+        const float step = lr_r / bc1;                                        \
+        const float decay = 1.f - lr_r * (wd * t.decay_mult[R]);              \
+        ADAMW_ONE(P, G, M, V)                                                 \
+    }
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const uint32_t e0 = (uint32_t)(i * 4);
+        int r = group_run(t, nruns, e0);
+        float4 pp = p4[i], mm = m4[i], vv = v4[i];
+        const float4 gq = g4[i];
+        if (e0 + 3 < t.end[r] || r + 1 >= nruns) {          // the whole group lies in run r
+            const float lr_r = lr * t.lr_mult[r];
+            const float step = lr_r / bc1;
+            const float decay = 1.f - lr_r * (wd * t.decay_mult[r]);
+            ADAMW_ONE(pp.x, gq.x, mm.x, vv.x)
+            ADAMW_ONE(pp.y, gq.y, mm.y, vv.y)
+            ADAMW_ONE(pp.z, gq.z, mm.z, vv.z)
+            ADAMW_ONE(pp.w, gq.w, mm.w, vv.w)
+        } else {                                            // a boundary inside the 16 bytes
+            ADAMW_RUN(r, pp.x, gq.x, mm.x, vv.x)
+            r = next_run(t, nruns, r, e0 + 1);
+            ADAMW_RUN(r, pp.y, gq.y, mm.y, vv.y)
+            r = next_run(t, nruns, r, e0 + 2);
+            ADAMW_RUN(r, pp.z, gq.z, mm.z, vv.z)
+            r = next_run(t, nruns, r, e0 + 3);
+            ADAMW_RUN(r, pp.w, gq.w, mm.w, vv.w)
+        }
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+    }
+    if (blockIdx.x == 0)
+        for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) {
+            const int r = next_run(t, nruns, find_run(t, nruns, (uint32_t)i), (uint32_t)i);
+            float pp = p[i], mm = m[i], vv = v[i];
+            ADAMW_RUN(r, pp, g[i], mm, vv)
+            p[i] = pp; m[i] = mm; v[i] = vv;
+        }
+#undef ADAMW_RUN
+}
+
+static int optim_blocks(size_t n) {
+    size_t blocks = (n / 4 + 255) / 256;
+    return blocks > 2048 ? 2048 : blocks < 1 ? 1 : (int)blocks;
+}
+
+extern "C" int radet_adamw_step_runs(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1,
+                                     float beta2, float eps, float weight_decay, int step, float max_norm, float grad_div,
+                                     const float* partials, int npartials, float* grad_norm_out, const RadetOptRun* runs,
+                                     int nruns, void* stream) {
+    if (step < 1 || grad_div <= 0.f || runs == nullptr || nruns < 1 || nruns > RADET_OPT_MAX_RUNS || n >= ((size_t)1 << 32))
+        return RADET_ERR_ARG;
+    const float bc1 = 1.f - powf(beta1, (float)step);
+    const float bc2 = 1.f - powf(beta2, (float)step);
+    hipLaunchKernelGGL(adamw_runs_kernel, dim3(optim_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
+                       beta2, eps, weight_decay, bc1, sqrtf(bc2), max_norm, grad_div, partials, npartials, grad_norm_out, runs,
+                       nruns);
+    return radet_check_launch();
+}
+
+// torch.optim.SGD (torch/optim/sgd.py:_single_tensor_sgd), in its order.  MOM: momentum != 0 (buf exists); nruns == 0: no table.
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                  size_t n, float lr, float momentum, float dampening, float wd, int nesterov,
+                                                  int first, float max_norm, float grad_div,
+                                                  const float* __restrict__ partials, int npartials,
+                                                  float* __restrict__ grad_norm_out, const RadetOptRun* __restrict__ runs,
+                                                  int nruns) {
+    __shared__ RunTable t;
+    if (nruns > 0) stage_runs(t, runs, nruns);
+    const float coef = clip_coef(max_norm, grad_div, partials, npartials, grad_norm_out);
+    const float keep = 1.f - dampening;
+    const size_t n4 = n / 4;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* b4 = reinterpret_cast<float4*>(buf);
+#define SGD_ONE(P, G, B, LR, WD)                                              \
+    {                                                                         \
+        float d = (G) * coef + (WD) * (P);                                    \
+        if (MOM) {                                                            \
+            (B) = first ? d : momentum * (B) + keep * d;                      \
+            d = nesterov ? d + momentum * (B) : (B);                          \
+        }                                                                     \
+        (P) = (P) - (LR) * d;                                                 \
+    }
+#define SGD_RUN(R, P, G, B) SGD_ONE(P, G, B, lr * t.lr_mult[R], wd * t.decay_mult[R])
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const uint32_t e0 = (uint32_t)(i * 4);
+        int r = nruns > 0 ? group_run(t, nruns, e0) : 0;
+        float4 pp = p4[i], bb = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 gq = g4[i];
+        if (MOM) bb = b4[i];
+        if (nruns == 0 || e0 + 3 < t.end[r] || r + 1 >= nruns) {
+            const float lr_r = nruns > 0 ? lr * t.lr_mult[r] : lr;
+            const float wd_r = nruns > 0 ? wd * t.decay_mult[r] : wd;
+            SGD_ONE(pp.x, gq.x, bb.x, lr_r, wd_r)
+            SGD_ONE(pp.y, gq.y, bb.y, lr_r, wd_r)
+            SGD_ONE(pp.z, gq.z, bb.z, lr_r, wd_r)
+            SGD_ONE(pp.w, gq.w, bb.w, lr_r, wd_r)
+        } else {
+            SGD_RUN(r, pp.x, gq.x, bb.x)
+            r = next_run(t, nruns, r, e0 + 1);
+            SGD_RUN(r, pp.y, gq.y, bb.y)
+            r = next_run(t, nruns, r, e0 + 2);
+            SGD_RUN(r, pp.z, gq.z, bb.z)
+            r = next_run(t, nruns, r, e0 + 3);
+            SGD_RUN(r, pp.w, gq.w, bb.w)
+        }
+        p4[i] = pp;
+        if (MOM) b4[i] = bb;
+    }
+    if (blockIdx.x == 0)
+        for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) {
+            float pp = p[i], bb = MOM ? buf[i] : 0.f;
+            if (nruns > 0) {
+                const int r = next_run(t, nruns, find_run(t, nruns, (uint32_t)i), (uint32_t)i);
+                SGD_RUN(r, pp, g[i], bb)
+            } else {
+                SGD_ONE(pp, g[i], bb, lr, wd)
+            }
+            p[i] = pp;
+            if (MOM) buf[i] = bb;
+        }
+#undef SGD_RUN
+#undef SGD_ONE
+}
+
+extern "C" int radet_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float dampening,
+                              float weight_decay, int nesterov, int step, float max_norm, float grad_div, const float* partials,
+                              int npartials, float* grad_norm_out, const RadetOptRun* runs, int nruns, void* stream) {
+    if (step < 1 || grad_div <= 0.f || n >= ((size_t)1 << 32)) return RADET_ERR_ARG;
+    if ((runs == nullptr) != (nruns == 0) || nruns < 0 || nruns > RADET_OPT_MAX_RUNS) return RADET_ERR_ARG;
+    if (nesterov && (dampening != 0.f || momentum == 0.f)) return RADET_ERR_ARG;
+    if (momentum != 0.f && buf == nullptr) return RADET_ERR_ARG;
+    auto kernel = momentum != 0.f ? sgd_kernel<true> : sgd_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(optim_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, lr, momentum, dampening,
+                       weight_decay, nesterov, (int)(step == 1), max_norm, grad_div, partials, npartials, grad_norm_out, runs,
+                       nruns);
+    return radet_check_launch();
+}
+
+// MODE 0: acc = g;  1: acc += g;  2: g = acc + g
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, float* __restrict__ g, size_t n) {
+    const size_t n4 = n / 4;
+    float4* a4 = reinterpret_cast<float4*>(acc);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const float4 y = g4[i];
+        if (MODE == 0) {
+            a4[i] = y;
+        } else {
+            const float4 x = a4[i];
+            const float4 s = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
+            if (MODE == 1) a4[i] = s; else g4[i] = s;
+        }
+    }
+    if (blockIdx.x == 0)
+        for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) {
+            if (MODE == 0) acc[i] = g[i];
+            else if (MODE == 1) acc[i] = acc[i] + g[i];
+            else g[i] = acc[i] + g[i];
+        }
+}
+
+extern "C" int radet_grad_accumulate(float* acc, float* g, size_t n, int mode, void* stream) {
+    if (mode < 0 || mode > 2) return RADET_ERR_ARG;
+    auto kernel = mode == 0 ? grad_accumulate_kernel<0> : mode == 1 ? grad_accumulate_kernel<1> : grad_accumulate_kernel<2>;
+    hipLaunchKernelGGL(kernel, dim3(optim_blocks(n)), dim3(256), 0, (hipStream_t)stream, acc, g, n);
     return radet_check_launch();
 }

@@ -1474,6 +1474,27 @@ def adamw_step(p, g, m, v, n, lr, betas, eps, wd, step, max_norm, grad_div, part
               step, max_norm, grad_div, _ptr(partials), partials.numel(), _ptr(grad_norm_out), _stream())
 
 
+OPT_MAX_RUNS = 1024                # RADET_OPT_MAX_RUNS of include/radet_hip.h: runs of a parameter-group table (16 KiB of LDS)
+
+def adamw_step_runs(p, g, m, v, n, lr, betas, eps, wd, step, max_norm, grad_div, partials, grad_norm_out, runs, nruns):
+    """radet_adamw_step with a device run table (`runs`: uint8 tensor holding nruns RadetOptRun records)"""
+    _lib.call("radet_adamw_step_runs", _ptr(p), _ptr(g), _ptr(m), _ptr(v), C.c_size_t(n), lr, betas[0], betas[1], eps, wd,
+              step, max_norm, grad_div, _ptr(partials), partials.numel(), _ptr(grad_norm_out), _ptr(runs), nruns, _stream())
+
+
+def sgd_step(p, g, buf, n, lr, momentum, dampening, wd, nesterov, step, max_norm, grad_div, partials, grad_norm_out,
+             runs=None, nruns=0):
+    _lib.call("radet_sgd_step", _ptr(p), _ptr(g), _ptr(buf), C.c_size_t(n), lr, momentum, dampening, wd, int(bool(nesterov)),
+              step, max_norm, grad_div, _ptr(partials), partials.numel(), _ptr(grad_norm_out), _ptr(runs), nruns, _stream())
+
+
+GRAD_ACC_SET, GRAD_ACC_ADD, GRAD_ACC_RESTORE = 0, 1, 2       # acc = g / acc += g / g = acc + g
+
+
+def grad_accumulate(acc, g, n, mode):
+    _lib.call("radet_grad_accumulate", _ptr(acc), _ptr(g), C.c_size_t(n), mode, _stream())
+
+
 def decode_ws_bytes(B, nlvl, nms_pre):
     return int(_lib.load().radet_decode_ws_bytes(B, nlvl, nms_pre))
 

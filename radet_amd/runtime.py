@@ -147,6 +147,53 @@ def compute_buckets(flat, conv_names, conv_trainable, split=("backbone.layer4.",
     return buckets
 
 
+OPT_RUN_DTYPE = np.dtype([("begin", "<u4"), ("end", "<u4"), ("lr_mult", "<f4"), ("decay_mult", "<f4")])   # RadetOptRun
+
+
+def check_opt_runs(runs, n):
+    """A run table the optimizer kernels accept (include/radet_hip.h, RadetOptRun): at most kernels.OPT_MAX_RUNS non-empty
+    runs, sorted, disjoint, covering [0, n).  The kernels trust this; nothing else validates it."""
+    if len(runs) > K.OPT_MAX_RUNS:
+        raise NotImplementedError(f"{len(runs)} parameter-group runs: the optimizer kernels hold at most RADET_OPT_MAX_RUNS = "
+                                  f"{K.OPT_MAX_RUNS} in LDS (merge groups, or give neighbouring parameters equal multipliers)")
+    if len(runs) < 1 or n >= 2 ** 32:
+        raise ValueError(f"a run table needs at least one run and an arena below 2^32 elements (got {len(runs)} runs, n = {n})")
+    b, e = runs["begin"].astype(np.int64), runs["end"].astype(np.int64)
+    if b[0] != 0 or e[-1] != n or (e <= b).any() or (b[1:] != e[:-1]).any():
+        raise ValueError("run table is not sorted, disjoint and covering [0, n)")
+    return runs
+
+
+def build_opt_runs(flat, groups):
+    """Per-parameter multipliers -> the run table of the optimizer kernels.  groups: {parameter name: (lr_mult, decay_mult)};
+    a trainable parameter it does not name has (1, 1).  Tensors that follow each other in the arena with equal multipliers
+    merge into one run; the arena's alignment gaps (zeros no kernel writes) join the run in front of them, the leading
+    one and the arena's padded end likewise, so the table covers [0, n_train).  Returns None when every multiplier is 1
+    (no table: the plain kernels), else a numpy record array of OPT_RUN_DTYPE."""
+    groups = dict(groups or {})
+    unknown = [k for k in groups if k not in flat.offsets]
+    if unknown:
+        raise KeyError(f"parameter groups name {unknown[:3]}{'...' if len(unknown) > 3 else ''}: not trainable parameters of this model")
+    out = []                                            # [begin, end, lr_mult, decay_mult]
+    for name in flat.train_names:
+        lm, dm = (float(x) for x in groups.get(name, (1.0, 1.0)))
+        b = flat.offsets[name]
+        e = b + flat.p[name].numel()
+        if out and (out[-1][2], out[-1][3]) == (lm, dm):
+            out[-1][1] = e
+        else:
+            if out:
+                out[-1][1] = b                          # (an alignment gap stays with the run before it)
+            out.append([b if out else 0, e, lm, dm])
+    if not out:
+        return None
+    out[-1][1] = flat.n_train
+    if all((r[2], r[3]) == (1.0, 1.0) for r in out):
+        return None
+    runs = np.array([tuple(r) for r in out], dtype=OPT_RUN_DTYPE)
+    return check_opt_runs(runs, flat.n_train)
+
+
 class _StreamWork:
     """What GradReducer needs of a c10d Work, for a collective issued synchronously on a stream of ours: an event behind it"""
 
@@ -296,7 +343,7 @@ class DetectorRuntime:
             return False
         arenas = [self.flat.params, self.flat.frozen]
         if self.opt_state is not None:
-            arenas += [self.opt_state["m"], self.opt_state["v"]]
+            arenas += [self.opt_state[k] for k in ("m", "v", "buf") if self.opt_state.get(k) is not None]
         for t in arenas:
             dist.broadcast(t, src)
         step = torch.tensor([self.step_count], dtype=torch.int64, device=self.dev)
@@ -432,29 +479,59 @@ class DetectorRuntime:
             bucket_hook(bucket)
 
     # ------------------------------------------------------------------ optimiser
-    def init_optimizer(self, lr=4e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=35.0, sync=True):
-        """AdamW state for the trainable arena.  COLLECTIVE when a process group is initialised (sync=True): every rank
-        must call it; the replicas then start from rank 0's parameters -- the broadcast MMDistributedDataParallel does at
-        construction in the reference (radet/apis/train.py:73-81)."""
+    def init_optimizer(self, lr=4e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=35.0, sync=True,
+                       type="AdamW", momentum=0.0, dampening=0.0, nesterov=False, groups=None):
+        """Optimizer state for the trainable arena: type "AdamW" (m, v) or "SGD" (buf, with momentum != 0).
+        groups: {parameter name: (lr_mult, decay_mult)} -- mmcv's paramwise_cfg, resolved (apis/train.py:resolve_paramwise);
+        it becomes a device run table (build_opt_runs) the fused kernels look each element up in.  None, or every
+        multiplier 1, is no table and, for AdamW, the plain radet_adamw_step.
+        COLLECTIVE when a process group is initialised (sync=True): every rank must call it; the replicas then start from
+        rank 0's parameters -- the broadcast MMDistributedDataParallel does at construction in the reference
+        (radet/apis/train.py:73-81)."""
+        if type not in ("AdamW", "SGD"):
+            raise NotImplementedError(f"optimizer type {type!r}: the fused step implements AdamW and SGD")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         n = self.flat.n_train
-        self.opt_state = dict(m=torch.zeros(n, device=self.dev), v=torch.zeros(n, device=self.dev), lr=lr, betas=betas,
-                              eps=eps, wd=weight_decay, max_norm=max_norm,
-                              partials=torch.zeros(1024, device=self.dev), grad_norm=torch.zeros(1, device=self.dev))
+        table = build_opt_runs(self.flat, groups)
+        st = dict(lr=lr, wd=weight_decay, max_norm=max_norm, partials=torch.zeros(1024, device=self.dev),
+                  grad_norm=torch.zeros(1, device=self.dev), type=type, groups=dict(groups or {}), run_table=table,
+                  runs=None if table is None else torch.from_numpy(table.view(np.uint8).copy()).to(self.dev),
+                  nruns=0 if table is None else len(table))
+        if type == "AdamW":
+            st.update(m=torch.zeros(n, device=self.dev), v=torch.zeros(n, device=self.dev), betas=betas, eps=eps)
+        else:
+            st.update(buf=torch.zeros(n, device=self.dev) if momentum != 0 else None, momentum=float(momentum),
+                      dampening=float(dampening), nesterov=bool(nesterov))
+        self.opt_state = st
         self.step_count = 0
+        self._acc = None
         if sync:
             self.sync_replicas()
 
     def optimizer_step(self, lr=None, grad_div=1.0):
         st = self.opt_state
         self.step_count += 1
-        K.sqnorm_partials(self.flat.grads, self.flat.n_train, st["partials"])
-        K.adamw_step(self.flat.params, self.flat.grads, st["m"], st["v"], self.flat.n_train, st["lr"] if lr is None else lr,
-                     st["betas"], st["eps"], st["wd"], self.step_count, st["max_norm"], grad_div, st["partials"],
-                     st["grad_norm"])
-        if _lib.TAPE is not None:                 # the two arguments of radet_adamw_step that move from step to step
-            _lib.TAPE.mark("lr", 5)
-            _lib.TAPE.mark("step", 10)
+        lr = st["lr"] if lr is None else lr
+        f, n = self.flat, self.flat.n_train
+        K.sqnorm_partials(f.grads, n, st["partials"])
+        marks = (5, 10)                           # the two arguments that move from step to step: lr, step
+        if st.get("type", "AdamW") == "SGD":
+            K.sgd_step(f.params, f.grads, st["buf"], n, lr, st["momentum"], st["dampening"], st["wd"], st["nesterov"],
+                       self.step_count, st["max_norm"], grad_div, st["partials"], st["grad_norm"], st["runs"], st["nruns"])
+            marks = (4, 9)
+        elif st.get("runs") is not None:
+            K.adamw_step_runs(f.params, f.grads, st["m"], st["v"], n, lr, st["betas"], st["eps"], st["wd"], self.step_count,
+                              st["max_norm"], grad_div, st["partials"], st["grad_norm"], st["runs"], st["nruns"])
+        else:
+            K.adamw_step(f.params, f.grads, st["m"], st["v"], n, lr, st["betas"], st["eps"], st["wd"], self.step_count,
+                         st["max_norm"], grad_div, st["partials"], st["grad_norm"])
+        if _lib.TAPE is not None:
+            _lib.TAPE.mark("lr", marks[0])
+            _lib.TAPE.mark("step", marks[1])
         self.engine.params_changed()              # the kernel wrote the arena behind torch's back: fold again next step
+
+    _acc = None             # the accumulation arena (train_step(accumulate=...)): same layout as the gradient arena
 
     def bf16_buckets(self):
         """Gradient buckets travel as bf16 (fp32 arena -> bf16 staging -> all-reduce -> back) by default in the bf16-STORAGE
@@ -515,23 +592,56 @@ class DetectorRuntime:
     tape_mode = os.environ.get("RADET_TAPE", "1")
     tape_after = int(os.environ.get("RADET_TAPE_AFTER", "2"))
 
-    def _tape_key(self, img, tg, world, use_reducer):
+    def _tape_key(self, img, tg, world, use_reducer, phase="plain", k=1):
         e, st = self.engine, self.opt_state
+        opt = (st.get("type", "AdamW"), st.get("betas"), st.get("eps"), st.get("momentum"), st.get("dampening"), st.get("nesterov"),
+               None if st.get("runs") is None else st["runs"].data_ptr(), st.get("nruns", 0))
+        state = st["m"] if st.get("m") is not None else st.get("buf")
         return (e.geo_key, getattr(e, "plan_id", None), tuple(img.shape), img.dtype, tuple(tg["p2g"].shape), int(tg["off"].numel()),
                 world, use_reducer, self.loss_weights is None or self.loss_weights.data_ptr(),
-                st["betas"], st["eps"], st["wd"], st["max_norm"], st["m"].data_ptr(), e.wgrad_streams, e.use_streams,
-                tuple(sorted(self.loss_hparams.items())) if self.loss_hparams else None)
+                opt, st["wd"], st["max_norm"], None if state is None else state.data_ptr(), e.wgrad_streams, e.use_streams,
+                tuple(sorted(self.loss_hparams.items())) if self.loss_hparams else None,
+                phase, k, None if self._acc is None else self._acc.data_ptr())
+
+    # One tape slot per PHASE of an accumulated step -- "plain" (no accumulation; `_tape`), "first", "middle", "last": the
+    # phases alternate, and a single slot would be reset by every call and never replay.
+    _tape = None            # dict(key, count, tape, failed) of the plain step
+    _acc_tapes = None       # phase -> the same, for the micro-steps of an accumulated step
+
+    def _slot(self, phase):
+        return self._tape if phase == "plain" else (self._acc_tapes or {}).get(phase)
+
+    def _new_slot(self, phase, key):
+        st = dict(key=key, count=0, tape=None, failed=None)
+        if phase == "plain":
+            self._tape = st
+        else:
+            if self._acc_tapes is None:
+                self._acc_tapes = {}
+            self._acc_tapes[phase] = st
+        return st
 
     def drop_tape(self):
         self._tape = None
+        self._acc_tapes = None
 
-    _tape = None            # dict(key, count, tape, failed)
-
-    def tape_stats(self):
-        t = (self._tape or {}).get("tape")
+    def tape_stats(self, phase="plain"):
+        t = (self._slot(phase) or {}).get("tape")
         return None if t is None else dict(t.stats(), replays=t.replays)
 
-    def train_step(self, img, tg, lr=None, next_img=None):
+    @staticmethod
+    def _phase(accumulate):
+        """accumulate = (j, k): micro-step j of k -> (phase, k); None or k = 1 is the plain step"""
+        if accumulate is None:
+            return "plain", 1
+        j, k = (int(x) for x in accumulate)
+        if k < 1 or not 0 <= j < k:
+            raise ValueError(f"accumulate=(j, k) needs 0 <= j < k, got {accumulate}")
+        if k == 1:
+            return "plain", 1
+        return ("first" if j == 0 else "last" if j == k - 1 else "middle"), k
+
+    def train_step(self, img, tg, lr=None, next_img=None, accumulate=None):
         """One optimisation step. With torch.distributed initialised (backend nccl = RCCL) gradients
         are summed across ranks per bucket on a side stream while the backward of earlier layers is
         still running; the mean (1/world) is folded into the fused clip+AdamW kernel.
@@ -539,7 +649,16 @@ class DetectorRuntime:
         of its forward pass (stem + frozen stages, `frozen_stages` of resnet.py:572-588) is then computed during this step's
         backward pass and picked up by the next call when it is given the same tensor; results are bit-identical to calls
         without it.
+        accumulate=(j, k): micro-step j of a step accumulated over k batches (mmcv's GradientCumulativeOptimizerHook).  The
+        gradient arena is overwritten by every backward pass, so the sum lives in a second arena: micro-step 0 copies the
+        (exchanged) gradients there, the following ones add theirs, and the last one writes sum + its own back into the
+        gradient arena and runs the optimizer with grad_div = world * k -- the mean over ranks and micro-batches, folded
+        into the fused kernel.  Only the last micro-step moves the parameters and `step_count`; `lr` is used by it alone.
+        None, or k = 1, is the plain step.
         Steady-state calls are replayed from a launch tape (see above); results are bit-identical to the eager step."""
+        phase, k = self._phase(accumulate)
+        if phase != "plain" and self._acc is None:
+            self._acc = torch.zeros_like(self.flat.grads)
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # a 1-rank process group still exercises the bucketed exchange when forced (single-GPU test of the RCCL path)
         use_reducer = world > 1 or (world == 1 and dist.is_available() and dist.is_initialized()
@@ -552,14 +671,18 @@ class DetectorRuntime:
                     and self.opt_state is not None and "partials" in self.opt_state
                     and all(tg[k].is_contiguous() for k in ("boxes", "labels", "off", "p2g", "pw")))
         if tapeable:
-            key = self._tape_key(img, tg, world, use_reducer)
-            st = self._tape
+            if phase != "plain":
+                # the key names the engine's plan: have it built before the key is taken, so that the phase that opens a
+                # run ("first") counts from its first call like the phases behind it (forward() finds the plan prepared)
+                e.prepare(img.shape[0], img.shape[2], img.shape[3])
+            key = self._tape_key(img, tg, world, use_reducer, phase, k)
+            st = self._slot(phase)
             if st is None or st["key"] != key:
-                st = self._tape = dict(key=key, count=0, tape=None, failed=None)
+                st = self._new_slot(phase, key)
             if st["tape"] is not None:
-                if self._tape_still_valid():
-                    return self._replay_step(st["tape"], img, tg, lr, world)
-                st = self._tape = dict(key=key, count=0, tape=None, failed=None)      # something moved: start over
+                if self._tape_still_valid(phase):
+                    return self._replay_step(st["tape"], img, tg, lr, world, phase)
+                st = self._new_slot(phase, key)                                       # something moved: start over
             st["count"] += 1
             if st["count"] > self.tape_after and st["failed"] is None and (not use_reducer or self.reducer is not None):
                 from .tape import Tape
@@ -602,16 +725,24 @@ class DetectorRuntime:
                     self.reducer.finish()
             else:
                 self.backward(next_img=next_img)
-            self.optimizer_step(lr=lr, grad_div=float(world))
+            if phase in ("first", "middle"):
+                K.grad_accumulate(self._acc, self.flat.grads, self.flat.n_train,
+                                  K.GRAD_ACC_SET if phase == "first" else K.GRAD_ACC_ADD)
+            else:
+                if phase == "last":
+                    K.grad_accumulate(self._acc, self.flat.grads, self.flat.n_train, K.GRAD_ACC_RESTORE)
+                self.optimizer_step(lr=lr, grad_div=float(world * k))
         except BaseException:
             if record is not None:
                 record.abort()
             raise
         if record is not None:
             record.end()
-            st = self._tape
-            if record.poisoned is None and (e._last_fold != (False, True) or e._pfx_ready is not None):
-                record.poisoned = "the recorded step was not a steady-state step (frozen weights were folded in it)"
+            st = self._slot(phase)
+            # steady state: the frozen weights are not folded; the trainable ones are folded by the steps that follow an
+            # optimizer step (plain, first) and by no other (middle, last: the parameters have not moved since)
+            if record.poisoned is None and (e._last_fold != (False, phase in ("plain", "first")) or e._pfx_ready is not None):
+                record.poisoned = "the recorded step was not a steady-state step (its weight folds are not the phase's)"
             if record.poisoned is None:
                 record.bind("img", img)
                 for k in ("boxes", "labels", "off", "p2g", "pw"):
@@ -626,20 +757,32 @@ class DetectorRuntime:
             return self.engine.losses * self.loss_weights
         return self.engine.losses
 
-    def _tape_still_valid(self):
+    def _trainable_version(self, nf):
+        e = self.engine
+        return e._part_version(nf, len(e.convs)) + (e._param_epoch,)
+
+    def _tape_still_valid(self, phase="plain"):
         """what a recorded step baked in beyond its key: the frozen convs' folded weights (folded outside the tape whenever
-        their sources move) and the arenas the module's parameters view"""
-        e, st = self.engine, self._tape
+        their sources move), the arenas the module's parameters view and -- for the micro-steps that hold no fold of the
+        trainable weights (middle, last) -- that those folded weights are still the parameters' """
+        e, st = self.engine, self._slot(phase)
         nf = st["nf"]
         if nf > 0 and e._part_version(0, nf) != e._folded[0]:
             return False
+        if phase in ("middle", "last") and self._trainable_version(nf) != e._folded[1]:
+            return False
         return self.flat.still_bound() and _lib.TAPE is None
 
-    def _replay_step(self, tape, img, tg, lr, world):
+    def _replay_step(self, tape, img, tg, lr, world, phase="plain"):
         e, st = self.engine, self.opt_state
+        tensors = dict(img=img, boxes=tg["boxes"], labels=tg["labels"], off=tg["off"], p2g=tg["p2g"], pw=tg["pw"])
+        if phase in ("first", "middle"):          # no optimizer call on these tapes: nothing to patch, no parameter moves
+            tape.replay(tensors=tensors)
+            if phase == "first":                  # (the tape folded the trainable weights: they are current now)
+                e._folded = (e._folded[0], self._trainable_version(self._slot(phase)["nf"]))
+            return e.losses * self.loss_weights if self.loss_weights is not None else e.losses
         self.step_count += 1
-        tape.replay(tensors=dict(img=img, boxes=tg["boxes"], labels=tg["labels"], off=tg["off"], p2g=tg["p2g"], pw=tg["pw"]),
-                    values=dict(lr=st["lr"] if lr is None else lr, step=self.step_count))
+        tape.replay(tensors=tensors, values=dict(lr=st["lr"] if lr is None else lr, step=self.step_count))
         e.params_changed()
         if self.loss_weights is not None:
             return e.losses * self.loss_weights
