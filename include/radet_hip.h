@@ -434,6 +434,33 @@ int radet_nms(const float* boxes, const float* cluster_scores, const float* vote
               float* out_boxes, float* out_scores, int64_t* out_labels, int* out_count, int64_t* aux0, int64_t* aux1,
               void* ws, void* stream);
 
+/* ---- Soft-NMS (mmcv.ops.batched_nms with nms.type = 'soft_nms', reached from radet_head.py:159-163; mmcv 1.3.18's
+ *      softnms_cpu restated -- mmcv is not available to the tests, so parity with it is UNPINNED; the tests pin a NumPy
+ *      restatement bit for bit).  Batched over images like radet_nms: inputs [B, cap] with counts[b] valid entries,
+ *      cap <= 65536.  Per image: boxes + float(label) * (largest valid coordinate + 1) in fp32 (class_agnostic: no
+ *      offset); then repeatedly pick the highest current score among the boxes neither picked nor pruned (ties: lowest
+ *      input index -- this project's rule, mmcv's depends on its swap history) and multiply every remaining score by
+ *        naive:    ovr >= iou_thr ? 0 : 1          linear: ovr >= iou_thr ? 1 - ovr : 1
+ *        gaussian: exp(-(ovr * ovr) / sigma), argument in fp32, exp in DOUBLE rounded once to fp32 (not glibc expf)
+ *      with ovr = inter / (area_i + area_p - inter), all fp32 and unfused; a NaN ovr (two zero-area boxes) gives weight 1
+ *      under every method (mmcv's gaussian branch would write NaN scores).  After each multiply a box with score <
+ *      min_score is removed for good; the picked box is never checked, so an image's first pick survives whatever its
+ *      score.  Candidates with a NaN score are never picked.
+ *      Outputs in pick order (scores non-increasing), the first max_out (> 0) of the sequence: out_boxes [B,max_out,4] the
+ *      original boxes, out_scores the decayed scores, out_labels, out_keep i64 [B,max_out] input indices, out_count [B].
+ *      One workgroup per image runs the global loop: up to 8192 candidates (1024 lanes x 8) from registers and LDS,
+ *      above through ws (radet_soft_nms_ws_bytes: 24 B per candidate, no dense mask); same results.  No host
+ *      synchronisation, no allocation.  RADET_ERR_ARG before any launch: method not 0..2, sigma <= 0 with gaussian,
+ *      max_out <= 0, cap outside 1..65536. */
+#define RADET_SOFT_NMS_NAIVE 0
+#define RADET_SOFT_NMS_LINEAR 1
+#define RADET_SOFT_NMS_GAUSSIAN 2
+size_t radet_soft_nms_ws_bytes(int B, int cap);
+int radet_soft_nms(const float* boxes, const float* scores, const int64_t* labels, const int* counts, int B, int cap,
+                   int method, float iou_thr, float sigma, float min_score, int class_agnostic, int max_out,
+                   float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_keep, int* out_count,
+                   void* ws, void* stream);
+
 /* ---- visibility-guided positive-sample assigner (radet/datasets/pipelines/label_assignment.py:57-201).
  *      One image per workgroup.  masks u8 [sumG, H, W]; rng_words u32 [B, U] = the next U raw 32-bit outputs of the image's
  *      RandomState (MT19937; a random_sample() is two words); out p2g i64 [B,N], pw f32 [B,N], used i32 [B] (words

@@ -1,6 +1,7 @@
 """`multiclass_nms` (radet/core/post_processing/bbox_nms.py:8-79) on the GPU: score filter = ordered stream
-compaction (radet_threshold_compact), suppression = the hard-NMS mode of the HIP NMS pipeline
-(radet_amd.ops.batched_nms).  Same arguments, return values and ordering as the reference."""
+compaction (radet_threshold_compact), suppression = radet_amd.ops.batched_nms: the hard-NMS mode of the HIP NMS
+pipeline, or Soft-NMS (radet_soft_nms) for nms_cfg['type'] == 'soft_nms', whose dets carry the decayed scores.  Same
+arguments, return values and ordering as the reference."""
 import torch
 
 from .. import kernels as K

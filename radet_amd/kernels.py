@@ -1520,6 +1520,20 @@ def nms(boxes, cluster_scores, vote_scores, labels, counts, B, cap, mode, iou_th
               _ptr(out_count), _ptr(aux0), _ptr(aux1), _ptr(ws), _stream())
 
 
+def soft_nms_ws_bytes(B, cap):
+    return int(_lib.load().radet_soft_nms_ws_bytes(B, cap))
+
+
+SOFT_NMS_METHODS = dict(naive=0, linear=1, gaussian=2)
+
+
+def soft_nms(boxes, scores, labels, counts, B, cap, method, iou_thr, sigma, min_score, class_agnostic, max_out, out_boxes,
+             out_scores, out_labels, out_keep, out_count, ws):
+    _lib.call("radet_soft_nms", _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(counts), B, cap, method, iou_thr, sigma,
+              min_score, int(class_agnostic), max_out, _ptr(out_boxes), _ptr(out_scores), _ptr(out_labels), _ptr(out_keep),
+              _ptr(out_count), _ptr(ws), _stream())
+
+
 def mbd_ws_bytes(px):
     return int(_lib.load().radet_mbd_ws_bytes(px))
 

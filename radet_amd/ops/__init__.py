@@ -1,5 +1,5 @@
 """radet.ops-compatible entry points (radet/ops/__init__.py:1-11 of the reference), executed by the
-HIP NMS kernel (radet_amd/csrc/decode_nms.hip).  Inputs may be CPU / GPU tensors or ndarrays; results come
+HIP NMS kernels (radet_amd/csrc/decode_nms.hip, soft_nms.hip).  Inputs may be CPU / GPU tensors or ndarrays; results come
 back on the input's device, same shapes / dtypes / ordering as the reference's C++ ops."""
 import functools
 
@@ -8,7 +8,7 @@ import torch
 
 from .. import kernels as K
 
-__all__ = ["vote_nms", "global_vote_nms", "cluster_nms", "batched_nms", "MBD_box2distance", "GDT_box2distance", "MBD", "GDT",
+__all__ = ["vote_nms", "global_vote_nms", "cluster_nms", "batched_nms", "soft_nms", "MBD_box2distance", "GDT_box2distance", "MBD", "GDT",
            "mbd_batch", "gdt_batch", "border_seeds", "resize_batch", "gaussian_blur9_batch", "sobel_edge_batch"]
 
 _MAX = 65536      # 16-bit positions in the kernel's sort keys (above 8192 the sorts run in global memory)
@@ -98,10 +98,73 @@ def cluster_nms(bboxes, scores, categories, iou_threshold=0.65):
     return ids[:n].to(src), num[:n].to(src)
 
 
+def _soft_args(iou_threshold, sigma, min_score, method, offset):
+    """the refusals of the Soft-NMS entry points (nothing is approximated): -> the kernel's method code"""
+    if offset != 0:
+        raise NotImplementedError(f"soft_nms(offset={offset}): only offset=0 (mmcv's default for float boxes) is implemented")
+    if method not in K.SOFT_NMS_METHODS:
+        raise ValueError(f"soft_nms method {method!r}: expected one of {sorted(K.SOFT_NMS_METHODS)}")
+    if method == "gaussian" and not float(sigma) > 0:
+        raise ValueError(f"soft_nms(method='gaussian') needs sigma > 0, got {sigma}")
+    return K.SOFT_NMS_METHODS[method]
+
+
+def _run_soft(b, s, lab, method, thr, sigma, min_score, class_agnostic):
+    """-> (boxes [k,4], decayed scores [k], keep [k]) of the device tensors b [n,4], s [n], lab i64 [n]"""
+    n = int(b.shape[0])
+    if n > _MAX:
+        raise ValueError(f"Soft-NMS input of {n} boxes exceeds the kernel's capacity ({_MAX})")
+    dev = _dev()
+    cap = max(n, 1)
+    ob = torch.zeros(1, cap, 4, device=dev)
+    osc = torch.zeros(1, cap, device=dev)
+    ol = torch.zeros(1, cap, dtype=torch.long, device=dev)
+    okp = torch.zeros(1, cap, dtype=torch.long, device=dev)
+    if n == 0:
+        return ob[0, :0], osc[0, :0], okp[0, :0]
+    cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+    oc = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(K.soft_nms_ws_bytes(1, cap), dtype=torch.uint8, device=dev)
+    K.soft_nms(b, s, lab, cnt, 1, cap, method, float(thr), float(sigma), float(min_score), bool(class_agnostic), cap, ob,
+               osc, ol, okp, oc, ws)
+    kk = int(oc.item())
+    return ob[0, :kk], osc[0, :kk], okp[0, :kk]
+
+
+def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method="linear", offset=0):
+    """mmcv.ops.soft_nms (one class, no class offset) -> (dets [k,5] = boxes and decayed scores in pick order, inds [k]).
+    Restates mmcv 1.3.18's softnms_cpu (parity unpinned: include/radet_hip.h, "Soft-NMS"); refuses offset != 0, an
+    unknown method and sigma <= 0 with 'gaussian'."""
+    m = _soft_args(iou_threshold, sigma, min_score, method, offset)
+    src = boxes.device if isinstance(boxes, torch.Tensor) else torch.device("cpu")
+    b = _t(boxes, torch.float32).reshape(-1, 4)
+    s = _t(scores, torch.float32).reshape(-1)
+    ob, osc, keep = _run_soft(b, s, torch.zeros(b.shape[0], dtype=torch.long, device=b.device), m, iou_threshold, sigma,
+                              min_score, True)
+    return torch.cat([ob, osc[:, None]], -1).to(src), keep.to(src)
+
+
 def batched_nms(boxes, scores, idxs, nms_cfg, class_agnostic=False):
-    """mmcv.ops.batched_nms semantics as used by radet_head.py:160: returns (cat[boxes, score], keep)."""
+    """mmcv.ops.batched_nms semantics as used by radet_head.py:160: returns (cat[boxes, score], keep).  nms_cfg['type'] ==
+    'soft_nms' runs Soft-NMS (scores = the decayed ones); a missing type, 'nms' and every other type run hard NMS."""
     src = boxes.device if isinstance(boxes, torch.Tensor) else torch.device("cpu")
     cfg = dict(nms_cfg)
+    class_agnostic = cfg.pop("class_agnostic", class_agnostic)
+    if cfg.get("type") == "soft_nms":
+        m = _soft_args(cfg.get("iou_threshold", 0.3), cfg.get("sigma", 0.5), cfg.get("min_score", 1e-3),
+                       cfg.get("method", "linear"), cfg.get("offset", 0))
+        split_thr = cfg.get("split_thr", 10000)
+        n = int(np.prod(tuple(scores.shape)))
+        if 0 <= split_thr <= n:
+            raise NotImplementedError(
+                f"batched_nms(type='soft_nms') with {n} >= split_thr={split_thr} boxes: mmcv's per-class split path returns "
+                "the undecayed scores there; pass split_thr=-1 in nms_cfg for Soft-NMS over all boxes")
+        b = _t(boxes, torch.float32).reshape(-1, 4)
+        s = _t(scores, torch.float32).reshape(-1)
+        lab = _t(idxs, torch.long).reshape(-1)
+        ob, osc, keep = _run_soft(b, s, lab, m, cfg.get("iou_threshold", 0.3), cfg.get("sigma", 0.5),
+                                  cfg.get("min_score", 1e-3), class_agnostic)
+        return torch.cat([ob, osc[:, None]], -1).to(src), keep.to(src)
     thr = cfg.get("iou_threshold", cfg.get("iou_thr", 0.5))
     b = _t(boxes, torch.float32).reshape(-1, 4)
     s = _t(scores, torch.float32).reshape(-1)

@@ -995,12 +995,15 @@ def _post_launch(self, hw, sf, test_cfg, head_out=None):
     cap = nlvl * nms_pre
     if cap > 65536:
         raise NotImplementedError(f"nms_pre={nms_pre}: more than 65536 candidates per image exceed the NMS kernel's 16-bit positions")
-    key = ("post", B, nlvl, nms_pre)
+    ncfg = dict(test_cfg["nms"])
+    typ = ncfg.get("type")
+    soft = typ == "soft_nms"          # Soft-NMS has a workspace of its own (24 B per candidate): no dense mask, no aux rows
+    key = ("post", B, nlvl, nms_pre) + (("soft",) if soft else ())
     posts = self.__dict__.setdefault("_posts", {})
     if key not in posts:
         # the NMS workspace holds a dense cap x cap / 64 x 8 B suppression mask per image (+ sort keys): 7 MiB per image at
         # the BOP configs' nms_pre = 1000, ~310 MB at nms_pre = 10000, 512 MiB at the 65536-candidate limit
-        need = K.nms_ws_bytes(B, cap) + K.decode_ws_bytes(B, nlvl, nms_pre)
+        need = (K.soft_nms_ws_bytes if soft else K.nms_ws_bytes)(B, cap) + K.decode_ws_bytes(B, nlvl, nms_pre)
         limit = int(float(os.environ.get("RADET_POST_WS_LIMIT_GB", "16")) * 2 ** 30)
         if need > limit:
             raise MemoryError(f"decode + NMS workspaces for batch {B} with nms_pre={nms_pre} ({cap} candidates per image) need "
@@ -1014,14 +1017,14 @@ def _post_launch(self, hw, sf, test_cfg, head_out=None):
             ctr=torch.empty(B, cap, device=dev), labels=torch.empty(B, cap, dtype=torch.long, device=dev),
             count=torch.zeros(B, dtype=torch.int32, device=dev), cscore=torch.empty(B, cap, device=dev),
             dws=torch.empty(K.decode_ws_bytes(B, nlvl, nms_pre), dtype=torch.uint8, device=dev),
-            nws=torch.empty(K.nms_ws_bytes(B, cap), dtype=torch.uint8, device=dev),
-            aux0=torch.zeros(B, cap, dtype=torch.long, device=dev), aux1=torch.zeros(B, cap, dtype=torch.long, device=dev))
+            nws=torch.empty((K.soft_nms_ws_bytes if soft else K.nms_ws_bytes)(B, cap), dtype=torch.uint8, device=dev))
+        if not soft:
+            posts[key].update(aux0=torch.zeros(B, cap, dtype=torch.long, device=dev),
+                              aux1=torch.zeros(B, cap, dtype=torch.long, device=dev))
     p = posts[key]
     K.decode_candidates(ho["cls"], ho["reg"], ho["iou"], ho["scales"], ho["ldesc"], nlvl, B, self.num_classes,
                         float(test_cfg["score_thr"]), nms_pre, hw, sf, p["boxes"], p["scores"], p["ctr"], p["labels"],
                         p["count"], p["dws"])
-    ncfg = dict(test_cfg["nms"])
-    typ = ncfg.get("type")
     max_per_img = int(test_cfg.get("max_per_img", 100))
     k = max_per_img if max_per_img > 0 else cap
     ob = torch.zeros(B, k, 4, device=self.dev)
@@ -1043,6 +1046,15 @@ def _post_launch(self, hw, sf, test_cfg, head_out=None):
         K.nms(p["boxes"], pick(ctype), pick(vtype), p["labels"], p["count"], B, cap, K.NMS_MODES[typ],
               float(ncfg.get("iou_threshold", 0.6)), bool(ncfg.get("iou_enable", False)), float(ncfg.get("sigma", 0.025)),
               max_per_img, ob, osc, ol, oc, p["aux0"], p["aux1"], p["nws"])
+    elif soft:
+        from .ops import _soft_args
+        method = _soft_args(ncfg.get("iou_threshold", 0.3), ncfg.get("sigma", 0.5), ncfg.get("min_score", 1e-3),
+                            ncfg.get("method", "linear"), ncfg.get("offset", 0))
+        torch.mul(p["scores"], p["ctr"], out=p["cscore"])
+        keep = torch.zeros(B, k, dtype=torch.long, device=self.dev)
+        K.soft_nms(p["boxes"], p["cscore"], p["labels"], p["count"], B, cap, method, float(ncfg.get("iou_threshold", 0.3)),
+                   float(ncfg.get("sigma", 0.5)), float(ncfg.get("min_score", 1e-3)), bool(ncfg.get("class_agnostic", False)),
+                   k, ob, osc, ol, keep, oc, p["nws"])
     else:
         torch.mul(p["scores"], p["ctr"], out=p["cscore"])
         K.nms(p["boxes"], p["cscore"], p["cscore"], p["labels"], p["count"], B, cap, 3,
