@@ -807,6 +807,17 @@ int radet_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, flo
  * mode 2 g = acc + g with acc left as it is (the last micro-step: clip and optimizer then run on g unchanged).
  * RADET_ERR_ARG for any other mode. */
 int radet_grad_accumulate(float* acc, float* g, size_t n, int mode, void* stream);
+/* Weight EMA (mmcv's EMAHook, `ema.mul_(1 - m).add_(param, alpha=m)`): per element t = fl32(ema * one_minus), then
+ * ema = fma(momentum, p, t) with its single rounding -- torch's CPU arithmetic bit for bit.  momentum and one_minus are m and
+ * 1 - m, each formed in double by the caller and rounded once to fp32.  p is only read.  Moves 12 bytes per element, like
+ * radet_grad_accumulate's mode 1.
+ * radet_ema_swap exchanges a and b exactly (evaluation and checkpoints see the EMA weights, then they are swapped back).
+ * Both take any n (64-bit index math) and any float-aligned base: 16-byte accesses over the aligned body when the two
+ * pointers share their offset inside a 16-byte line (up to 3 head elements are peeled), element accesses otherwise.
+ * n == 0 launches nothing and returns 0.  RADET_ERR_ARG with n > 0: a NULL or not 4-byte-aligned pointer, arrays that
+ * overlap. */
+int radet_ema_update(float* ema, const float* p, size_t n, float momentum, float one_minus, void* stream);
+int radet_ema_swap(float* a, float* b, size_t n, void* stream);
 
 /* ---- COCO-protocol box evaluation (radet_amd/datasets/cocoeval.py:COCOeval, the yardstick: both entry points equal it bit
  *      for bit; IEEE fp64 + - * / and comparisons only).

@@ -160,6 +160,8 @@ SIGNATURES = {
     "radet_adamw_step_runs": (_i, [_p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _i, _f, _f, _p, _i, _p, _p, _i, _p]),
     "radet_sgd_step": (_i, [_p, _p, _p, _sz, _f, _f, _f, _f, _i, _i, _f, _f, _p, _i, _p, _p, _i, _p]),
     "radet_grad_accumulate": (_i, [_p, _p, _sz, _i, _p]),
+    "radet_ema_update": (_i, [_p, _p, _sz, _f, _f, _p]),
+    "radet_ema_swap": (_i, [_p, _p, _sz, _p]),
     "radet_coco_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p]),
     "radet_coco_accumulate": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "radet_tape_fn_index": (_i, [C.c_char_p]),

@@ -7,6 +7,7 @@ iteration-based fixed / step / CosineAnnealing / poly policies with warm-up, gra
 (GradientCumulativeOptimizerHook), text log every `interval` iterations (one 3-float device->host read instead of the
 reference's four blocking all-reduces per iteration) and checkpoints whose `state_dict` uses the reference's parameter
 names."""
+import contextlib
 import math
 import time
 
@@ -299,12 +300,86 @@ def load_optimizer_state_dict(model, runtime, osd):
         raise KeyError("unrecognised optimizer state: expected torch's {state, param_groups} or {step, exp_avg, exp_avg_sq}")
 
 
+_EMA_HOOK_KEYS = ("type", "momentum", "interval", "warm_up", "resume_from", "priority")
+
+
+def parse_custom_hooks(cfg):
+    """cfg.custom_hooks -> the keyword arguments of DetectorRuntime.init_ema, or None without a hook.  The reference builds
+    every entry from mmcv's HOOKS (radet/apis/train.py:151-163); the one implemented here is
+    dict(type='EMAHook', momentum=0.0002, interval=1, warm_up=100) with mmcv 1.3.18's defaults (`priority` is accepted and
+    ignored: the update's place behind the optimizer is fixed).  Its own `resume_from` and every other hook type raise
+    NotImplementedError instead of being dropped."""
+    hooks = cfg.get("custom_hooks", None) or []
+    if not isinstance(hooks, (list, tuple)):
+        raise TypeError(f"custom_hooks should be a list, but got {type(hooks)}")
+    ema = None
+    for h in hooks:
+        if not isinstance(h, dict) or "type" not in h:
+            raise TypeError(f"each item of custom_hooks is a dict with a 'type', but got {h!r}")
+        if h["type"] != "EMAHook":
+            raise NotImplementedError(f"custom_hooks type {h['type']!r}: the only hook this harness implements is EMAHook "
+                                      "(an entry is never dropped silently)")
+        for k in h:
+            if k not in _EMA_HOOK_KEYS:
+                raise KeyError(f"EMAHook key {k!r} is not one of {_EMA_HOOK_KEYS}")
+        if h.get("resume_from") is not None:
+            raise NotImplementedError("EMAHook resume_from is not implemented: resume with train_detector(resume_from=), "
+                                      "whose checkpoints carry the EMA")
+        if ema is not None:
+            raise ValueError("custom_hooks holds more than one EMAHook")
+        momentum, interval = h.get("momentum", 0.0002), h.get("interval", 1)
+        if not (isinstance(momentum, float) and 0.0 < momentum < 1.0):
+            raise ValueError(f"EMAHook momentum must lie in (0, 1), got {momentum!r}")
+        if not (isinstance(interval, int) and not isinstance(interval, bool) and interval > 0):
+            raise ValueError(f"EMAHook interval must be a positive int, got {interval!r}")
+        ema = dict(momentum=momentum, interval=interval, warm_up=h.get("warm_up", 100))
+    return ema
+
+
+def ema_state_dict(model, runtime):
+    """The EMA arena under mmcv EMAHook's buffer names (`ema_` + the parameter's name with '.' replaced by '_').  Only the
+    trainable arena is averaged: a frozen parameter's entry is a copy of the parameter."""
+    from ..runtime import ema_key
+    flat, ema = runtime.flat, runtime.ema_state["ema"]
+    out = {}
+    for n, p in model.named_parameters():
+        if n in flat.offsets:
+            o = flat.offsets[n]
+            out[ema_key(n)] = ema[o:o + p.numel()].view(p.shape).cpu().clone()
+        else:
+            out[ema_key(n)] = p.detach().cpu().clone()
+    return out
+
+
+def load_ema_state_dict(model, runtime, sd):
+    """Fill the EMA arena from the `ema_*` entries of a checkpoint's state_dict.  A file that holds none of them restarts
+    the EMA from the parameters as they are now (just loaded); one that holds only some of them is refused."""
+    from ..runtime import ema_key
+    flat, ema = runtime.flat, runtime.ema_state["ema"]
+    have = [n for n in flat.train_names if ema_key(n) in sd]
+    if not have:
+        ema.copy_(flat.params)
+        return False
+    if len(have) != len(flat.train_names):
+        lost = [n for n in flat.train_names if ema_key(n) not in sd]
+        raise KeyError(f"checkpoint holds EMA entries but not those of {lost[:3]}{'...' if len(lost) > 3 else ''}")
+    for n in flat.train_names:
+        o, k = flat.offsets[n], flat.p[n].numel()
+        ema[o:o + k].copy_(sd[ema_key(n)].reshape(-1))
+    return True
+
+
 def save_checkpoint(model, path, meta=None, runtime=None):
     """mmcv-style checkpoint: dict(meta=..., state_dict=..., optimizer=...) with reference parameter names; the
-    optimizer entry is `torch.optim.AdamW.state_dict()`-compatible."""
+    optimizer entry is `torch.optim.AdamW.state_dict()`-compatible.  A runtime with an EMA (init_ema) adds the EMA arena to
+    the state_dict under mmcv's `ema_*` names and meta['ema_swapped']: True when written inside `runtime.ema_weights()`, as
+    train_detector does -- the parameters of the file are then the EMA weights and its `ema_*` entries the raw ones."""
     ckpt = dict(meta=dict(meta or {}), state_dict={k: v.detach().cpu() for k, v in model.state_dict().items()})
     if runtime is not None and runtime.opt_state is not None:
         ckpt["optimizer"] = optimizer_state_dict(model, runtime)
+    if runtime is not None and runtime.ema_state is not None:
+        ckpt["state_dict"].update(ema_state_dict(model, runtime))
+        ckpt["meta"]["ema_swapped"] = bool(runtime.ema_state["swapped"])
     torch.save(ckpt, path)
     return path
 
@@ -312,13 +387,22 @@ def save_checkpoint(model, path, meta=None, runtime=None):
 def load_checkpoint(model, path, strict=False, runtime=None, sync=True):
     """Load a reference-format checkpoint.  With `runtime` and an initialised process group this is COLLECTIVE (sync=True):
     every rank must call it, and all continue from rank 0's parameters / optimizer state / step counter -- so a file that
-    only rank 0 can read reaches every replica.  Pass sync=False for rank-local use (rank-0 evaluation, conversion)."""
+    only rank 0 can read reaches every replica.  Pass sync=False for rank-local use (rank-0 evaluation, conversion).
+    A runtime with an EMA (init_ema) takes the file's `ema_*` entries into its EMA arena -- without them the EMA restarts
+    from the loaded parameters -- and, where meta['ema_swapped'] says the file holds the EMA weights as the parameters,
+    swaps the two back: training continues exactly.  Without an EMA the entries are ignored and the model is the file's
+    parameters, the EMA weights of a swapped file."""
     ckpt = torch.load(path, map_location="cpu")
     sd = ckpt.get("state_dict", ckpt)
     sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
     missing = model.load_state_dict(sd, strict=strict)      # copies in place: parameters stay in the flat arena
     if runtime is not None and "optimizer" in ckpt and runtime.opt_state is not None:
         load_optimizer_state_dict(model, runtime, ckpt["optimizer"])
+    if runtime is not None and runtime.ema_state is not None:
+        st = runtime.ema_state
+        st["swapped"] = load_ema_state_dict(model, runtime, sd) and bool(ckpt.get("meta", {}).get("ema_swapped"))
+        if st["swapped"]:
+            runtime.swap_ema()                               # the file's parameters were the EMA weights: back to the raw ones
     if runtime is not None and sync:
         runtime.sync_replicas()                              # data-parallel: every rank continues from rank 0's state
     return ckpt.get("meta", {}), missing
@@ -455,7 +539,12 @@ def train_detector(model, batches, cfg, max_iters=None, log=print, checkpoint_pa
     step, CosineAnnealing, poly (build_lr_schedule); cfg.optimizer_config type GradientCumulativeOptimizerHook accumulates
     `cumulative_iters` batches per optimizer step (the learning rate follows the micro-iteration, as mmcv's hooks do).
     resume_from: a checkpoint of this harness; training continues at its meta['iter'] (a multiple of cumulative_iters) and
-    `batches` supplies the batches from that iteration on."""
+    `batches` supplies the batches from that iteration on.
+    cfg.custom_hooks: one dict(type='EMAHook', ...) keeps an exponential moving average of the trainable parameters
+    (parse_custom_hooks, DetectorRuntime.init_ema).  The update follows every iteration, micro-iterations of an accumulated
+    step included; every evaluation and every checkpoint is bracketed by a swap, so both see the EMA weights: a
+    checkpoint's parameters are the EMA weights, its `ema_*` entries the raw ones, and a resume with the hook is exact."""
+    ema_cfg = parse_custom_hooks(cfg)
     if cfg.get("fp16", None) is not None:        # reference: Fp16OptimizerHook + wrap_fp16_model (apis/train.py:113-117)
         wrap_fp16_model(model)                   # here: bf16 operands, fp32 accumulate / master weights, no loss scaling
     rt = model.train().runtime()
@@ -469,23 +558,29 @@ def train_detector(model, batches, cfg, max_iters=None, log=print, checkpoint_pa
     rt.init_optimizer(**kw)
     rt.set_loss_from_head(model.bbox_head)
     start = 0
+    if ema_cfg is not None:
+        rt.init_ema(**ema_cfg)                   # a copy of the parameters; a resumed run takes its EMA from the file below
     if resume_from:
         meta, _ = load_checkpoint(model, resume_from, runtime=rt)
         start = int(meta.get("iter", 0))
+        if meta.get("ema_swapped") and ema_cfg is None:
+            log(f"{resume_from} holds EMA weights as its parameters and no EMAHook is configured: training continues from "
+                "the EMA weights")
         if start % k:
             raise ValueError(f"{resume_from} was written at iteration {start}, inside an accumulated step of {k} iterations")
     interval = cfg.get("log_config", {}).get("interval", 50)
     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
     history, t0 = [], time.time()
+    ema_in = rt.ema_weights if ema_cfg is not None else contextlib.nullcontext     # swap in, evaluate or save, swap out
     for it, batch in enumerate(batches, start):
         if it >= max_iters:
             break
         lr = sched.get_lr(it)
         tg = rt.pack_targets(batch["gt_bboxes"], batch["gt_labels"], batch["points_to_gt_index"], batch["points_weight"])
         if k == 1:
-            losses = rt.train_step(batch["img"].to(rt.dev), tg, lr=lr)
+            losses = rt.train_step(batch["img"].to(rt.dev), tg, lr=lr, ema_iter=it)
         else:
-            losses = rt.train_step(batch["img"].to(rt.dev), tg, lr=lr, accumulate=micro_step(it, max_iters, k, start))
+            losses = rt.train_step(batch["img"].to(rt.dev), tg, lr=lr, accumulate=micro_step(it, max_iters, k, start), ema_iter=it)
         if (it + 1) % interval == 0 or it + 1 == max_iters:
             vals = torch.cat([losses, rt.opt_state["grad_norm"]]).cpu().tolist()     # the only host sync
             history.append(vals[:3])
@@ -494,7 +589,9 @@ def train_detector(model, batches, cfg, max_iters=None, log=print, checkpoint_pa
                     f"loss_iou: {vals[2]:.4f}, loss: {sum(vals[:3]):.4f}, grad_norm: {vals[3]:.4f}, "
                     f"time: {(time.time() - t0) / (it + 1 - start):.4f} s/iter")
         if checkpoint_path and ckpt_every and (it + 1) % ckpt_every == 0 and rank == 0:
-            save_checkpoint(model, checkpoint_path.format(iter=it + 1), meta=dict(iter=it + 1), runtime=rt)
+            with ema_in():
+                save_checkpoint(model, checkpoint_path.format(iter=it + 1), meta=dict(iter=it + 1), runtime=rt)
         if eval_every > 0 and (it + 1) % eval_every == 0:
-            evaluate_during_training(model, rt, val_loader, cfg, it + 1, log=log, eval_log=eval_log)
+            with ema_in():
+                evaluate_during_training(model, rt, val_loader, cfg, it + 1, log=log, eval_log=eval_log)
     return history

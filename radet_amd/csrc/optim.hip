@@ -329,3 +329,79 @@ extern "C" int radet_grad_accumulate(float* acc, float* g, size_t n, int mode, v
     hipLaunchKernelGGL(kernel, dim3(optim_blocks(n)), dim3(256), 0, (hipStream_t)stream, acc, g, n);
     return radet_check_launch();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Weight EMA over the trainable arena (mmcv's EMAHook: ema.mul_(1 - m).add_(param, alpha=m)) and the exchange of two arenas.
+// torch's CPU ops round twice: t = fl(ema * (1 - m)), then ONE fused multiply-add fl(m * p + t); the intrinsics pin exactly
+// that whatever -ffp-contract says.  Both kernels are shaped like grad_accumulate_kernel -- 16-byte accesses, a grid-stride
+// loop -- but take any base pointer a float may have: the host peels `head` elements so that the 16-byte body is aligned
+// (both pointers share their offset inside a 16-byte line), or makes everything head when they do not.  The peeled head
+// and the tail behind the last whole group are spread over the whole grid, one element per thread and trip.
+__device__ __forceinline__ float ema_one(float e, float p, float m, float om) { return __fmaf_rn(m, p, __fmul_rn(e, om)); }
+
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, size_t n,
+                                                         size_t head, float m, float om) {
+    const size_t n4 = (n - head) / 4;
+    float4* e4 = reinterpret_cast<float4*>(ema + head);
+    const float4* p4 = reinterpret_cast<const float4*>(p + head);
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t i = tid; i < n4; i += stride) {
+        float4 e = e4[i];
+        const float4 q = p4[i];
+        e.x = ema_one(e.x, q.x, m, om); e.y = ema_one(e.y, q.y, m, om);
+        e.z = ema_one(e.z, q.z, m, om); e.w = ema_one(e.w, q.w, m, om);
+        e4[i] = e;
+    }
+    const size_t body_end = head + n4 * 4, rest = n - n4 * 4;       // scalar elements: [0, head) and [body_end, n)
+    for (size_t k = tid; k < rest; k += stride) {
+        const size_t i = k < head ? k : body_end + (k - head);
+        ema[i] = ema_one(ema[i], p[i], m, om);
+    }
+}
+
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ a, float* __restrict__ b, size_t n, size_t head) {
+    const size_t n4 = (n - head) / 4;
+    float4* a4 = reinterpret_cast<float4*>(a + head);
+    float4* b4 = reinterpret_cast<float4*>(b + head);
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t i = tid; i < n4; i += stride) {
+        const float4 x = a4[i], y = b4[i];
+        a4[i] = y; b4[i] = x;
+    }
+    const size_t body_end = head + n4 * 4, rest = n - n4 * 4;
+    for (size_t k = tid; k < rest; k += stride) {
+        const size_t i = k < head ? k : body_end + (k - head);
+        const float x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+    }
+}
+
+// elements to peel in front of the 16-byte body of two float arrays: 0-3 when they share their offset inside a 16-byte
+// line, n (no body: the scalar path) when they do not
+static size_t ema_head(const void* a, const void* b, size_t n) {
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b;
+    if ((ua & 15) != (ub & 15)) return n;
+    const size_t head = ((16 - (ua & 15)) & 15) / 4;
+    return head < n ? head : n;
+}
+
+static bool ema_bad_pair(const void* a, const void* b, size_t n) {
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b;
+    if (a == nullptr || b == nullptr || ((ua | ub) & 3)) return true;
+    return ua < ub ? ub - ua < 4 * n : ua - ub < 4 * n;             // (the kernels' __restrict__: the arrays are disjoint)
+}
+
+extern "C" int radet_ema_update(float* ema, const float* p, size_t n, float momentum, float one_minus, void* stream) {
+    if (n == 0) return RADET_OK;
+    if (ema_bad_pair(ema, p, n)) return RADET_ERR_ARG;
+    hipLaunchKernelGGL(ema_update_kernel, dim3(optim_blocks(n)), dim3(256), 0, (hipStream_t)stream, ema, p, n,
+                       ema_head(ema, p, n), momentum, one_minus);
+    return radet_check_launch();
+}
+
+extern "C" int radet_ema_swap(float* a, float* b, size_t n, void* stream) {
+    if (n == 0) return RADET_OK;
+    if (ema_bad_pair(a, b, n)) return RADET_ERR_ARG;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(optim_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, n, ema_head(a, b, n));
+    return radet_check_launch();
+}

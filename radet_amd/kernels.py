@@ -1495,6 +1495,16 @@ def grad_accumulate(acc, g, n, mode):
     _lib.call("radet_grad_accumulate", _ptr(acc), _ptr(g), C.c_size_t(n), mode, _stream())
 
 
+def ema_update(ema, p, n, momentum):
+    """ema = ema * (1 - momentum) + momentum * p with torch's CPU rounding (radet_ema_update): `momentum` is a Python float
+    (a double); it and 1 - momentum are each rounded once to fp32 on the way into the call"""
+    _lib.call("radet_ema_update", _ptr(ema), _ptr(p), C.c_size_t(n), float(momentum), 1.0 - float(momentum), _stream())
+
+
+def ema_swap(a, b, n):
+    _lib.call("radet_ema_swap", _ptr(a), _ptr(b), C.c_size_t(n), _stream())
+
+
 def decode_ws_bytes(B, nlvl, nms_pre):
     return int(_lib.load().radet_decode_ws_bytes(B, nlvl, nms_pre))
 

@@ -5,6 +5,7 @@ with backward + fused clip/AdamW) and inference (decode + NMS).
 Replaces what the reference obtains from torch autograd + mmcv's DDP wrapper / OptimizerHook
 (radet/apis/train.py:73-126, radet/models/detectors/base.py:185-253).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -194,6 +195,19 @@ def build_opt_runs(flat, groups):
     return check_opt_runs(runs, flat.n_train)
 
 
+def ema_momentum(it, momentum, interval=1, warm_up=100):
+    """mmcv EMAHook's momentum for the update after iteration `it` (0-based, runner.iter): min(momentum ** interval,
+    (1 + it) / (warm_up + it)), in Python doubles.  The hook fires only when it % interval == 0."""
+    if warm_up + it == 0:                       # (warm_up = 0 at iteration 0 is 1 / 0 in mmcv; here the EMA restarts from the parameters)
+        return 1.0
+    return min(momentum ** interval, (1 + it) / (warm_up + it))
+
+
+def ema_key(name):
+    """mmcv EMAHook's buffer name of a parameter: 'ema_' + the name with every '.' replaced by '_'"""
+    return "ema_" + name.replace(".", "_")
+
+
 class _StreamWork:
     """What GradReducer needs of a c10d Work, for a collective issued synchronously on a stream of ours: an event behind it"""
 
@@ -344,6 +358,8 @@ class DetectorRuntime:
         arenas = [self.flat.params, self.flat.frozen]
         if self.opt_state is not None:
             arenas += [self.opt_state[k] for k in ("m", "v", "buf") if self.opt_state.get(k) is not None]
+        if self.ema_state is not None:
+            arenas.append(self.ema_state["ema"])      # (every rank then computes the same EMA: no further communication)
         for t in arenas:
             dist.broadcast(t, src)
         step = torch.tensor([self.step_count], dtype=torch.int64, device=self.dev)
@@ -533,6 +549,53 @@ class DetectorRuntime:
 
     _acc = None             # the accumulation arena (train_step(accumulate=...)): same layout as the gradient arena
 
+    # ------------------------------------------------------------------ weight EMA (mmcv's EMAHook)
+    ema_state = None        # dict(ema, momentum, interval, warm_up, swapped) once init_ema() was called
+
+    def init_ema(self, momentum=0.0002, interval=1, warm_up=100):
+        """Exponential moving average of the trainable arena, mmcv 1.3.18's EMAHook restated: the EMA arena has the layout of
+        `flat.params` and starts as a copy of it; train_step(..., ema_iter=it) then runs, for every iteration with
+        it % interval == 0, ema = ema * (1 - m) + m * param with m = ema_momentum(...).  Frozen parameters and buffers (BN
+        running statistics) are not averaged.  Call it on every rank, once the parameters are what training starts from; a
+        later apis.load_checkpoint(..., runtime=) takes the file's EMA, or restarts it from the loaded parameters, and
+        sync_replicas() broadcasts the arena with the others."""
+        if not 0.0 < momentum < 1.0:
+            raise ValueError(f"EMA momentum must lie in (0, 1), got {momentum!r}")
+        if not (isinstance(interval, int) and not isinstance(interval, bool) and interval > 0):
+            raise ValueError(f"EMA interval must be a positive int, got {interval!r}")
+        self.ema_state = dict(ema=self.flat.params.clone(), momentum=float(momentum), interval=interval,
+                              warm_up=warm_up, swapped=False)
+        return self.ema_state
+
+    def swap_ema(self):
+        """Exchange the parameter arena and the EMA arena (one launch): the model's parameters are then the averaged weights
+        and `ema_state['ema']` holds the raw ones, until the next call puts both back bit for bit."""
+        st = self.ema_state
+        if st is None:
+            raise RuntimeError("swap_ema() without init_ema(): this runtime keeps no EMA")
+        K.ema_swap(self.flat.params, st["ema"], self.flat.n_train)
+        st["swapped"] = not st["swapped"]
+        self.engine.params_changed()              # the kernel wrote the arena behind torch's back: fold again next pass
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with rt.ema_weights():` -- the block sees the EMA weights as the parameters; the raw weights are back after it"""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def _ema_update(self, it):
+        """The EMA update of iteration `it`, if it fires: one eager launch on the current stream behind the step (taped or
+        not: it is never recorded, so both give the same bits and the tapes hold what they held without an EMA)."""
+        st = self.ema_state
+        if st is None or it is None or it % st["interval"]:
+            return
+        if st["swapped"]:
+            raise RuntimeError("train_step with the EMA weights swapped in: call swap_ema() again first")
+        K.ema_update(st["ema"], self.flat.params, self.flat.n_train, ema_momentum(it, st["momentum"], st["interval"], st["warm_up"]))
+
     def bf16_buckets(self):
         """Gradient buckets travel as bf16 (fp32 arena -> bf16 staging -> all-reduce -> back) by default in the bf16-STORAGE
         mode only: its step is half as long as the fp32 one while the fp32 exchange (127.7 MB per step, ~1.5 ms of per-link
@@ -641,7 +704,7 @@ class DetectorRuntime:
             return "plain", 1
         return ("first" if j == 0 else "last" if j == k - 1 else "middle"), k
 
-    def train_step(self, img, tg, lr=None, next_img=None, accumulate=None):
+    def train_step(self, img, tg, lr=None, next_img=None, accumulate=None, ema_iter=None):
         """One optimisation step. With torch.distributed initialised (backend nccl = RCCL) gradients
         are summed across ranks per bucket on a side stream while the backward of earlier layers is
         still running; the mean (1/world) is folded into the fused clip+AdamW kernel.
@@ -655,6 +718,10 @@ class DetectorRuntime:
         gradient arena and runs the optimizer with grad_div = world * k -- the mean over ranks and micro-batches, folded
         into the fused kernel.  Only the last micro-step moves the parameters and `step_count`; `lr` is used by it alone.
         None, or k = 1, is the plain step.
+        ema_iter: the iteration number (0-based, counted like mmcv's runner.iter) when init_ema() was called: the EMA update
+        of that iteration follows the step on the same stream -- behind the optimizer kernel, or at the end of a micro-step
+        that moved nothing (mmcv's hook fires on every iteration), and in front of the next step's weight fold.  It is one
+        eager launch outside the tape.  None, or no init_ema(): the step issues what it issued before.
         Steady-state calls are replayed from a launch tape (see above); results are bit-identical to the eager step."""
         phase, k = self._phase(accumulate)
         if phase != "plain" and self._acc is None:
@@ -681,7 +748,9 @@ class DetectorRuntime:
                 st = self._new_slot(phase, key)
             if st["tape"] is not None:
                 if self._tape_still_valid(phase):
-                    return self._replay_step(st["tape"], img, tg, lr, world, phase)
+                    out = self._replay_step(st["tape"], img, tg, lr, world, phase)
+                    self._ema_update(ema_iter)
+                    return out
                 st = self._new_slot(phase, key)                                       # something moved: start over
             st["count"] += 1
             if st["count"] > self.tape_after and st["failed"] is None and (not use_reducer or self.reducer is not None):
@@ -753,6 +822,7 @@ class DetectorRuntime:
                 st["failed"] = record.poisoned
                 if os.environ.get("RADET_TAPE_STRICT") == "1":
                     raise _lib.RadetHipError(f"launch tape could not be recorded: {record.poisoned}")
+        self._ema_update(ema_iter)
         if self.loss_weights is not None:       # reported values carry the configured loss weights, like the reference's
             return self.engine.losses * self.loss_weights
         return self.engine.losses

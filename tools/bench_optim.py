@@ -1,7 +1,8 @@
 """Times the optimizer kernels on the headline arena (the trainable parameters of configs/bop/r50_ycbv_pbr.py) and writes
 profiles/bench_optim.json.  The variants -- radet_adamw_step (the yardstick), radet_adamw_step_runs with the table that
 paramwise_cfg=dict(norm_decay_mult=0.) makes, radet_sgd_step with and without that table and with and without momentum,
-radet_grad_accumulate in its three modes -- are launched interleaved, round after round, each between two HIP events; per
+radet_grad_accumulate in its three modes, radet_ema_update (beside the accumulate mode that moves the same 12 bytes per
+element) and radet_ema_swap -- are launched interleaved, round after round, each between two HIP events; per
 variant: median / min / max / 10th-90th percentile of the device time, the bytes the algorithm has to move and the rate
 they give.  Needs an MI355X: there is no CPU path.
 
@@ -19,12 +20,8 @@ import numpy as np
 import torch
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=40)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_optim.json"))
-    args = ap.parse_args()
+def measure(args):
+    """the timed rounds; args: rounds, warmup.  Returns the dictionary main() writes."""
     if args.rounds < 20:
         raise SystemExit("at least 20 timed launches per variant")
     if not torch.cuda.is_available():
@@ -46,6 +43,7 @@ def main():
     p = torch.randn(n, device=dev, generator=gen)
     g = torch.randn(n, device=dev, generator=gen) * 1e-3
     m, v, buf, acc = (torch.zeros(n, device=dev) for _ in range(4))
+    ema = torch.zeros(n, device=dev)
     parts, gn = torch.zeros(1024, device=dev), torch.zeros(1, device=dev)
     K.sqnorm_partials(g, n, parts)
     lr, step = 1e-6, 7                                              # (small: thousands of launches must not move p far)
@@ -62,6 +60,11 @@ def main():
         ("grad_accumulate_set", 2 * F, lambda: K.grad_accumulate(acc, g, n, K.GRAD_ACC_SET)),
         ("grad_accumulate_add", 3 * F, lambda: K.grad_accumulate(acc, g, n, K.GRAD_ACC_ADD)),
         ("grad_accumulate_restore", 3 * F, lambda: K.grad_accumulate(acc, g, n, K.GRAD_ACC_RESTORE)),
+        # the EMA update on the arenas of the accumulate modes (mode 1 moves the same bytes: read two arenas, write one);
+        # the swap twice, so that every round starts from the same arenas
+        ("ema_update", 3 * F, lambda: K.ema_update(acc, g, n, 0.0002)),
+        ("ema_swap", 4 * F, lambda: K.ema_swap(acc, ema, n)),
+        ("ema_swap_back", 4 * F, lambda: K.ema_swap(acc, ema, n)),
     ]
     g0 = g.clone()
     times = {name: [] for name, _, _ in variants}
@@ -92,6 +95,20 @@ def main():
     out["runs_vs_yardstick"] = dict(delta_us=round(t["median_us"] - y["median_us"], 2),
                                     yardstick_spread_us=round(y["p90_us"] - y["p10_us"], 2),
                                     ratio=round(t["median_us"] / y["median_us"], 4))
+    y, t = out["variants"]["grad_accumulate_add"], out["variants"]["ema_update"]
+    out["ema_vs_sibling"] = dict(delta_us=round(t["median_us"] - y["median_us"], 2), sibling_p10_us=y["p10_us"],
+                                 sibling_p90_us=y["p90_us"], inside_band=bool(y["p10_us"] <= t["median_us"] <= y["p90_us"]),
+                                 ratio=round(t["median_us"] / y["median_us"], 4))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_optim.json"))
+    args = ap.parse_args()
+    out = measure(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
         json.dump(out, fh, indent=1)
