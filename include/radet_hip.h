@@ -713,6 +713,42 @@ int radet_cutout_f32(float* out, int nbatch, int Hp, int Wp, const int* desc, in
 int radet_preprocess_frames(const int* desc, int nimg, int Hp, int Wp, float m0, float m1, float m2, float s0, float s1,
                             float s2, float* out, void* stream);
 
+/* ---- detections -> a packed batch of RoI crops (csrc/crops.hip), two launches, nothing read back to the host.
+ * radet_crop_plan (one workgroup): boxes f32 [B,K,4] (16-byte aligned), scores f32 [B,K], counts i32 [B] -- the NMS outputs
+ *      as they are -- walked image-major, then by rank j < counts[b].  A detection is valid if its four coordinates are
+ *      finite, w = x2 - x1 > 0, h = y2 - y1 > 0, |cx|, |cy| < 2^20 and score >= score_thr; the valid ones are compacted in
+ *      order (stable).  counters i32 [2 + B]: counters[0] = n_out = min(n_total, cap), counters[1] = n_total = the number
+ *      of valid detections, counters[2 + b] = the number of rows of the frames 0 .. b (frame b's rows end there: a host
+ *      that copies the counters splits the batch per frame without reading a row);
+ *      rows i32 [cap][CROP_ROW_INTS] = {b, j, wx0, wy0, ww, wh} for the first n_out of them, rows beyond are not written.
+ *      The window has the output's aspect ratio (no distortion) and may overhang the frame or miss it; fp32, every
+ *      operation rounded once:
+ *          a  = (float)Wo / (float)Ho
+ *          hs = fmaxf(h, w / a) * scale                       ws = hs * a
+ *          wh = clamp((int)ceilf(hs), 1, CROP_MAX_SIDE)       ww = clamp((int)ceilf(ws), 1, CROP_MAX_SIDE)
+ *          cx = (x1 + x2) * 0.5f                              cy = (y1 + y2) * 0.5f
+ *          wx0 = (int)floorf(cx - 0.5f * (float)ww)           wy0 = (int)floorf(cy - 0.5f * (float)wh)
+ * radet_crop_frames (grid: pixel tiles x cap): slot n < n_out (read from counters on the device; the other blocks exit
+ *      before any load or store) = the wh x ww window at (wy0, wx0) of frame b resized to Ho x Wo: taps and coefficients of
+ *      a wh x ww image (the edge clamp is at the window's border), each tap read at (wy0 + ty, wx0 + tx) of the frame or
+ *      the fill colour outside it -- bit for bit radet_resize_linear_u8 with the view row {Ho, Wo, wy0, wx0, wh, ww, 0, 0,
+ *      Ho, Wo, 0, fill}.  desc = B rows of PREP_DESC_INTS ints as above (address, row stride, source h, w; the other
+ *      fields are not read); fill = c0 | c1 << 8 | c2 << 16 in the frame's channel order.  flags: CROP_F32: out f32
+ *      [cap,3,Ho,Wo] = (q - mean) * stdinv per plane, with CROP_TO_RGB after the BGR->RGB swap (radet_augment_finish's
+ *      Normalize); without CROP_F32: out u8 [cap,Ho,Wo,3], the raw BGR bytes (4-byte aligned).  A row whose b is not in
+ *      [0, B) or whose window is not one the plan writes is skipped.
+ * RADET_ERR_ARG before any launch: B, K or cap < 0, K == 0 or a NULL pointer with B and cap > 0, Ho or Wo outside
+ *      [1, 4096], cap > 65535, B * K >= 2^31, scale not finite or <= 0, unknown flags.  B == 0 or cap == 0: RADET_OK, no
+ *      launch. */
+#define CROP_ROW_INTS 6
+#define CROP_MAX_SIDE 16384
+#define CROP_TO_RGB 1
+#define CROP_F32 2
+int radet_crop_plan(const float* boxes, const float* scores, const int* counts, int B, int K, int Ho, int Wo, float scale,
+                    float score_thr, int cap, int* rows, int* counters, void* stream);
+int radet_crop_frames(const int* rows, const int* counters, const int* desc, int B, int cap, int Ho, int Wo, int flags,
+                      unsigned fill, float m0, float m1, float m2, float s0, float s1, float s2, void* out, void* stream);
+
 /* ---- stand-alone box / loss operators behind the registered classes (used on their own; inside the detector the same
  *      arithmetic runs fused in radet_head_loss / radet_decode_candidates) ------------------------------------------ */
 /* bbox_overlaps / BboxOverlaps2D (radet/core/bbox/iou_calculators/iou2d_calculator.py:43-159): boxes [batch, M, 4] and

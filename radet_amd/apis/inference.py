@@ -69,29 +69,73 @@ def _frame_pipeline(model):
     return pipeline
 
 
-def _prepare_frames(pipeline, frames):
-    """one batch of frames, of any sizes, through the pipeline: the collated test batch (one upload, one launch)"""
+def _prepare_frames(pipeline, frames, with_source=False):
+    """one batch of frames, of any sizes, through the pipeline: the collated test batch (one upload, one launch); with_source:
+    (that batch, (descriptor table, frames)) for the crops that are cut from the frames behind NMS"""
     import random
     planned = [pipeline.plan(dict(img=f, bbox_fields=[], mask_fields=[], seg_fields=[]), random, np.random) for f in frames]
-    return pipeline.run(planned, collate=True)
+    return pipeline.run_frames(planned) if with_source else pipeline.run(planned, collate=True)
 
 
-def _inference_frames(model, frames):
-    if not frames:
-        return []
-    with torch.no_grad():
-        return model(return_loss=False, rescale=True, **_prepare_frames(_frame_pipeline(model), frames))
+_CROP_KEYS = ("size", "scale", "score_thr", "max_crops", "fill", "normalize")
 
 
-def detect_frames(model, frames, batch_size=8, on_device=False):
+def _crop_request(model, crops):
+    """crops=dict(size=..., scale=1.2, score_thr=0.0, max_crops=None, fill=(0, 0, 0), normalize=...) -> ops.crops.CropSpec.
+    normalize defaults to the test pipeline's img_norm_cfg (None asks for u8 NHWC BGR crops), max_crops to every detection
+    slot of the batch (B * max_per_img)."""
+    from ..ops.crops import crop_spec
+    if not isinstance(crops, dict) or "size" not in crops or set(crops) - set(_CROP_KEYS):
+        raise ValueError(f"crops={crops!r}: expected dict(size=..., [{', '.join(_CROP_KEYS[1:])}])")
+    kw = dict(crops)
+    if "normalize" not in kw:
+        stages = list(model.cfg.data.test.pipeline)
+        stages += [t for s in stages for t in (s.get("transforms") or ())]
+        norm = [s for s in stages if s.get("type") == "Normalize"]
+        if len(norm) != 1:
+            raise ValueError("crops: the test pipeline has no single Normalize stage; pass normalize=dict(mean, std, to_rgb)")
+        kw["normalize"] = dict(mean=norm[0]["mean"], std=norm[0]["std"], to_rgb=norm[0].get("to_rgb", True))
+    return crop_spec(**kw)
+
+
+def _single_view(data):
+    imgs, metas = data["img"], data["img_metas"]
+    if isinstance(imgs, (list, tuple)):                      # (a MultiScaleFlipAug pipeline: the single test view)
+        imgs, metas = imgs[0], metas[0]
+    return imgs, metas
+
+
+def _inference_frames(model, frames, crops=None):
+    if crops is None:
+        if not frames:
+            return []
+        with torch.no_grad():
+            return model(return_loss=False, rescale=True, **_prepare_frames(_frame_pipeline(model), frames))
+    from ..ops.crops import check_frames
+    check_frames(frames)
+    spec = _crop_request(model, crops)
+    data, source = _prepare_frames(_frame_pipeline(model), frames, True)
+    imgs, metas = _single_view(data)
+    if model.training:
+        model.eval()
+    dets, out, _ = model.runtime().detect(imgs, metas, model.test_cfg, True, crops=(spec, source[0]))
+    del source                                               # (detect has waited for the batch: the frames' table can go)
+    return [bbox2result(b, l, model.bbox_head.num_classes) for b, l in dets], out
+
+
+def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
     """Generator over an iterable of frames (ndarray or device tensor HxWx3 uint8 BGR, sizes may differ): batches of
     `batch_size` frames (the last one smaller) go through the frame pipeline and `DetectorRuntime.detect_stream`, so the host
     is one batch behind the device.  Yields one result per frame, in order: the per-class list of ndarray[k, 5] (boxes in the
     frame's own coordinates), or with on_device=True the (dets f32[k, 5], labels i64[k]) device tensors.  Leaving the loop
-    early closes the stream underneath, which leaves the runtime ready for the next call."""
+    early closes the stream underneath, which leaves the runtime ready for the next call.
+    crops=dict(size=..., ...) as for inference_detector: yields (result, Crops of that frame) -- the crops of a batch are cut
+    from its frames on the device behind its NMS; a frame's record holds views of the batch's tensors and the batch's n_total."""
+    from ..ops.crops import check_frames, split_crops
     if batch_size < 1:
         raise ValueError(f"batch_size={batch_size}")
     pipeline = _frame_pipeline(model)
+    spec = None if crops is None else _crop_request(model, crops)
     if model.training:
         model.eval()
     num_classes = model.bbox_head.num_classes
@@ -108,26 +152,45 @@ def detect_frames(model, frames, batch_size=8, on_device=False):
 
     def prepared():
         for group in batches():
-            data = _prepare_frames(pipeline, group)
-            imgs, metas = data["img"], data["img_metas"]
-            if isinstance(imgs, (list, tuple)):              # (a MultiScaleFlipAug pipeline: the single test view)
-                imgs, metas = imgs[0], metas[0]
-            yield imgs, metas
+            if spec is None:
+                yield _single_view(_prepare_frames(pipeline, group))
+                continue
+            check_frames(group)
+            data, source = _prepare_frames(pipeline, group, True)
+            yield _single_view(data) + (source,)             # (the stream carries the table and the frames with the batch)
 
-    stream = model.runtime().detect_stream(prepared(), model.test_cfg, rescale=True)
+    stream = model.runtime().detect_stream(prepared(), model.test_cfg, rescale=True, **({} if spec is None else dict(crops=spec)))
     try:
         for dets in stream:
-            for boxes, labels in dets:
-                yield (boxes, labels) if on_device else bbox2result(boxes, labels, num_classes)
+            per_frame = None
+            if spec is not None:
+                dets, batch_crops, ends = dets
+                per_frame = split_crops(batch_crops, ends)  # (ends came with the counts: nothing is read from the device)
+            for i, (boxes, labels) in enumerate(dets):
+                res = (boxes, labels) if on_device else bbox2result(boxes, labels, num_classes)
+                yield res if per_frame is None else (res, per_frame[i])
     finally:
         stream.close()
 
 
-def inference_detector(model, imgs, scale_factor=None):
+def inference_detector(model, imgs, scale_factor=None, crops=None):
     """imgs: f32[B,3,H,W] (normalised) -> list[B] of list[num_classes] of ndarray[k,5]; or a file name -> the result of that
     image; or a list of file names -> the list of their results; or a loaded image (ndarray, or uint8 device tensor, HxWx3
     BGR) -> its result; or a list of those, of any sizes -> the list of their results, computed as one batch
-    (radet/apis/inference.py:86-140)."""
+    (radet/apis/inference.py:86-140).
+    crops=dict(size=(Ho, Wo) or int, scale=1.2, score_thr=0.0, max_crops=None, fill=(0, 0, 0), normalize=...), with loaded
+    frames only: returns (results, ops.Crops) -- one crop per detection, cut from its frame on the device behind NMS, resized to
+    `size` and normalised like the test pipeline (normalize=None: u8 NHWC BGR); see radet_amd.ops.crop_detections.  An empty
+    list of frames is refused with crops= (without it the result is []): there is no batch to cut crops from.
+    Memory: the crops' tensor is allocated before the number of detections is known, max_crops slots of 3 * Ho * Wo values
+    (f32: 12 * Ho * Wo bytes each), and the returned views keep all of it alive.  The default max_crops is every detection
+    slot of the batch, B * max_per_img -- 629 MB for 8 frames x 100 slots of 256 x 256 f32, twice that in flight in
+    detect_frames -- so pass the max_crops the pose stage can take."""
+    if crops is not None:
+        if _is_frame(imgs):
+            res, out = _inference_frames(model, [imgs], crops)
+            return res[0], out
+        return _inference_frames(model, list(imgs) if isinstance(imgs, (list, tuple)) else imgs, crops)
     if isinstance(imgs, str):
         return _inference_files(model, [imgs])[0]
     if isinstance(imgs, (list, tuple)) and all(isinstance(i, str) for i in imgs):

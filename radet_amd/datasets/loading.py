@@ -1170,6 +1170,24 @@ def frame_desc_rows(frames, dst_hw, to_rgb, host_base):
     return rows, offs, o
 
 
+def upload_frames(frames, dst_hw, to_rgb, dev):
+    """[descriptor table | host frames, packed] into one device buffer in ONE pinned, non-blocking copy (the table needs the
+    buffer's address, so the buffer is allocated first); frames that are device tensors are not copied, the table holds their
+    addresses.  Returns the table, i32 [B, PREP_DESC_INTS]: a view of the buffer, which it keeps alive."""
+    head = len(frames) * K.PREP_DESC_INTS * 4
+    _, _, nbytes = frame_desc_rows(frames, dst_hw, to_rgb, 0)
+    up = torch.empty(head + nbytes, dtype=torch.uint8, device=dev)
+    rows, offs, _ = frame_desc_rows(frames, dst_hw, to_rgb, up.data_ptr() + head)
+    stage = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    host[:head] = rows.reshape(-1).view(np.uint8)
+    for f, o in zip(frames, offs):
+        if o is not None:
+            np.copyto(host[head + o:head + o + f.size].reshape(f.shape), f)
+    up.copy_(stage, non_blocking=True)
+    return up[:head].view(torch.int32)
+
+
 class ImagePipeline:
     """A pipeline that starts from files: host planning per sample, one batched device pass per batch.  Or from frames in
     memory (LoadImageFromWebcam first): a test pipeline whose device pass is one upload and one launch (_run_frames)."""
@@ -1583,7 +1601,7 @@ class ImagePipeline:
     def run(self, planned, collate=False):
         """device part of a batch of planned samples; returns per-sample dicts, or one collated batch dict"""
         if self.frames:
-            return self._run_frames(planned, collate)
+            return self._run_frames(planned, collate)[0]
         dev = self._dev()
         B = len(planned)
         # each sample's view: RandomCrop planned the output window of the virtual resized image, Expand / MinIoURandomCrop the
@@ -1707,11 +1725,21 @@ class ImagePipeline:
                     p2g[i], pw[i] = a[j], b[j]
         return self._collect(planned, out, p2g, pw, collate)
 
+    def run_frames(self, planned):
+        """a frame pipeline's collated batch together with what its frames are read from, for a caller that reads them again
+        (the RoI crops of the batch's detections): -> (batch, (descriptor table i32 [B, PREP_DESC_INTS], frames)).  The table
+        is a view of the upload buffer and keeps it alive; the crops are cut later, possibly on another stream, so the caller
+        holds both until then."""
+        if not self.frames:
+            raise ValueError("run_frames: not a pipeline that starts from frames in memory")
+        return self._run_frames(planned, True)
+
     def _run_frames(self, planned, collate):
         """device part of a batch of planned frames (LoadImageFromWebcam): the descriptor table and the host frames go up
         in ONE pinned, non-blocking copy -- frames that are device tensors are not copied at all, the table holds their
         addresses -- and ONE radet_preprocess_frames launch writes the batch; no packed temporaries.  Device frames must be
-        ready on the current stream; nothing here waits for the device."""
+        ready on the current stream; nothing here waits for the device.  Returns (what run() returns, (descriptor table,
+        frames)) -- see run_frames."""
         dev = self._dev()
         B = len(planned)
         frames = [s["img"] for s in planned]
@@ -1730,23 +1758,12 @@ class ImagePipeline:
         Wp = max(s["pad_shape"][1] for s in planned)
         if any(s["pad_shape"][0] < h or s["pad_shape"][1] < w for s, (h, w) in zip(planned, hw)):
             raise ValueError("pad_shape smaller than the image")
-        # upload buffer: [descriptor table | host frames, packed]; the table needs the buffer's address, so allocate first
-        head = B * K.PREP_DESC_INTS * 4
-        _, _, nbytes = frame_desc_rows(frames, hw, cfg0["to_rgb"], 0)
-        up = torch.empty(head + nbytes, dtype=torch.uint8, device=dev)
-        rows, offs, _ = frame_desc_rows(frames, hw, cfg0["to_rgb"], up.data_ptr() + head)
-        stage = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=True)
-        host = stage.numpy()
-        host[:head] = rows.reshape(-1).view(np.uint8)
-        for f, o in zip(frames, offs):
-            if o is not None:
-                np.copyto(host[head + o:head + o + f.size].reshape(f.shape), f)
-        up.copy_(stage, non_blocking=True)
+        table = upload_frames(frames, hw, cfg0["to_rgb"], dev)
         out = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=dev)
         mean = cfg0["mean"].astype(np.float64).astype(np.float32)
         stdinv = (1.0 / cfg0["std"].astype(np.float64)).astype(np.float32)
-        K.preprocess_frames(up[:head].view(torch.int32), B, Hp, Wp, mean, stdinv, out)
-        return self._collect(planned, out, None, None, collate)
+        K.preprocess_frames(table, B, Hp, Wp, mean, stdinv, out)
+        return self._collect(planned, out, None, None, collate), (table, frames)
 
     def _distance_maps(self, planned, hw, img, lsum, params, dev):
         """The mask-free sampler's maps of a batch, f32 [G_i, h, w] per sample: every box's padded crop cut from the

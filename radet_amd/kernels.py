@@ -1880,6 +1880,41 @@ def preprocess_frames(desc, n, Hp, Wp, mean, stdinv, out):
               *[float(v) for v in stdinv], _ptr(out), _stream())
 
 
+# ---------------------------------------------------------------------- detections -> RoI crops (csrc/crops.hip)
+CROP_ROW_INTS = 6                  # include/radet_hip.h: {b, j, wx0, wy0, ww, wh}
+CROP_MAX_SIDE = 16384
+CROP_MAX_OUT = 4096                # largest output side
+CROP_MAX_SLOTS = 65535             # largest cap (the pixel kernel's second grid dimension)
+CROP_TO_RGB, CROP_F32 = 1, 2
+
+
+def crop_plan(boxes, scores, counts, size, scale, score_thr, cap, rows, counters):
+    """the NMS outputs boxes f32 [B,K,4], scores f32 [B,K], counts i32 [B] -> rows i32 [cap, CROP_ROW_INTS] (the windows of
+    the valid detections, in order, the first cap of them) and counters i32 [2 + B] = {n_out, n_total, ends [B]}: frame b's
+    rows are [ends[b - 1] (0 for b == 0), ends[b]); size = (Ho, Wo)"""
+    B, Kd = int(boxes.shape[0]), int(boxes.shape[1])
+    assert boxes.dtype == torch.float32 and tuple(boxes.shape) == (B, Kd, 4) and scores.dtype == torch.float32
+    assert tuple(scores.shape) == (B, Kd) and counts.dtype == torch.int32 and counts.numel() == B
+    assert rows.dtype == torch.int32 and rows.numel() >= cap * CROP_ROW_INTS and counters.dtype == torch.int32 and counters.numel() >= 2 + B
+    _lib.call("radet_crop_plan", _ptr(boxes), _ptr(scores), _ptr(counts), B, Kd, int(size[0]), int(size[1]), float(scale),
+              float(score_thr), int(cap), _ptr(rows), _ptr(counters), _stream())
+
+
+def crop_frames(rows, counters, desc, B, cap, size, out, fill=0, mean=None, stdinv=None, to_rgb=False):
+    """the slots n < counters[0] of out: the window of rows[n] cut from the frame of desc i32 [B, PREP_DESC_INTS] and resized
+    to size = (Ho, Wo).  out f32 [cap,3,Ho,Wo] (mean, stdinv given: Normalize, to_rgb as there) or u8 [cap,Ho,Wo,3] (raw
+    BGR); fill = c0 | c1 << 8 | c2 << 16 in the frames' channel order"""
+    Ho, Wo = int(size[0]), int(size[1])
+    f32 = out.dtype == torch.float32
+    assert f32 or out.dtype == torch.uint8
+    assert out.numel() >= cap * 3 * Ho * Wo and desc.dtype == torch.int32 and desc.numel() >= B * PREP_DESC_INTS
+    assert rows.dtype == torch.int32 and rows.numel() >= cap * CROP_ROW_INTS and f32 == (mean is not None) == (stdinv is not None)
+    flags = (CROP_F32 if f32 else 0) | (CROP_TO_RGB if f32 and to_rgb else 0)
+    _lib.call("radet_crop_frames", _ptr(rows), _ptr(counters), _ptr(desc), int(B), int(cap), Ho, Wo, flags, int(fill),
+              *[float(v) for v in (mean if f32 else (0, 0, 0))], *[float(v) for v in (stdinv if f32 else (1, 1, 1))], _ptr(out),
+              _stream())
+
+
 # ---------------------------------------------------------------------- COCO-protocol evaluation (csrc/cocoeval.hip)
 COCO_MAX_GT = 512                  # RADET_COCO_MAX_GT of include/radet_hip.h: ground truths per (category, image) segment
 COCO_ERR_OVERSIZE = -3             # RADET_ERR_COCO_OVERSIZE

@@ -9,7 +9,8 @@ import torch
 from .. import kernels as K
 
 __all__ = ["vote_nms", "global_vote_nms", "cluster_nms", "batched_nms", "soft_nms", "MBD_box2distance", "GDT_box2distance", "MBD", "GDT",
-           "mbd_batch", "gdt_batch", "border_seeds", "resize_batch", "gaussian_blur9_batch", "sobel_edge_batch"]
+           "mbd_batch", "gdt_batch", "border_seeds", "resize_batch", "gaussian_blur9_batch", "sobel_edge_batch", "crop_detections",
+           "Crops"]
 
 _MAX = 65536      # 16-bit positions in the kernel's sort keys (above 8192 the sorts run in global memory)
 
@@ -459,3 +460,6 @@ class GDT_box2distance:
         idx = [i for i, e in enumerate(mask_enable) if e]          # (disabled crops never leave the host)
         maps, _ = self.packed_maps(_Packed.pack([box_images[i] for i in idx], torch.uint8, 3), [True] * len(idx))
         return _cropped(box_images, mask_enable, bbox_images_xy, maps, idx, torch.float32)
+
+
+from .crops import Crops, crop_detections  # noqa: E402  (RoI crops of detections: its own module, it needs _dev from here)

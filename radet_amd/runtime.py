@@ -933,16 +933,49 @@ DetectorRuntime.neck_api = _neck_api
 
 
 # ---------------------------------------------------------------------- inference + module-level API
-def _detect(self, img, img_metas, test_cfg, rescale=False):
+def _detect(self, img, img_metas, test_cfg, rescale=False, crops=None):
     """simple_test: forward -> per-level threshold/top-k/decode -> NMS, all on the GPU, batched over
-    images; returns [(dets f32[K,5], labels i64[K])] per image on the device."""
+    images; returns [(dets f32[K,5], labels i64[K])] per image on the device.  crops = (CropSpec, frame descriptor table):
+    the RoI crops of the detections are cut from the batch's frames behind NMS (two more launches, the same stream, their
+    counters in the counts' own device-to-host copy); returns (that list, ops.crops.Crops of the batch, ends i32 [B] on the
+    host: frame b's crops are [ends[b - 1], ends[b]) of the batch's -- ops.crops.split_crops)."""
     with torch.no_grad():
         self.forward(img.to(self.dev))
         hw, sf = _meta_tensors(self, img_metas, rescale)
-        return _post_collect(self, *_post_launch(self, hw, sf, test_cfg))
+        if crops is None:
+            return _post_collect(self, *_post_launch(self, hw, sf, test_cfg))
+        counts = _crop_counts(self, len(img_metas))
+        outs = _post_launch(self, hw, sf, test_cfg, counts_out=counts)
+        job = _crops_launch(self, outs, counts, crops)
+        host = counts.cpu().numpy()
+        return (_post_collect(self, *outs, counts=host),) + _crops_collect(job, host, len(img_metas))
 
 
-def _detect_stream(self, batches, test_cfg, rescale=False):
+def _crop_counts(self, B):
+    """the detection counts of a batch with crops: i32 [B + 2 + B] = counts [B] | the plan's counters: n_out | n_total | where
+    each frame's rows end [B], so that one device-to-host copy brings all the host needs to hand the crops out per frame"""
+    return torch.zeros(B + 2 + B, dtype=torch.int32, device=self.dev)
+
+
+def _crops_launch(self, outs, counts, crops):
+    """the two crop launches behind _post_launch, on the current stream; crops = (CropSpec, descriptor table)"""
+    from .ops.crops import launch_crops
+    spec, desc = crops
+    ob, osc, _, oc = outs
+    B, k = int(ob.shape[0]), int(ob.shape[1])
+    cap = spec.max_crops if spec.max_crops is not None else B * k
+    if cap > K.CROP_MAX_SLOTS:
+        raise ValueError(f"crops: {B} x {k} detection slots exceed the kernel's {K.CROP_MAX_SLOTS}; pass max_crops")
+    return launch_crops(spec, ob, osc, oc, desc, cap, counts[B:])
+
+
+def _crops_collect(job, host_counts, B):
+    """host_counts: _crop_counts' words on the host -> (Crops of the batch, ends [B])"""
+    from .ops.crops import collect_crops
+    return collect_crops(job[0], job[1], host_counts[B], host_counts[B + 1]), host_counts[B + 2:B + 2 + B].copy()
+
+
+def _detect_stream(self, batches, test_cfg, rescale=False, crops=None):
     """`detect` over an iterable of (img, img_metas) batches with the host one batch behind the device: batch k + 1's
     device program (forward, decode, NMS) is enqueued BEFORE the host waits for batch k's detection counts, so the GPU
     never idles on the per-batch hand-over (what the reference's `single_gpu_test` loop -- apis/test.py -- pays per batch
@@ -950,7 +983,12 @@ def _detect_stream(self, batches, test_cfg, rescale=False):
     sizes, scale factors) go through pinned memory and the counts come back behind an event on the stream that produced
     them: nothing in the loop synchronises the main stream.  Decode + NMS of batch k (a dozen launches of a few workgroups each, ~0.3 ms at
     batch 8) run on a stream of their own NEXT TO the forward pass of batch k + 1: the head outputs alternate between two
-    sets of buffers, and the forward pass that reuses a set first waits for the post-processing that read it."""
+    sets of buffers, and the forward pass that reuses a set first waits for the post-processing that read it.
+    crops (an ops.crops.CropSpec): every batch is (img, img_metas, (descriptor table, frames)) and its RoI crops are cut behind
+    its NMS on the same stream; yields (that list, Crops of the batch, ends) as `detect` returns them -- the plan's counters
+    come with the counts in the pinned copy, so handing the crops out per frame reads nothing more from the device.  The
+    batch's record holds the table (a view of the upload buffer) and the frames until the host has waited for the batch: the
+    launches that read them run a batch behind."""
     # (no stream of its own: a process should not create more than four HIP streams on this device -- engine.py, "stream
     # budget" -- and the training step's tower-chain stream is idle here: the inference pass runs its reg chain on `side`)
     post = self.engine._chain_stream()
@@ -959,8 +997,8 @@ def _detect_stream(self, batches, test_cfg, rescale=False):
     alts = {}                    # id(plan) -> (plan, the other set of head-output buffers)
     post_ev = [None, None]       # events "decode / NMS done" of the batch before last and of the last batch
 
-    def fetch_counts(outs, pinned):     # on the current stream: the detection counts into pinned memory + "arrived" event
-        pinned.copy_(outs[3], non_blocking=True)
+    def fetch_counts(counts, pinned):   # on the current stream: the detection counts into pinned memory + "arrived" event
+        pinned.copy_(counts, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
         return done
@@ -970,8 +1008,19 @@ def _detect_stream(self, batches, test_cfg, rescale=False):
         done.synchronize()                                      # the host waits for THIS batch only
         counts = pinned.numpy()
         ob, osc, ol, _ = outs
-        return [(torch.cat([ob[i, :int(counts[i])], osc[i, :int(counts[i]), None]], -1), ol[i, :int(counts[i])])
+        dets = [(torch.cat([ob[i, :int(counts[i])], osc[i, :int(counts[i]), None]], -1), ol[i, :int(counts[i])])
                 for i in range(ob.shape[0])]
+        if crops is None:
+            return dets
+        return (dets,) + _crops_collect(rec[4], counts, ob.shape[0])   # (rec[5]: the frames and their table, alive until here)
+
+    def post_launch(hw, sf, src):       # decode + NMS, and the batch's crops behind them: -> (outs, what fetch_counts copies, job)
+        if crops is None:
+            outs = _post_launch(self, hw, sf, test_cfg)
+            return outs, outs[3], None
+        counts = _crop_counts(self, hw.shape[0])
+        outs = _post_launch(self, hw, sf, test_cfg, counts_out=counts)
+        return outs, counts, _crops_launch(self, outs, counts, (crops, src[0]))
 
     def upload(a):
         return torch.from_numpy(a).pin_memory().to(self.dev, non_blocking=True)
@@ -981,7 +1030,9 @@ def _detect_stream(self, batches, test_cfg, rescale=False):
     def run():
         prev = None
         with torch.no_grad():
-            for img, img_metas in batches:
+            for batch in batches:
+                img, img_metas = batch[:2]
+                src = batch[2] if crops is not None else None
                 hw = upload(np.asarray([[float(m["img_shape"][0]), float(m["img_shape"][1])] for m in img_metas], np.float32))
                 sf = upload(np.stack([np.asarray(m["scale_factor"], np.float32).reshape(4) for m in img_metas])) if rescale else None
                 img = img.to(self.dev, non_blocking=True)
@@ -1002,22 +1053,25 @@ def _detect_stream(self, batches, test_cfg, rescale=False):
                     fwd.record()
                     with torch.cuda.stream(post):
                         post.wait_event(fwd)
-                        outs = _post_launch(self, hw, sf, test_cfg)
+                        outs, counts, job = post_launch(hw, sf, src)
                         ev = torch.cuda.Event()
                         ev.record()
-                        pinned = torch.empty(outs[3].shape, dtype=outs[3].dtype).pin_memory()
-                        done = fetch_counts(outs, pinned)
+                        pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
+                        done = fetch_counts(counts, pinned)
+                    if job is not None:                             # (the crops and their rows are read on the caller's
+                        for t in job:                               # stream next: their memory returns to this one's pool)
+                            t.record_stream(torch.cuda.current_stream())
                     post_ev[0], post_ev[1] = post_ev[1], ev
                 else:
                     self.forward(img)
-                    outs = _post_launch(self, hw, sf, test_cfg)
+                    outs, counts, job = post_launch(hw, sf, src)
                     ev = torch.cuda.Event()
                     ev.record()
-                    pinned = torch.empty(outs[3].shape, dtype=outs[3].dtype).pin_memory()
+                    pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
                     with torch.cuda.stream(post):                   # (the copy must not queue behind the next batch's forward pass)
                         post.wait_event(ev)
-                        done = fetch_counts(outs, pinned)
-                rec = (outs, done, pinned, (hw, sf))
+                        done = fetch_counts(counts, pinned)
+                rec = (outs, done, pinned, (hw, sf), job, src)
                 if prev is not None:
                     yield collect(prev)
                 prev = rec
@@ -1049,10 +1103,11 @@ def _meta_tensors(self, img_metas, rescale):
     return hw, sf
 
 
-def _post_launch(self, hw, sf, test_cfg, head_out=None):
+def _post_launch(self, hw, sf, test_cfg, head_out=None, counts_out=None):
     """Device part of the post-processing (no host synchronisation, no host->device copies: capturable in a hipGraph):
     decode + NMS launches on the engine's head outputs (or on `head_out` = dict(cls, reg, iou, scales, ldesc, nlvl, B,
-    level_hw) row buffers handed in through the module API).  Returns the output tensors (boxes, scores, labels, counts)."""
+    level_hw) row buffers handed in through the module API).  Returns the output tensors (boxes, scores, labels, counts);
+    counts_out: a zeroed i32 tensor whose first B entries become `counts` (a caller that copies more words with them)."""
     e = self.engine
     if head_out is None:
         head_out = dict(cls=e.buf["cls"], reg=e.buf["reg_u"], iou=e.buf["iou"], scales=e.scales_tensor(), ldesc=e.ldesc,
@@ -1100,7 +1155,7 @@ def _post_launch(self, hw, sf, test_cfg, head_out=None):
     ob = torch.zeros(B, k, 4, device=self.dev)
     osc = torch.zeros(B, k, device=self.dev)
     ol = torch.zeros(B, k, dtype=torch.long, device=self.dev)
-    oc = torch.zeros(B, dtype=torch.int32, device=self.dev)
+    oc = torch.zeros(B, dtype=torch.int32, device=self.dev) if counts_out is None else counts_out[:B]
     if typ in ("vote", "global_vote"):
         ctype, vtype = ncfg.get("cluster_score", "cls"), ncfg.get("vote_score", "iou")
         prod = None
@@ -1132,8 +1187,9 @@ def _post_launch(self, hw, sf, test_cfg, head_out=None):
     return ob, osc, ol, oc
 
 
-def _post_collect(self, ob, osc, ol, oc):
-    counts = oc.cpu().numpy()
+def _post_collect(self, ob, osc, ol, oc, counts=None):
+    """counts: the first B words are oc's, already on the host"""
+    counts = oc.cpu().numpy() if counts is None else counts
     out = []
     for i in range(ob.shape[0]):
         kk = int(counts[i])
@@ -1141,11 +1197,15 @@ def _post_collect(self, ob, osc, ol, oc):
     return out
 
 
-def _detect_graph(self, img, img_metas, test_cfg, rescale=False):
+def _detect_graph(self, img, img_metas, test_cfg, rescale=False, crops=None):
     """`detect` with the whole device program (weight folding, ~110 conv / GroupNorm launches on two streams, decode,
     the NMS pipeline) captured once per (batch, image size, test_cfg) in a hipGraph and replayed: single-image
     serving is otherwise bound by the host's launch rate (3.2 ms of Python + ctypes enqueue for ~1.7 ms of GPU work
-    at batch 1).  Inputs are copied into the graph's static buffers; results are read back like `detect`."""
+    at batch 1).  Inputs are copied into the graph's static buffers; results are read back like `detect`.  crops= is refused:
+    the frames' addresses change from call to call and a captured launch holds the ones it was captured with."""
+    if crops is not None:
+        raise NotImplementedError("detect_graph(crops=...): RoI crops are not captured in the graph (the frames' addresses are "
+                                  "per call); use detect / detect_stream, or ops.crop_detections on the graph's detections")
     with torch.no_grad():
         img = img.to(self.dev)
         key = (tuple(img.shape), bool(rescale), repr(sorted(dict(test_cfg).items(), key=str)))
