@@ -706,12 +706,48 @@ int radet_cutout_f32(float* out, int nbatch, int Hp, int Wp, const int* desc, in
  *      desc (device) = nimg rows of PREP_DESC_INTS ints:
  *      {source byte address lo, hi, source row stride in bytes (unsigned), source h, w, destination (resized) h, w, flags};
  *      a pixel is 3 consecutive bytes, pixels of a row are contiguous; any address alignment (byte loads), so a frame may
- *      be a view into a larger device tensor.  flags: PREP_TO_RGB.  Pixels beyond the destination h x w are zero; a row
- *      with source h or w <= 0 is all zeros.  nimg <= 65535, Hp * Wp < 2^31. */
+ *      be a view into a larger device tensor.  flags: PREP_TO_RGB | PREP_FLIP_H | PREP_FLIP_V.  Pixels beyond the
+ *      destination h x w are zero; a row with source h or w <= 0 is all zeros.  nimg <= 65535, Hp * Wp < 2^31.
+ *      PREP_FLIP_H / PREP_FLIP_V (both: diagonal) are the views of test-time augmentation, mmcv.imflip of the RESIZED image
+ *      in front of Normalize and Pad: inside the destination h x w, pixel (y, x) of a flipped row is what the unflipped row
+ *      writes at (y, w - 1 - x), at (h - 1 - y, x), or at both mirrored; the padding stays on the right and at the bottom.
+ *      A row without these flags writes the bits it wrote before they existed. */
 #define PREP_DESC_INTS 8
 #define PREP_TO_RGB 1
+#define PREP_FLIP_H 2
+#define PREP_FLIP_V 4
 int radet_preprocess_frames(const int* desc, int nimg, int Hp, int Wp, float m0, float m1, float m2, float s0, float s1,
                             float s2, float* out, void* stream);
+
+/* ---- test-time augmentation: the views' candidates back in the frame, packed per image (csrc/tta.hip), one launch.
+ *      Input: the candidate lists of V * B (view, image) rows, row r = v * B + b, as radet_decode_candidates writes them in
+ *      VIEW coordinates (scale_factor = NULL) into ONE pool: pool_boxes f32 [pool, 4] (16-byte aligned), pool_scores /
+ *      pool_ctr f32 [pool], pool_labels i64 [pool], counts i32 [V * B].  Views of different scales may have different
+ *      capacities: nothing but its descriptor row says where a row's list lies, so every decode launch (one per group of
+ *      views that ran as one forward batch) writes its own [rows, cap] block of the pool.
+ *      desc = V * B rows of MERGE_DESC_INTS 32-bit words:
+ *        {h, w (the view's img_shape, f32 bits), sx, sy, sx, sy (its scale_factor, f32 bits), flip code (0 none, 1
+ *         horizontal, 2 vertical, 3 diagonal), start (the pool index of the row's first candidate), cap (the row's capacity)};
+ *      it is passed twice: desc_host (host memory, read during the call only, never by the device) is what the argument
+ *      checks read, desc (device) the same words for the kernel -- uploading them is the caller's.
+ *      Output, per image b: out_* [B, cap_out] hold view 0's counts[0 * B + b] candidates, then view 1's, ...; inside a
+ *      view the order is kept and nothing is dropped (the reference's torch.cat order of aug_test_bboxes; every NMS here
+ *      breaks ties by input index); out_count[b] = the sum of the counts (a count above its row's cap counts as cap).
+ *      Slots at and beyond out_count[b] are not written.  Scores, centerness and labels are copied; boxes are
+ *      bbox_mapping_back (radet/core/bbox/transforms.py:46-55), fp32, every operation rounded once, a true IEEE division:
+ *        horizontal: x1' = w - x2, x2' = w - x1;  vertical: y1' = h - y2, y2' = h - y1;  diagonal: both;
+ *        then x1' / sx, y1' / sy, x2' / sx(word 4), y2' / sy(word 5).
+ *      grid (ceil(cap_out / 256), B), one output slot per thread, 16-byte loads and stores for the boxes.  No host
+ *      synchronisation, no allocation, capturable.  RADET_ERR_ARG before any launch: V outside 1..TTA_MAX_VIEWS, B < 0 or
+ *      > 65535, cap_out outside 1..65536, a NULL pointer with B > 0, and from desc_host: a flip code outside 0..3, a cap < 0,
+ *      a row whose [start, start + cap) leaves [0, pool), an image whose caps do not add up to at most cap_out.  B == 0:
+ *      RADET_OK, no launch. */
+#define TTA_MAX_VIEWS 16
+#define MERGE_DESC_INTS 9
+int radet_merge_views(const int* desc_host, const int* desc, int V, int B, size_t pool, const float* pool_boxes,
+                      const float* pool_scores, const float* pool_ctr, const int64_t* pool_labels, const int* counts,
+                      int cap_out, float* out_boxes, float* out_scores, float* out_ctr, int64_t* out_labels, int* out_count,
+                      void* stream);
 
 /* ---- detections -> a packed batch of RoI crops (csrc/crops.hip), two launches, nothing read back to the host.
  * radet_crop_plan (one workgroup): boxes f32 [B,K,4] (16-byte aligned), scores f32 [B,K], counts i32 [B] -- the NMS outputs

@@ -50,22 +50,67 @@ def _is_frame(x):
 _FILE_LOADER_ARGS = ("decode", "index_cache", "seg_mcus")        # LoadImageFromFile's own; LoadImageFromWebcam has no file
 
 
-def _frame_pipeline(model):
+_TTA_KEYS = ("img_scale", "flip", "flip_direction")
+
+
+def _tta_stages(stages, tta):
+    """the test pipeline with the three view arguments of its MultiScaleFlipAug stage replaced by tta's; its transforms stay"""
+    if not isinstance(tta, dict) or not tta or set(tta) - set(_TTA_KEYS):
+        raise ValueError(f"tta={tta!r}: expected dict([{', '.join(_TTA_KEYS)}])")
+    at = [i for i, t in enumerate(stages) if dict(t).get("type") == "MultiScaleFlipAug"]
+    if len(at) != 1:
+        raise ValueError("tta=: the test pipeline has no single MultiScaleFlipAug stage to override")
+    stages = list(stages)
+    stages[at[0]] = {**dict(stages[at[0]]), **tta}
+    return stages
+
+
+def set_tta(model, tta=None):
+    """Test-time augmentation for this model's inference on loaded frames (inference_detector, detect_frames), set on the model
+    beside its cfg: tta=dict(img_scale=[...], flip=True, flip_direction='horizontal' | 'vertical' | 'diagonal' | a list)
+    overrides those three arguments of the MultiScaleFlipAug stage of model.cfg.data.test.pipeline; its transforms stay.
+    None clears the override (the config's own stage, which may itself make several views, holds again).  The two entry
+    points keep the reference's signatures, so the override is a property of the model, not an argument of theirs.
+    With an override set, file names and normalised tensors are refused by inference_detector.  Returns the model."""
+    if tta is not None:
+        tta = dict(tta)
+        if not tta or set(tta) - set(_TTA_KEYS):
+            raise ValueError(f"tta={tta!r}: expected dict([{', '.join(_TTA_KEYS)}])")
+    object.__setattr__(model, "tta", tta)
+    return model
+
+
+def _frame_pipeline(model, tta=None):
     """model.cfg.data.test.pipeline with its first stage replaced by LoadImageFromWebcam (radet/apis/inference.py:97-102), built
-    once per model and test pipeline"""
+    once per model, test pipeline and tta= override (the few last ones are kept)"""
     from ..datasets.loading import ImagePipeline
     cfg = getattr(model, "cfg", None)
     if cfg is None:
         raise ValueError("inference on frames needs model.cfg (init_detector sets it)")
     stages = list(cfg.data.test.pipeline)
-    key = repr(stages)
-    cached = getattr(model, "_frame_pipeline", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
+    key = (repr(stages), None if tta is None else repr(sorted(dict(tta).items())))
+    # model._frame_pipeline: (key, pipeline) of the config's own pipeline; model._tta_pipelines: the last few tta= overrides
+    if tta is None:
+        cached = getattr(model, "_frame_pipeline", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+    else:
+        cache = getattr(model, "_tta_pipelines", None)
+        if cache is None:
+            cache = {}
+            object.__setattr__(model, "_tta_pipelines", cache)
+        if key in cache:
+            return cache[key]
+        stages = _tta_stages(stages, tta)
     first = {k: v for k, v in dict(stages[0]).items() if k not in _FILE_LOADER_ARGS}
     first["type"] = "LoadImageFromWebcam"
     pipeline = ImagePipeline([first] + stages[1:])
-    object.__setattr__(model, "_frame_pipeline", (key, pipeline))
+    if tta is None:
+        object.__setattr__(model, "_frame_pipeline", (key, pipeline))
+    else:
+        while len(cache) >= 4:
+            cache.pop(next(iter(cache)))
+        cache[key] = pipeline
     return pipeline
 
 
@@ -106,19 +151,24 @@ def _single_view(data):
 
 
 def _inference_frames(model, frames, crops=None):
+    tta = getattr(model, "tta", None)
     if crops is None:
         if not frames:
             return []
         with torch.no_grad():
-            return model(return_loss=False, rescale=True, **_prepare_frames(_frame_pipeline(model), frames))
+            return model(return_loss=False, rescale=True, **_prepare_frames(_frame_pipeline(model, tta), frames))
     from ..ops.crops import check_frames
     check_frames(frames)
     spec = _crop_request(model, crops)
-    data, source = _prepare_frames(_frame_pipeline(model), frames, True)
-    imgs, metas = _single_view(data)
+    pipeline = _frame_pipeline(model, tta)
+    data, source = _prepare_frames(pipeline, frames, True)
     if model.training:
         model.eval()
-    dets, out, _ = model.runtime().detect(imgs, metas, model.test_cfg, True, crops=(spec, source[0]))
+    if pipeline.views > 1:                                   # (the table's first B rows describe the source frames)
+        dets, out, _ = model.runtime().detect_aug(data["img"], data["img_metas"], model.test_cfg, True, crops=(spec, source[0]))
+    else:
+        imgs, metas = _single_view(data)
+        dets, out, _ = model.runtime().detect(imgs, metas, model.test_cfg, True, crops=(spec, source[0]))
     del source                                               # (detect has waited for the batch: the frames' table can go)
     return [bbox2result(b, l, model.bbox_head.num_classes) for b, l in dets], out
 
@@ -130,11 +180,14 @@ def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
     frame's own coordinates), or with on_device=True the (dets f32[k, 5], labels i64[k]) device tensors.  Leaving the loop
     early closes the stream underneath, which leaves the runtime ready for the next call.
     crops=dict(size=..., ...) as for inference_detector: yields (result, Crops of that frame) -- the crops of a batch are cut
-    from its frames on the device behind its NMS; a frame's record holds views of the batch's tensors and the batch's n_total."""
+    from its frames on the device behind its NMS; a frame's record holds views of the batch's tensors and the batch's n_total.
+    Test-time augmentation -- set_tta(model, dict(img_scale=[...], flip=True, flip_direction=...)), or a config whose
+    MultiScaleFlipAug makes several views: every batch runs DetectorRuntime.detect_aug's program -- the forward batch is F * batch_size per
+    scale (F: that scale's unflipped + flipped views) -- still one batch behind the device, on the caller's stream."""
     from ..ops.crops import check_frames, split_crops
     if batch_size < 1:
         raise ValueError(f"batch_size={batch_size}")
-    pipeline = _frame_pipeline(model)
+    pipeline = _frame_pipeline(model, getattr(model, "tta", None))
     spec = None if crops is None else _crop_request(model, crops)
     if model.training:
         model.eval()
@@ -152,6 +205,12 @@ def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
 
     def prepared():
         for group in batches():
+            if pipeline.views > 1:
+                if spec is not None:
+                    check_frames(group)
+                data, source = _prepare_frames(pipeline, group, True)
+                yield data["img"], data["img_metas"], source
+                continue
             if spec is None:
                 yield _single_view(_prepare_frames(pipeline, group))
                 continue
@@ -159,7 +218,10 @@ def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
             data, source = _prepare_frames(pipeline, group, True)
             yield _single_view(data) + (source,)             # (the stream carries the table and the frames with the batch)
 
-    stream = model.runtime().detect_stream(prepared(), model.test_cfg, rescale=True, **({} if spec is None else dict(crops=spec)))
+    if pipeline.views > 1:
+        stream = model.runtime().detect_aug_stream(prepared(), model.test_cfg, crops=spec)
+    else:
+        stream = model.runtime().detect_stream(prepared(), model.test_cfg, rescale=True, **({} if spec is None else dict(crops=spec)))
     try:
         for dets in stream:
             per_frame = None
@@ -185,7 +247,21 @@ def inference_detector(model, imgs, scale_factor=None, crops=None):
     Memory: the crops' tensor is allocated before the number of detections is known, max_crops slots of 3 * Ho * Wo values
     (f32: 12 * Ho * Wo bytes each), and the returned views keep all of it alive.  The default max_crops is every detection
     slot of the batch, B * max_per_img -- 629 MB for 8 frames x 100 slots of 256 x 256 f32, twice that in flight in
-    detect_frames -- so pass the max_crops the pose stage can take."""
+    detect_frames -- so pass the max_crops the pose stage can take.
+    Test-time augmentation, with loaded frames only: a MultiScaleFlipAug with several views (flip=True, several img_scale) in
+    cfg.data.test.pipeline is honoured as in the reference, and set_tta(model, dict(img_scale=[...], flip=True,
+    flip_direction='horizontal' | 'vertical' | 'diagonal' | a list)) overrides those three arguments of the config's stage
+    (its transforms stay) for this model's calls.  The frames go through DetectorRuntime.detect_aug: the forward batch is F * batch_size per scale (F = that
+    scale's unflipped + flipped views), the views' candidates are mapped back and merged on the GPU and the config's NMS
+    runs once.  How the views compose is this project's rule (detect_aug); with an override set, file names are refused."""
+    tta = getattr(model, "tta", None)
+    if tta is not None:
+        names = isinstance(imgs, str) or (isinstance(imgs, (list, tuple)) and any(isinstance(i, str) for i in imgs))
+        if names:
+            raise NotImplementedError("inference_detector on file names with set_tta(model, ...): test-time augmentation is built for frames in "
+                                      "memory; load the images (mmcv.imread order: HxWx3 uint8 BGR) and pass them")
+        if not (_is_frame(imgs) or (isinstance(imgs, (list, tuple)) and all(_is_frame(i) for i in imgs))):
+            raise ValueError("inference_detector with set_tta(model, ...) takes loaded frames (ndarray or uint8 tensor HxWx3 BGR)")
     if crops is not None:
         if _is_frame(imgs):
             res, out = _inference_frames(model, [imgs], crops)

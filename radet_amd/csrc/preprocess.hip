@@ -7,7 +7,9 @@
 // read byte by byte and nothing is assumed about its alignment.  The arithmetic is the file pipeline's, from the same
 // helpers (pixel_ops.h): resize_u8_kernel's taps and fixed-point blend, then aug_finish_kernel's BGR->RGB, (q - mean) *
 // stdinv and zeros outside the frame's h x w -- bit-equal to radet_resize_linear_u8 -> radet_augment_finish, without the
-// packed u8 temporaries and the three pass-through launches between them.
+// packed u8 temporaries and the three pass-through launches between them.  A row may ask for the flipped image
+// (PREP_FLIP_H / PREP_FLIP_V, test-time augmentation): the mirror is taken inside the destination h x w, the padding stays
+// on the right and at the bottom.
 //
 // grid (ceil(Hp * Wp / 256), nimg): one output pixel (3 planes) per thread, as aug_finish_kernel; stores along x are
 // coalesced per plane.  Memory-bound: 12 source bytes (mostly shared with the neighbouring lanes) and 12 stored bytes
@@ -35,7 +37,9 @@ __global__ __launch_bounds__(256) void preprocess_frames_kernel(const int* __res
     }
     const PREP_GLOBAL uint8_t* src = (const PREP_GLOBAL uint8_t*)(((uint64_t)(uint32_t)d[1] << 32) | (uint64_t)(uint32_t)d[0]);
     const size_t stride = (size_t)(uint32_t)d[2];
-    const LinTaps t = lin_taps_u8(y, x, sh, sw, dh, dw);
+    // a flipped row (mmcv.imflip of the resized image): pixel (y, x) is the unflipped row's pixel at the mirrored place
+    const int fy = (d[7] & PREP_FLIP_V) ? dh - 1 - y : y, fx = (d[7] & PREP_FLIP_H) ? dw - 1 - x : x;
+    const LinTaps t = lin_taps_u8(fy, fx, sh, sw, dh, dw);
     const PREP_GLOBAL uint8_t* r0 = src + (size_t)t.y0 * stride;
     const PREP_GLOBAL uint8_t* r1 = src + (size_t)t.y1 * stride;
     const size_t c0 = (size_t)t.sx * 3, c1 = (size_t)t.x1 * 3;

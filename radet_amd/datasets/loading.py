@@ -1121,20 +1121,51 @@ class Collect:
 
 @PIPELINES.register_module()
 class MultiScaleFlipAug:
-    """one view only: a single img_scale with flip=False (test-time augmentation with several views is refused, like
-    forward_test)"""
+    """The views of test-time augmentation in the reference's order (radet/datasets/pipelines/test_time_aug.py:94-106):
+    scales outermost; per scale the unflipped view, then one view per flip_direction.  Every view is planned as the single
+    view at its scale is, with flip / flip_direction set, so img_shape, pad_shape and scale_factor are Resize's and Pad's.
+    One view (a single img_scale, flip=False) is the plain test pipeline.  Several views are built for pipelines on frames
+    in memory only (ImagePipeline refuses them behind LoadImageFromFile).  scale_factor= is refused (Resize has no such
+    input here); flip=True without a RandomFlip among the transforms is an error -- the reference warns and then maps the
+    boxes back with a flip that never happened."""
 
     def __init__(self, transforms, img_scale=None, scale_factor=None, flip=False, flip_direction="horizontal"):
+        if scale_factor is not None or img_scale is None:
+            _refuse("MultiScaleFlipAug(scale_factor=...) / without img_scale")
         scales = img_scale if isinstance(img_scale, list) else [img_scale]
-        if flip or scale_factor is not None or img_scale is None or len(scales) != 1:
-            _refuse("MultiScaleFlipAug with more than one view (flip=True / several scales / scale_factor)")
-        self.img_scale = tuple(scales[0])
+        if not scales or not all(isinstance(v, (tuple, list)) and len(v) == 2 for v in scales):
+            raise TypeError(f"MultiScaleFlipAug: img_scale is a tuple or a list of tuples, got {img_scale!r}")
+        directions = list(flip_direction) if isinstance(flip_direction, (list, tuple)) else [flip_direction]
+        for d in directions:
+            if d not in K.PREP_FLIP:
+                raise ValueError(f"MultiScaleFlipAug: flip_direction {d!r} (one of {sorted(K.PREP_FLIP)}, or a list of them)")
         self.transforms = [build_from_cfg(t, PIPELINES) if isinstance(t, dict) else t for t in transforms]
+        if flip and not any(isinstance(t, RandomFlip) for t in self.transforms):
+            raise ValueError("MultiScaleFlipAug(flip=True) without a RandomFlip among its transforms: the views would not be "
+                             "flipped, and their boxes would be mapped back as if they were")
+        self.flip, self.flip_direction = bool(flip), directions
+        flips = [(False, None)] + ([(True, d) for d in directions] if flip else [])
+        self.views = [(tuple(sc), f, d) for sc in scales for f, d in flips]
+        if len(self.views) > K.TTA_MAX_VIEWS:
+            raise ValueError(f"MultiScaleFlipAug: {len(self.views)} views ({len(scales)} scales x {len(flips)} flips), at most "
+                             f"{K.TTA_MAX_VIEWS}")
+        self.img_scale = self.views[0][0]
 
-    def plan(self, s, rnd, nprnd):
-        s.update(scale=self.img_scale, flip=False, flip_direction=None, _tta=True)
+    def _plan_view(self, s, view, rnd, nprnd):
+        s.update(scale=view[0], flip=view[1], flip_direction=view[2], _tta=True)
         for t in self.transforms:
             t.plan(s, rnd, nprnd)
+
+    def plan(self, s, rnd, nprnd):
+        if len(self.views) == 1:
+            return self._plan_view(s, self.views[0], rnd, nprnd)
+        views = []
+        for view in self.views:                                 # (every view from the state in front of this stage)
+            v = dict(s)
+            self._plan_view(v, view, rnd, nprnd)
+            views.append(v)
+        s.update(views[0])                                      # the sample itself is its first view; the others ride along
+        s["_views"] = views
 
 
 # ---------------------------------------------------------------------------------------------------- the batched device part
@@ -1147,14 +1178,17 @@ _FRAME_STAGES = ("LoadImageFromWebcam", "MultiScaleFlipAug", "Resize", "RandomFl
                  "ImageToTensor", "Collect")
 
 
-def frame_desc_rows(frames, dst_hw, to_rgb, host_base):
+def frame_desc_rows(frames, dst_hw, to_rgb, host_base, views=1, flips=None):
     """The descriptor rows of radet_preprocess_frames (include/radet_hip.h, PREP_DESC_INTS) for a batch of frames HxWx3 u8:
     an ndarray goes into the batch's upload buffer, packed, at the byte offset returned for it (its address: host_base +
     offset, the device address of that buffer's pixel part); a torch tensor is read where it is (data_ptr, row stride).
-    Host arithmetic only.  Returns (int32 [B, PREP_DESC_INTS], byte offset per frame or None, bytes of the upload)."""
-    rows = np.zeros((len(frames), K.PREP_DESC_INTS), np.int32)
+    views > 1 (test-time augmentation): views * B rows, view-major (row v * B + b), dst_hw and flips (PREP_FLIP_* bits) per
+    row; the rows of a frame's views name the same address, and the frame is in the upload once.
+    Host arithmetic only.  Returns (int32 [views * B, PREP_DESC_INTS], byte offset per frame or None, bytes of the upload)."""
+    B = len(frames)
+    rows = np.zeros((views * B, K.PREP_DESC_INTS), np.int32)
     offs, o = [], 0
-    for row, f, (dh, dw) in zip(rows, frames, dst_hw):
+    for b, f in enumerate(frames):
         h, w = int(f.shape[0]), int(f.shape[1])
         if isinstance(f, np.ndarray):
             addr, stride = host_base + o, 3 * w
@@ -1165,19 +1199,21 @@ def frame_desc_rows(frames, dst_hw, to_rgb, host_base):
             offs.append(None)
         if not 0 <= stride < 2 ** 31:
             raise ValueError(f"frame of shape {tuple(f.shape)}: a row stride of {stride} bytes does not fit the descriptor")
-        row[0:2] = np.array([addr & 0xFFFFFFFF, addr >> 32], np.uint32).view(np.int32)
-        row[2:8] = [stride, h, w, dh, dw, K.PREP_TO_RGB if to_rgb else 0]
+        for r in range(b, views * B, B):
+            row, (dh, dw) = rows[r], dst_hw[r]
+            row[0:2] = np.array([addr & 0xFFFFFFFF, addr >> 32], np.uint32).view(np.int32)
+            row[2:8] = [stride, h, w, dh, dw, (K.PREP_TO_RGB if to_rgb else 0) | (flips[r] if flips is not None else 0)]
     return rows, offs, o
 
 
-def upload_frames(frames, dst_hw, to_rgb, dev):
+def upload_frames(frames, dst_hw, to_rgb, dev, views=1, flips=None):
     """[descriptor table | host frames, packed] into one device buffer in ONE pinned, non-blocking copy (the table needs the
     buffer's address, so the buffer is allocated first); frames that are device tensors are not copied, the table holds their
-    addresses.  Returns the table, i32 [B, PREP_DESC_INTS]: a view of the buffer, which it keeps alive."""
-    head = len(frames) * K.PREP_DESC_INTS * 4
-    _, _, nbytes = frame_desc_rows(frames, dst_hw, to_rgb, 0)
+    addresses.  Returns the table, i32 [views * B, PREP_DESC_INTS]: a view of the buffer, which it keeps alive."""
+    head = views * len(frames) * K.PREP_DESC_INTS * 4
+    _, _, nbytes = frame_desc_rows(frames, dst_hw, to_rgb, 0, views, flips)
     up = torch.empty(head + nbytes, dtype=torch.uint8, device=dev)
-    rows, offs, _ = frame_desc_rows(frames, dst_hw, to_rgb, up.data_ptr() + head)
+    rows, offs, _ = frame_desc_rows(frames, dst_hw, to_rgb, up.data_ptr() + head, views, flips)
     stage = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=True)
     host = stage.numpy()
     host[:head] = rows.reshape(-1).view(np.uint8)
@@ -1291,6 +1327,13 @@ class ImagePipeline:
             _refuse("a CutOut behind the photometric stages together with GenerateDistanceMap(with_gt_mask=False) (the mask-free "
                     "crops are cut from the u8 image in front of the blends: they would not see the holes)")
         self.tta = any(isinstance(t, MultiScaleFlipAug) for t in self.transforms)
+        # test-time augmentation: the number of views per sample (1: the plain test pipeline)
+        self.views = max([len(t.views) for t in self.transforms if isinstance(t, MultiScaleFlipAug)] or [1])
+        if self.views > 1 and not self.frames:
+            raise NotImplementedError(
+                f"MultiScaleFlipAug with {self.views} views (flip=True / several scales) behind LoadImageFromFile: test-time "
+                "augmentation is built for frames in memory (LoadImageFromWebcam first; inference_detector / detect_frames on "
+                "loaded images); file datasets, single_gpu_test and tools/test.py with several views are not implemented")
 
     @staticmethod
     def _check_affine(flat, names, block):
@@ -1739,31 +1782,60 @@ class ImagePipeline:
         in ONE pinned, non-blocking copy -- frames that are device tensors are not copied at all, the table holds their
         addresses -- and ONE radet_preprocess_frames launch writes the batch; no packed temporaries.  Device frames must be
         ready on the current stream; nothing here waits for the device.  Returns (what run() returns, (descriptor table,
-        frames)) -- see run_frames."""
+        frames)) -- see run_frames.
+        Several views (MultiScaleFlipAug with flips / scales): still ONE upload -- the table of all V * B rows, view-major,
+        and every host frame once: the rows of a frame's views name the same address -- and one launch per distinct scale,
+        which writes that scale's unflipped and flipped views together, [F * B, 3, Hp, Wp] with the views as slices.
+        Collated: dict(img=[V tensors], img_metas=[V lists]), as the reference collates a test-time-augmentation batch.
+        The table's first B rows describe the source frames (view 0's rows)."""
         dev = self._dev()
         B = len(planned)
         frames = [s["img"] for s in planned]
         for f in frames:
             if isinstance(f, torch.Tensor) and f.device != dev:
                 raise ValueError(f"a frame on {f.device} in a batch prepared on {dev}")
-        hw = [tuple(int(v) for v in s.get("resize_hw", s["img"].shape[:2])) for s in planned]
+        V = self.views
+        views = [[s["_views"][v] for s in planned] for v in range(V)] if V > 1 else [planned]
+        every = [s for view in views for s in view]               # view-major: row v * B + b
+        hw = [tuple(int(v) for v in s.get("resize_hw", s["img"].shape[:2])) for s in every]
         cfg0 = planned[0]["img_norm_cfg"]
-        for s in planned[1:]:
+        for s in every[1:]:
             c = s["img_norm_cfg"]
             if not (np.array_equal(c["mean"], cfg0["mean"]) and np.array_equal(c["std"], cfg0["std"]) and c["to_rgb"] == cfg0["to_rgb"]):
                 raise ValueError("one batch, one Normalize")
-        if any(s.get("flip") for s in planned):
-            raise ValueError("a pipeline that starts with LoadImageFromWebcam does not flip")
-        Hp = max(s["pad_shape"][0] for s in planned)
-        Wp = max(s["pad_shape"][1] for s in planned)
-        if any(s["pad_shape"][0] < h or s["pad_shape"][1] < w for s, (h, w) in zip(planned, hw)):
+        if V == 1 and any(s.get("flip") for s in planned):
+            raise ValueError("a single-view pipeline that starts with LoadImageFromWebcam does not flip")
+        if any(s["pad_shape"][0] < h or s["pad_shape"][1] < w for s, (h, w) in zip(every, hw)):
             raise ValueError("pad_shape smaller than the image")
-        table = upload_frames(frames, hw, cfg0["to_rgb"], dev)
-        out = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=dev)
+        flips = [K.PREP_FLIP[s["flip_direction"]] if s.get("flip") else 0 for s in every]
+        table = upload_frames(frames, hw, cfg0["to_rgb"], dev, views=V, flips=flips)
         mean = cfg0["mean"].astype(np.float64).astype(np.float32)
         stdinv = (1.0 / cfg0["std"].astype(np.float64)).astype(np.float32)
-        K.preprocess_frames(table, B, Hp, Wp, mean, stdinv, out)
-        return self._collect(planned, out, None, None, collate), (table, frames)
+        if V == 1:
+            Hp = max(s["pad_shape"][0] for s in planned)
+            Wp = max(s["pad_shape"][1] for s in planned)
+            out = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=dev)
+            K.preprocess_frames(table, B, Hp, Wp, mean, stdinv, out)
+            return self._collect(planned, out, None, None, collate), (table, frames)
+        # one launch per scale: the views of a scale are consecutive (MultiScaleFlipAug's order), hence consecutive rows
+        outs, v0 = [], 0
+        while v0 < V:
+            v1 = v0 + 1
+            while v1 < V and planned[0]["_views"][v1]["scale"] == planned[0]["_views"][v0]["scale"]:
+                v1 += 1
+            group = [s for view in views[v0:v1] for s in view]
+            Hp = max(s["pad_shape"][0] for s in group)
+            Wp = max(s["pad_shape"][1] for s in group)
+            out = torch.empty(len(group), 3, Hp, Wp, dtype=torch.float32, device=dev)
+            K.preprocess_frames(table[v0 * B * K.PREP_DESC_INTS:], len(group), Hp, Wp, mean, stdinv, out)
+            outs += [out[(v - v0) * B:(v - v0 + 1) * B] for v in range(v0, v1)]
+            v0 = v1
+        if not collate:
+            per_view = [self._collect(view, out, None, None, False) for view, out in zip(views, outs)]
+            samples = [{k: [d[b][k][0] for d in per_view] for k in per_view[0][b]} for b in range(B)]
+            return samples, (table, frames)
+        metas = [[{k: s[k] for k in s["_collect"].meta_keys if k in s} for s in view] for view in views]
+        return dict(img=outs, img_metas=metas), (table, frames)
 
     def _distance_maps(self, planned, hw, img, lsum, params, dev):
         """The mask-free sampler's maps of a batch, f32 [G_i, h, w] per sample: every box's padded crop cut from the

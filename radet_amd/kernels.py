@@ -1868,7 +1868,8 @@ def paste_maps(maps, desc, n, H, W, out):
 
 # ---------------------------------------------------------------------- in-memory frames, one launch (csrc/preprocess.hip)
 PREP_DESC_INTS = 8                 # include/radet_hip.h
-PREP_TO_RGB = 1
+PREP_TO_RGB, PREP_FLIP_H, PREP_FLIP_V = 1, 2, 4
+PREP_FLIP = dict(horizontal=PREP_FLIP_H, vertical=PREP_FLIP_V, diagonal=PREP_FLIP_H | PREP_FLIP_V)
 
 
 def preprocess_frames(desc, n, Hp, Wp, mean, stdinv, out):
@@ -1878,6 +1879,42 @@ def preprocess_frames(desc, n, Hp, Wp, mean, stdinv, out):
     assert desc.numel() >= n * PREP_DESC_INTS
     _lib.call("radet_preprocess_frames", _ptr(desc), int(n), int(Hp), int(Wp), *[float(v) for v in mean],
               *[float(v) for v in stdinv], _ptr(out), _stream())
+
+
+# ---------------------------------------------------------------------- test-time augmentation (csrc/tta.hip)
+TTA_MAX_VIEWS = 16                 # include/radet_hip.h
+MERGE_DESC_INTS = 9                # {h, w, sx, sy, sx, sy (f32 bits), flip code, start, cap}
+FLIP_CODES = {None: 0, "horizontal": 1, "vertical": 2, "diagonal": 3}
+
+
+def merge_desc_rows(hw, sf, flips, starts, caps):
+    """the descriptor rows of radet_merge_views for V * B (view, image) rows, row r = v * B + b: hw [R, 2] the views'
+    img_shape, sf [R, 4] their scale factors, flips [R] codes 0..3, starts / caps [R] in candidates.  Host arithmetic only."""
+    import numpy as np
+    R = len(flips)
+    rows = np.zeros((R, MERGE_DESC_INTS), np.int32)
+    rows[:, 0:2] = np.asarray(hw, np.float32).reshape(R, 2).view(np.int32)
+    rows[:, 2:6] = np.asarray(sf, np.float32).reshape(R, 4).view(np.int32)
+    rows[:, 6], rows[:, 7], rows[:, 8] = flips, starts, caps
+    return rows
+
+
+def merge_views(desc_host, desc, V, B, pool_boxes, pool_scores, pool_ctr, pool_labels, counts, cap_out, out_boxes, out_scores,
+                out_ctr, out_labels, out_count):
+    """the candidates of V * B (view, image) rows back in the frame and packed per image (include/radet_hip.h,
+    radet_merge_views).  desc_host: i32 ndarray [V * B, MERGE_DESC_INTS], read during the call (the argument checks); desc:
+    the same words on the device.  The pool is flat: boxes f32 [pool, 4], the others [pool]."""
+    import numpy as np
+    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == np.int32 and desc_host.flags.c_contiguous
+    assert desc_host.size == V * B * MERGE_DESC_INTS and desc.dtype == torch.int32 and desc.numel() >= desc_host.size
+    pool = int(pool_scores.numel())
+    assert pool_boxes.dtype == torch.float32 and pool_boxes.numel() == 4 * pool and pool_ctr.numel() == pool
+    assert pool_labels.dtype == torch.int64 and pool_labels.numel() == pool and counts.dtype == torch.int32 and counts.numel() >= V * B
+    assert out_boxes.numel() >= B * cap_out * 4 and min(out_scores.numel(), out_ctr.numel(), out_labels.numel()) >= B * cap_out
+    assert out_labels.dtype == torch.int64 and out_count.dtype == torch.int32 and out_count.numel() >= B
+    _lib.call("radet_merge_views", desc_host.ctypes.data, _ptr(desc), int(V), int(B), C.c_size_t(pool), _ptr(pool_boxes),
+              _ptr(pool_scores), _ptr(pool_ctr), _ptr(pool_labels), _ptr(counts), int(cap_out), _ptr(out_boxes), _ptr(out_scores),
+              _ptr(out_ctr), _ptr(out_labels), _ptr(out_count), _stream())
 
 
 # ---------------------------------------------------------------------- detections -> RoI crops (csrc/crops.hip)

@@ -136,14 +136,23 @@ class RADet(nn.Module):
             imgs, img_metas = [imgs], [img_metas]
         if len(imgs) != len(img_metas):
             raise ValueError(f"num of augmentations ({len(imgs)}) != num of image meta ({len(img_metas)})")
+        for img, metas in zip(imgs, img_metas):
+            for m in metas:
+                m["batch_input_shape"] = tuple(img.size()[-2:])
         if len(imgs) != 1:
-            raise NotImplementedError("test-time augmentation is out of scope (flip=False in the BOP configs)")
-        for m in img_metas[0]:
-            m["batch_input_shape"] = tuple(imgs[0].size()[-2:])
+            return self.aug_test(imgs, img_metas, **kwargs)
         return self.simple_test(imgs[0], img_metas[0], **kwargs)
 
     def simple_test(self, img, img_metas, rescale=False):
         dets = self.runtime().detect(img, img_metas, self.test_cfg, rescale)
+        return [bbox2result(b, l, self.bbox_head.num_classes) for b, l in dets]
+
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """test-time augmentation (single_stage.py:112-124): imgs, img_metas are lists over the views MultiScaleFlipAug made
+        of one batch.  DetectorRuntime.detect_aug: a forward pass per group of views of one shape (batch F * B), the views'
+        candidates mapped back and merged on the GPU, ONE NMS.  How the views compose is this project's rule (detect_aug):
+        the reference's aug_test cannot run with RADetHead."""
+        dets = self.runtime().detect_aug(imgs, img_metas, self.test_cfg, rescale)
         return [bbox2result(b, l, self.bbox_head.num_classes) for b, l in dets]
 
     def _parse_losses(self, losses):

@@ -86,6 +86,12 @@ class RADetHead(nn.Module):
         return self._rt().get_bboxes_api(cls_scores, bbox_preds, centernesses, img_metas, cfg or self.test_cfg, rescale,
                                          with_nms)
 
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """The reference's head inherits aug_test(feats, img_metas) from BBoxTestMixin and cannot run it (its with_nms=False
+        candidates are [n, 9]).  Here backbone and head are one device program, so this takes the views' IMAGES (lists over
+        views) and goes to DetectorRuntime.detect_aug: -> [(det_bboxes [k, 5], det_labels [k])] per image."""
+        return self._rt().detect_aug(imgs, img_metas, self.test_cfg, rescale)
+
     def get_anchors(self, featmap_sizes, img_metas, device="cuda"):
         anchors = self.anchor_generator.grid_anchors(featmap_sizes, device)
         flags = [self.anchor_generator.valid_flags(featmap_sizes, m["pad_shape"], device) for m in img_metas]

@@ -1108,30 +1108,48 @@ def _post_launch(self, hw, sf, test_cfg, head_out=None, counts_out=None):
     decode + NMS launches on the engine's head outputs (or on `head_out` = dict(cls, reg, iou, scales, ldesc, nlvl, B,
     level_hw) row buffers handed in through the module API).  Returns the output tensors (boxes, scores, labels, counts);
     counts_out: a zeroed i32 tensor whose first B entries become `counts` (a caller that copies more words with them)."""
+    ho = _head_out(self, head_out)
+    B, nlvl = ho["B"], ho["nlvl"]
+    nms_pre = _nms_pre(self, test_cfg, ho["level_hw"])
+    cap = nlvl * nms_pre
+    if cap > 65536:
+        raise NotImplementedError(f"nms_pre={nms_pre}: more than 65536 candidates per image exceed the NMS kernel's 16-bit positions")
+    soft = dict(test_cfg["nms"]).get("type") == "soft_nms"
+    p = _post_ws(self, ("post", B, nlvl, nms_pre) + (("soft",) if soft else ()), B, cap, soft, K.decode_ws_bytes(B, nlvl, nms_pre),
+                 f"batch {B} with nms_pre={nms_pre}")
+    K.decode_candidates(ho["cls"], ho["reg"], ho["iou"], ho["scales"], ho["ldesc"], nlvl, B, self.num_classes,
+                        float(test_cfg["score_thr"]), nms_pre, hw, sf, p["boxes"], p["scores"], p["ctr"], p["labels"],
+                        p["count"], p["dws"])
+    return _nms_launch(self, p, B, cap, test_cfg, counts_out)
+
+
+def _head_out(self, head_out=None):
     e = self.engine
     if head_out is None:
         head_out = dict(cls=e.buf["cls"], reg=e.buf["reg_u"], iou=e.buf["iou"], scales=e.scales_tensor(), ldesc=e.ldesc,
                         nlvl=e.nlvl, B=e.B, level_hw=e.plv.hw)
-    ho = head_out
-    B, nlvl = ho["B"], ho["nlvl"]
+    return head_out
+
+
+def _nms_pre(self, test_cfg, level_hw):
     nms_pre = int(test_cfg.get("nms_pre", -1))
     if nms_pre <= 0:
-        nms_pre = max(h * w for h, w in ho["level_hw"]) * self.num_classes
-    cap = nlvl * nms_pre
-    if cap > 65536:
-        raise NotImplementedError(f"nms_pre={nms_pre}: more than 65536 candidates per image exceed the NMS kernel's 16-bit positions")
-    ncfg = dict(test_cfg["nms"])
-    typ = ncfg.get("type")
-    soft = typ == "soft_nms"          # Soft-NMS has a workspace of its own (24 B per candidate): no dense mask, no aux rows
-    key = ("post", B, nlvl, nms_pre) + (("soft",) if soft else ())
+        nms_pre = max(h * w for h, w in level_hw) * self.num_classes
+    return nms_pre
+
+
+def _post_ws(self, key, B, cap, soft, extra_bytes, what, pool=0):
+    """The cached buffers of one post-processing geometry: the candidate lists [B, cap] the NMS reads, its workspace, and
+    `extra_bytes` of decode workspace (dws); pool > 0 (test-time augmentation): the views' candidate pool of that many
+    entries in front of them.  The limit (RADET_POST_WS_LIMIT_GB) is checked on cap, the capacity the NMS sees."""
     posts = self.__dict__.setdefault("_posts", {})
     if key not in posts:
         # the NMS workspace holds a dense cap x cap / 64 x 8 B suppression mask per image (+ sort keys): 7 MiB per image at
         # the BOP configs' nms_pre = 1000, ~310 MB at nms_pre = 10000, 512 MiB at the 65536-candidate limit
-        need = (K.soft_nms_ws_bytes if soft else K.nms_ws_bytes)(B, cap) + K.decode_ws_bytes(B, nlvl, nms_pre)
+        need = (K.soft_nms_ws_bytes if soft else K.nms_ws_bytes)(B, cap) + extra_bytes + 32 * pool
         limit = int(float(os.environ.get("RADET_POST_WS_LIMIT_GB", "16")) * 2 ** 30)
         if need > limit:
-            raise MemoryError(f"decode + NMS workspaces for batch {B} with nms_pre={nms_pre} ({cap} candidates per image) need "
+            raise MemoryError(f"decode + NMS workspaces for {what} ({cap} candidates per image) need "
                               f"{need / 2 ** 30:.1f} GiB (dense suppression mask: cap^2 / 8 bytes per image); lower nms_pre or the "
                               f"batch, or raise RADET_POST_WS_LIMIT_GB (now {limit / 2 ** 30:.0f})")
         while posts and (len(posts) >= 8 or sum(v["nws"].numel() for v in posts.values()) + need > limit):
@@ -1141,15 +1159,24 @@ def _post_launch(self, hw, sf, test_cfg, head_out=None, counts_out=None):
             boxes=torch.empty(B, cap, 4, device=dev), scores=torch.empty(B, cap, device=dev),
             ctr=torch.empty(B, cap, device=dev), labels=torch.empty(B, cap, dtype=torch.long, device=dev),
             count=torch.zeros(B, dtype=torch.int32, device=dev), cscore=torch.empty(B, cap, device=dev),
-            dws=torch.empty(K.decode_ws_bytes(B, nlvl, nms_pre), dtype=torch.uint8, device=dev),
+            dws=torch.empty(extra_bytes, dtype=torch.uint8, device=dev),
             nws=torch.empty((K.soft_nms_ws_bytes if soft else K.nms_ws_bytes)(B, cap), dtype=torch.uint8, device=dev))
         if not soft:
             posts[key].update(aux0=torch.zeros(B, cap, dtype=torch.long, device=dev),
                               aux1=torch.zeros(B, cap, dtype=torch.long, device=dev))
-    p = posts[key]
-    K.decode_candidates(ho["cls"], ho["reg"], ho["iou"], ho["scales"], ho["ldesc"], nlvl, B, self.num_classes,
-                        float(test_cfg["score_thr"]), nms_pre, hw, sf, p["boxes"], p["scores"], p["ctr"], p["labels"],
-                        p["count"], p["dws"])
+        if pool:
+            posts[key].update(pool_boxes=torch.empty(pool, 4, device=dev), pool_scores=torch.empty(pool, device=dev),
+                              pool_ctr=torch.empty(pool, device=dev), pool_labels=torch.empty(pool, dtype=torch.long, device=dev))
+    return posts[key]
+
+
+def _nms_launch(self, p, B, cap, test_cfg, counts_out=None):
+    """The NMS half of the post-processing, shared by the single-view path and test-time augmentation: the config's NMS
+    (vote / global_vote / nms / soft_nms) over the candidate lists p[boxes, scores, ctr, labels, count] of capacity cap, and
+    max_per_img.  Returns (boxes, scores, labels, counts)."""
+    ncfg = dict(test_cfg["nms"])
+    typ = ncfg.get("type")
+    soft = typ == "soft_nms"          # Soft-NMS has a workspace of its own (24 B per candidate): no dense mask, no aux rows
     max_per_img = int(test_cfg.get("max_per_img", 100))
     k = max_per_img if max_per_img > 0 else cap
     ob = torch.zeros(B, k, 4, device=self.dev)
@@ -1203,6 +1230,11 @@ def _detect_graph(self, img, img_metas, test_cfg, rescale=False, crops=None):
     serving is otherwise bound by the host's launch rate (3.2 ms of Python + ctypes enqueue for ~1.7 ms of GPU work
     at batch 1).  Inputs are copied into the graph's static buffers; results are read back like `detect`.  crops= is refused:
     the frames' addresses change from call to call and a captured launch holds the ones it was captured with."""
+    if isinstance(img, (list, tuple)):
+        if len(img) != 1:
+            raise NotImplementedError(f"detect_graph with {len(img)} views: test-time augmentation is not captured in a graph; "
+                                      "use detect_aug")
+        img, img_metas = img[0], img_metas[0]
     if crops is not None:
         raise NotImplementedError("detect_graph(crops=...): RoI crops are not captured in the graph (the frames' addresses are "
                                   "per call); use detect / detect_stream, or ops.crop_detections on the graph's detections")
@@ -1242,6 +1274,187 @@ def _detect_graph(self, img, img_metas, test_cfg, rescale=False, crops=None):
         g["img"].copy_(img)
         g["graph"].replay()
         return _post_collect(self, *g["outs"])
+
+
+# ---------------------------------------------------------------------- test-time augmentation
+def _level_hw(H, W):
+    """the head's level sizes for an H x W input (the engine's own chain: stem 7/2/3, pool 3/2/1, three stride-2 stages,
+    two stride-2 extra levels) -- known before any launch, for the capacity checks of detect_aug"""
+    from .engine import conv_out_hw
+    hw = conv_out_hw(*conv_out_hw(H, W, 7, 2, 3), 3, 2, 1)
+    out = []
+    for _ in range(5):
+        hw = conv_out_hw(*hw, 3, 2, 1)
+        out.append(hw)
+    return out
+
+
+def _view_groups(imgs):
+    """consecutive views of one tensor shape: [(first view, one past the last)] -- each runs as one forward batch"""
+    groups, v0 = [], 0
+    for v in range(1, len(imgs) + 1):
+        if v == len(imgs) or tuple(imgs[v].shape) != tuple(imgs[v0].shape):
+            groups.append((v0, v))
+            v0 = v
+    return groups
+
+
+def _stack_views(ts):
+    """the views of a group as one batch: no copy when they are consecutive slices of one tensor (ImagePipeline writes a
+    scale's views that way), else a concatenation"""
+    if len(ts) == 1:
+        return ts[0]
+    t0 = ts[0]
+    if all(t.is_contiguous() and t.untyped_storage().data_ptr() == t0.untyped_storage().data_ptr()
+           and t.storage_offset() == t0.storage_offset() + i * t0.numel() for i, t in enumerate(ts)):
+        return torch.empty(0, dtype=t0.dtype, device=t0.device).set_(t0.untyped_storage(), t0.storage_offset(),
+                                                                     (len(ts) * t0.shape[0],) + tuple(t0.shape[1:]))
+    return torch.cat(ts)
+
+
+def _aug_plan(self, imgs, img_metas, test_cfg):
+    """Host part of detect_aug, before any launch: the checks, the groups, the pool layout and the merge descriptor.
+    -> dict(V, B, groups [(v0, v1, nms_pre, cap, pool offset)], cap_out, pool, desc (ndarray), hw, sf0)"""
+    V = len(imgs)
+    if V != len(img_metas) or not 1 <= V <= K.TTA_MAX_VIEWS:
+        raise ValueError(f"detect_aug: {V} views with {len(img_metas)} lists of metas (1..{K.TTA_MAX_VIEWS} views, one list each)")
+    B = int(imgs[0].shape[0])
+    for v in range(V):
+        if int(imgs[v].shape[0]) != B or len(img_metas[v]) != B:
+            raise ValueError(f"detect_aug: view {v} holds {int(imgs[v].shape[0])} images and {len(img_metas[v])} metas, view 0 "
+                             f"{B}: every view is a view of the same batch")
+    for b in range(B):
+        shapes = {tuple(m[b]["ori_shape"]) for m in img_metas if "ori_shape" in m[b]}
+        if len(shapes) > 1:
+            raise ValueError(f"detect_aug: the views of image {b} disagree in ori_shape ({sorted(shapes)})")
+    nlvl = len(self.engine.strides)
+    groups, pool, cap_out = [], 0, 0
+    hw = np.zeros((V * B, 2), np.float32)
+    sf = np.zeros((V * B, 4), np.float32)
+    flips, starts, caps = (np.zeros(V * B, np.int32) for _ in range(3))
+    pres = []
+    for v0, v1 in _view_groups(imgs):
+        nms_pre = _nms_pre(self, test_cfg, _level_hw(int(imgs[v0].shape[2]), int(imgs[v0].shape[3])))
+        cap = nlvl * nms_pre
+        groups.append((v0, v1, nms_pre, cap, pool))
+        pres.append(nms_pre)
+        for v in range(v0, v1):
+            for b, m in enumerate(img_metas[v]):
+                r = v * B + b
+                hw[r] = m["img_shape"][:2]
+                sf[r] = np.asarray(m["scale_factor"], np.float32).reshape(4)
+                direction = m.get("flip_direction") if m.get("flip") else None
+                if direction not in K.FLIP_CODES:
+                    raise ValueError(f"detect_aug: view {v} has flip_direction {direction!r}")
+                flips[r], starts[r], caps[r] = K.FLIP_CODES[direction], pool + ((v - v0) * B + b) * cap, cap
+        pool += (v1 - v0) * B * cap
+        cap_out += (v1 - v0) * cap
+    if cap_out > 65536:
+        raise NotImplementedError(f"test-time augmentation with V={V} views, nlvl={nlvl} levels and nms_pre={sorted(set(pres))}: "
+                                  f"the merged list of {cap_out} candidates per image exceeds the NMS kernel's 65536 (16-bit "
+                                  f"positions); lower nms_pre")
+    if pool >= 2 ** 31:
+        raise NotImplementedError(f"test-time augmentation: a candidate pool of {pool} entries (batch {B}); lower nms_pre or the batch")
+    return dict(V=V, B=B, nlvl=nlvl, groups=groups, cap_out=cap_out, pool=pool, desc=K.merge_desc_rows(hw, sf, flips, starts, caps),
+                hw=hw, sf0=sf[:B].copy())
+
+
+def _aug_launch(self, imgs, plan, test_cfg, upload, counts_out=None):
+    """Device part of detect_aug on the current stream: per group of views one forward pass and, behind it, one
+    radet_decode_candidates into the group's block of the pool (view coordinates, clamped to the view's own img_shape);
+    ONE radet_merge_views; the config's NMS over the merged lists (_nms_launch).  upload: ndarray -> device tensor.
+    Returns the NMS outputs, boxes in the frames' coordinates."""
+    V, B, nlvl, cap_out, pool = plan["V"], plan["B"], plan["nlvl"], plan["cap_out"], plan["pool"]
+    soft = dict(test_cfg["nms"]).get("type") == "soft_nms"
+    dbytes = max(K.decode_ws_bytes((v1 - v0) * B, nlvl, pre) for v0, v1, pre, _, _ in plan["groups"])
+    key = ("aug", B, tuple(g[:4] for g in plan["groups"])) + (("soft",) if soft else ())
+    p = _post_ws(self, key, B, cap_out, soft, dbytes, f"batch {B} with {V} views, nlvl={nlvl}, nms_pre="
+                 f"{sorted({g[2] for g in plan['groups']})}", pool=pool)
+    if "view_count" not in p:
+        p["view_count"] = torch.zeros(V * B, dtype=torch.int32, device=self.dev)
+    hw = upload(plan["hw"])
+    desc = upload(plan["desc"])
+    for v0, v1, nms_pre, cap, off in plan["groups"]:
+        self.forward(_stack_views([t.to(self.dev) for t in imgs[v0:v1]]))
+        ho = _head_out(self)
+        n = (v1 - v0) * B
+        if ho["B"] != n or ho["nlvl"] != nlvl or _nms_pre(self, test_cfg, ho["level_hw"]) != nms_pre:
+            raise RuntimeError("detect_aug: the engine's level geometry differs from the planned one")
+        K.decode_candidates(ho["cls"], ho["reg"], ho["iou"], ho["scales"], ho["ldesc"], nlvl, n, self.num_classes,
+                            float(test_cfg["score_thr"]), nms_pre, hw[v0 * B:v1 * B], None, p["pool_boxes"][off:off + n * cap],
+                            p["pool_scores"][off:off + n * cap], p["pool_ctr"][off:off + n * cap],
+                            p["pool_labels"][off:off + n * cap], p["view_count"][v0 * B:v1 * B], p["dws"])
+    K.merge_views(plan["desc"], desc, V, B, p["pool_boxes"], p["pool_scores"], p["pool_ctr"], p["pool_labels"], p["view_count"],
+                  cap_out, p["boxes"], p["scores"], p["ctr"], p["labels"], p["count"])
+    return _nms_launch(self, p, B, cap_out, test_cfg, counts_out)
+
+
+def _detect_aug(self, imgs, img_metas, test_cfg, rescale=False, crops=None):
+    """aug_test: `detect` over several views of one batch (test-time augmentation; imgs, img_metas: lists over views, as
+    MultiScaleFlipAug's collated batch).  Views of one tensor shape run as ONE forward batch -- a scale's unflipped and
+    flipped views at batch F * B.  The union handed to the NMS holds exactly the candidates the single-view path would
+    hand its NMS for each view (score_thr on the class score, the top nms_pre per level and view), mapped back to the
+    frame (bbox_mapping_back) and concatenated in view order; then the config's own NMS and max_per_img, once.  This
+    composition rule is this project's: the reference's aug_test cannot run with this head.  rescale=False: the kept
+    boxes times view 0's scale factor (aug_test_bboxes).  crops: as in `detect`, cut from the frames with the merged
+    detections (the descriptor table's first B rows).  Returns what `detect` returns."""
+    with torch.no_grad():
+        plan = _aug_plan(self, imgs, img_metas, test_cfg)
+        if plan["V"] == 1:
+            return _detect(self, imgs[0], img_metas[0], test_cfg, rescale, crops)
+        B = plan["B"]
+
+        def upload(a):
+            return torch.from_numpy(a).to(self.dev)
+        counts = None if crops is None else _crop_counts(self, B)
+        outs = _aug_launch(self, imgs, plan, test_cfg, upload, counts_out=counts)
+        job = None if crops is None else _crops_launch(self, outs, counts, crops)
+        if not rescale:
+            outs = (outs[0] * upload(plan["sf0"])[:, None, :],) + tuple(outs[1:])
+        if crops is None:
+            return _post_collect(self, *outs)
+        host = counts.cpu().numpy()
+        return (_post_collect(self, *outs, counts=host),) + _crops_collect(job, host, B)
+
+
+def _detect_aug_stream(self, batches, test_cfg, crops=None):
+    """`detect_aug(rescale=True)` over an iterable of multi-view batches (imgs [V], img_metas [V], (descriptor table, frames))
+    with the host one batch behind the device: batch k + 1's device program is enqueued before the host waits for batch k's
+    counts, which arrive through a pinned copy behind an event, as in detect_stream.  Everything runs on the caller's stream:
+    the decode / NMS overlap of detect_stream on a second stream is absent here.  crops: an ops.crops.CropSpec; the crops are
+    cut from the batch's frames (the table's first B rows) behind its NMS.  Yields what detect_aug returns, in order."""
+    def upload(a):
+        return torch.from_numpy(a).pin_memory().to(self.dev, non_blocking=True)
+
+    def collect(rec):
+        outs, done, pinned, B, job = rec[:5]    # (the rest keeps the batch's views, table and frames alive until here)
+        done.synchronize()                      # the host waits for THIS batch only
+        host = pinned.numpy()
+        dets = _post_collect(self, *outs, counts=host)
+        return dets if crops is None else (dets,) + _crops_collect(job, host, B)
+
+    prev = None
+    with torch.no_grad():
+        for imgs, metas, source in batches:
+            plan = _aug_plan(self, imgs, metas, test_cfg)
+            B = plan["B"]
+            counts = torch.zeros(B, dtype=torch.int32, device=self.dev) if crops is None else _crop_counts(self, B)
+            outs = _aug_launch(self, imgs, plan, test_cfg, upload, counts_out=counts)
+            job = None if crops is None else _crops_launch(self, outs, counts, (crops, source[0]))
+            pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
+            pinned.copy_(counts, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            rec = (outs, done, pinned, B, job, source, imgs)
+            if prev is not None:
+                yield collect(prev)
+            prev = rec
+        if prev is not None:
+            yield collect(prev)
+
+
+DetectorRuntime.detect_aug = _detect_aug
+DetectorRuntime.detect_aug_stream = _detect_aug_stream
 
 
 def _rows_to_nchw(self, rows, levels, ch):
@@ -1386,8 +1599,8 @@ def _get_bboxes_api(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, 
     """ATSSHead.get_bboxes / RADetHead._get_bboxes_single (atss_head.py:325-387, radet_head.py:55-170): NCHW lists
     -> [(det_bboxes [k, 5], det_labels [k])] per image (device tensors)."""
     if not with_nms:
-        raise NotImplementedError("get_bboxes(with_nms=False) only feeds test-time augmentation, which is out of scope "
-                                  "(flip=False in the BOP configs)")
+        raise NotImplementedError("get_bboxes(with_nms=False) only feeds the reference's aug_test; test-time augmentation "
+                                  "runs through detect_aug (RADet.aug_test), which merges the views' candidates on the GPU")
     assert len(cls_scores) == len(bbox_preds) == len(centernesses)
     with torch.no_grad():
         lv, rc = _lists_to_rows(self, cls_scores, self.num_classes)

@@ -11,6 +11,15 @@ Host clock around work that ends in a device synchronise; medians over --reps ro
 every shape.  No figure here is a pass condition.
 
     python tools/bench_frames.py [--batch 8] [--iters 50] [--reps 7] [--frames 400]
+
+--tta times test-time augmentation instead and writes profiles/bench_tta.json: `inference_detector(frames)` with a set_tta override of
+V = 2 views (img_scale (640, 480), unflipped + horizontal flip: one forward batch of 2 * --batch) against the yardstick,
+V single-view `inference_detector` calls on the same frames in the same process, in alternating rounds; and, between HIP
+events, the radet_merge_views launch on the call's own candidate pool and a radet_preprocess_frames launch with flipped rows
+beside the same launch without flips.  The single-view call's launch sequence is recorded (names and count) so that it can be
+compared with the commit before.
+
+    python tools/bench_frames.py --tta [--batch 4] [--iters 20] [--reps 7]
 """
 import argparse
 import json
@@ -47,16 +56,139 @@ def wall_ms(fn, iters):
     return (time.perf_counter() - t0) * 1e3 / iters
 
 
+def event_ms(fn, iters):
+    """device milliseconds per launch of `iters` back-to-back launches between two HIP events"""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def log_calls(fn):
+    from radet_amd import _lib
+    seen, call = [], _lib.call
+    _lib.call = lambda name, *a: seen.append(name) or call(name, *a)
+    try:
+        fn()
+    finally:
+        _lib.call = call
+    return seen
+
+
+def band(xs):
+    xs = sorted(xs)
+    return [xs[int(0.1 * (len(xs) - 1))], xs[int(round(0.9 * (len(xs) - 1)))]]
+
+
+def tta_main(args):
+    from radet_amd import kernels as K
+    from radet_amd.apis import inference_detector, set_tta
+    from radet_amd.apis.inference import _frame_pipeline, _prepare_frames
+    from radet_amd.datasets.loading import frame_desc_rows
+    from radet_amd.models import build_detector
+    from radet_amd.runtime import _aug_plan
+    from radet_amd.utils import Config
+    from radet_amd.utils.synth_init import synth_fill
+    dev = torch.device("cuda")
+    B = args.batch
+    rng = np.random.RandomState(0)
+    frames = [rng.randint(0, 256, (480, 640, 3)).astype(np.uint8) for _ in range(B)]
+    cfg = Config.fromfile(os.path.join(ROOT, "configs", "bop", "r50_ycbv_pbr.py"))
+    cfg.model["pretrained"] = None
+    torch.manual_seed(0)
+    model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).to(dev).eval()
+    synth_fill(model, seed=0)
+    with torch.no_grad():
+        model.bbox_head.atss_cls.bias += 2.0                        # (candidates above the threshold: full lists)
+    model.cfg = Config(dict(data=dict(test=dict(pipeline=pipeline_cfg("LoadImageFromFile")))))
+    tta = dict(img_scale=[(640, 480)], flip=True, flip_direction="horizontal")
+    V = 2
+    def tta_call():
+        set_tta(model, tta)
+        try:
+            return inference_detector(model, frames)
+        finally:
+            set_tta(model, None)
+    paths = dict(tta=tta_call,
+                 single_x_v=lambda: [inference_detector(model, frames) for _ in range(V)])
+    for fn in paths.values():
+        wall_ms(fn, 3)
+    single_log = log_calls(lambda: inference_detector(model, frames))
+    tta_log = log_calls(paths["tta"])
+    rounds = {k: [] for k in paths}
+    for _ in range(args.reps):
+        for k, fn in paths.items():                                 # alternating: drift hits both alike
+            rounds[k].append(wall_ms(fn, args.iters))
+    # the merge launch alone, on the pool the call above left behind
+    rt = model.runtime()
+    data = _prepare_frames(_frame_pipeline(model, tta), frames)
+    plan = _aug_plan(rt, data["img"], data["img_metas"], model.test_cfg)
+    p = next(v for k, v in rt._posts.items() if k[0] == "aug")
+    desc = torch.from_numpy(plan["desc"]).to(dev)
+
+    def merge():
+        K.merge_views(plan["desc"], desc, V, B, p["pool_boxes"], p["pool_scores"], p["pool_ctr"], p["pool_labels"], p["view_count"],
+                      plan["cap_out"], p["boxes"], p["scores"], p["ctr"], p["labels"], p["count"])
+    # the preparation launch: V * B rows with the second half flipped, beside the same rows unflipped
+    buf = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).to(dev)
+    mean = np.array(NORM["mean"], np.float32)
+    stdinv = (1.0 / np.array(NORM["std"], np.float64)).astype(np.float32)
+    out = torch.empty(V * B, 3, 480, 640, device=dev)
+    tables = {}
+    for name, flips in (("flipped", [0] * B + [K.PREP_FLIP_H] * B), ("unflipped", [0] * (V * B))):
+        rows, _, _ = frame_desc_rows(frames, [(480, 640)] * (V * B), True, buf.data_ptr(), views=V, flips=flips)
+        tables[name] = torch.from_numpy(rows).to(dev)
+    launches = dict(merge_views_ms=merge,
+                    preprocess_flipped_ms=lambda: K.preprocess_frames(tables["flipped"], V * B, 480, 640, mean, stdinv, out),
+                    preprocess_unflipped_ms=lambda: K.preprocess_frames(tables["unflipped"], V * B, 480, 640, mean, stdinv, out))
+    for fn in launches.values():
+        event_ms(fn, 10)
+    lrounds = {k: [] for k in launches}
+    for _ in range(args.reps):
+        for k, fn in launches.items():
+            lrounds[k].append(event_ms(fn, 50))
+    counts = p["view_count"].cpu().tolist()
+    med = statistics.median
+    out = dict(case=dict(batch=B, views=V, frame_hw=[480, 640], tta=dict(img_scale=[[640, 480]], flip=True, flip_direction="horizontal"),
+                         forward_batch=V * B, nms_pre=int(model.test_cfg["nms_pre"]), merged_capacity=plan["cap_out"],
+                         candidates_per_view_row=[min(counts), max(counts)], iters=args.iters, reps=args.reps),
+               device=torch.cuda.get_device_name(0), clocks="default governor, not pinned; medians of alternating rounds",
+               yardstick="V single-view inference_detector calls on the same frames, same process (the single-view path issues "
+                         "the launches of the commit before: single_view_launches)",
+               tta_call_ms=med(rounds["tta"]), single_view_x_v_ms=med(rounds["single_x_v"]),
+               tta_over_yardstick=med(rounds["tta"]) / med(rounds["single_x_v"]),
+               tta_call_ms_band=band(rounds["tta"]), single_view_x_v_ms_band=band(rounds["single_x_v"]),
+               tta_call_ms_all=rounds["tta"], single_view_x_v_ms_all=rounds["single_x_v"],
+               **{k: med(v) for k, v in lrounds.items()}, **{k + "_all": v for k, v in lrounds.items()},
+               single_view_launches=len(single_log), tta_launches=len(tta_log),
+               single_view_launch_tail=single_log[-3:], single_view_first_launch=single_log[0],
+               tta_launch_counts={n: tta_log.count(n) for n in ("radet_preprocess_frames", "radet_decode_candidates",
+                                                                "radet_merge_views", "radet_nms")})
+    path = args.out or os.path.join(ROOT, "profiles", "bench_tta.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--frames", type=int, default=400, help="frames of the end-to-end pass")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_frames.json"))
+    ap.add_argument("--tta", action="store_true", help="time test-time augmentation instead -> profiles/bench_tta.json")
+    ap.add_argument("--out", default=None, help="default: profiles/bench_frames.json (profiles/bench_tta.json with --tta)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frames.py measures on the GPU: no device found")
+    if args.tta:
+        return tta_main(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "bench_frames.json")
     from radet_amd.apis import detect_frames
     from radet_amd.datasets.loading import ImagePipeline
     from radet_amd.models import build_detector
