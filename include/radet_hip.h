@@ -749,6 +749,42 @@ int radet_merge_views(const int* desc_host, const int* desc, int V, int B, size_
                       int cap_out, float* out_boxes, float* out_scores, float* out_ctr, int64_t* out_labels, int* out_count,
                       void* stream);
 
+/* ---- tiled inference: the rows' candidates filtered at the tile borders, back in the frame, packed per image
+ *      (csrc/tiles.hip), one launch.  A batch of B frames has R = row_start[B] rows, image-major: image b's rows are
+ *      [row_start[b], row_start[b + 1]) -- its full-frame row, if it has one, then its tiles -- 1..TILE_MAX_ROWS of them.
+ *      Input: the rows' candidate lists as radet_decode_candidates writes them in ROW coordinates (scale_factor = NULL, boxes
+ *      clamped to the row's img_shape) into ONE pool, laid out as for radet_merge_views; counts i32 [R].
+ *      desc = R rows of TILE_DESC_INTS 32-bit words:
+ *        {h, w (the row's img_shape, f32 bits), sx, sy, sx, sy (its scale_factor, f32 bits), x0, y0 (where the row's source
+ *         rectangle starts in the frame, the integers as f32 bits), edge mask (TILE_EDGE_L | _T | _R | _B: that side of the
+ *         row is a cut through the frame, not a side of the frame), start (pool index of the row's first candidate), cap};
+ *      the full-frame row has x0 = y0 = 0 and mask 0.  desc and row_start are passed twice, as radet_merge_views' desc is:
+ *      *_host (host memory, read during the call only) for the argument checks, the device copies for the kernel.
+ *      A candidate (x1, y1, x2, y2) of a row is DROPPED if  L and x1 <= m,  or T and y1 <= m,  or R and x2 >= w - m,  or
+ *      B and y2 >= h - m  (m = edge_margin; w - m, h - m in fp32, rounded once; comparisons with a NaN are false).  With
+ *      m = 0 these are exactly the boxes the decode clamped onto a cut: the object reaches past the tile, and a neighbouring
+ *      tile or the full-frame row sees it whole.  A kept box is mapped back as  x / sx + x0  (a true IEEE division, then one
+ *      add, each rounded once; x2 and y2 use words 4 and 5); scores, centerness and labels are copied.
+ *      Output, per image b: out_* [B, cap_out] hold the kept candidates in row order, inside a row in candidate order (a
+ *      stable compaction; a count below 0 counts as 0, one above its row's cap as cap); out_count[b] = the number kept,
+ *      out_dropped[b] = the number dropped, together the sum of the image's clamped counts.  Slots at and beyond out_count[b]
+ *      are not written.  grid B: one workgroup of 512 threads per image, ballot + popcount ranks, no atomics, so the order
+ *      does not depend on scheduling.  No host synchronisation, no allocation, capturable.  RADET_ERR_ARG before any launch:
+ *      B < 0 or > 65535, cap_out outside 1..65536, an edge_margin that is negative or not finite, a NULL pointer with B > 0,
+ *      and from the host copies: row_start[0] != 0, an image with no row or more than TILE_MAX_ROWS, an edge mask outside
+ *      0..15, a cap < 0, a row whose [start, start + cap) leaves [0, pool), an image whose caps add up to more than cap_out.
+ *      B == 0: RADET_OK, no launch. */
+#define TILE_MAX_ROWS 64
+#define TILE_DESC_INTS 11
+#define TILE_EDGE_L 1
+#define TILE_EDGE_T 2
+#define TILE_EDGE_R 4
+#define TILE_EDGE_B 8
+int radet_merge_tiles(const int* desc_host, const int* desc, const int* row_start_host, const int* row_start, int B, size_t pool,
+                      const float* pool_boxes, const float* pool_scores, const float* pool_ctr, const int64_t* pool_labels,
+                      const int* counts, float edge_margin, int cap_out, float* out_boxes, float* out_scores, float* out_ctr,
+                      int64_t* out_labels, int* out_count, int* out_dropped, void* stream);
+
 /* ---- detections -> a packed batch of RoI crops (csrc/crops.hip), two launches, nothing read back to the host.
  * radet_crop_plan (one workgroup): boxes f32 [B,K,4] (16-byte aligned), scores f32 [B,K], counts i32 [B] -- the NMS outputs
  *      as they are -- walked image-major, then by rank j < counts[b].  A detection is valid if its four coordinates are

@@ -141,6 +141,7 @@ SIGNATURES = {
     "radet_paste_maps": (_i, [_p, _sz, _i, _p, _i, _i, _i, _p, _p]),
     "radet_preprocess_frames": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p]),
     "radet_merge_views": (_i, [_p, _p, _i, _i, _sz, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "radet_merge_tiles": (_i, [_p, _p, _p, _p, _i, _sz, _p, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "radet_crop_plan": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p]),
     "radet_crop_frames": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p]),
     "radet_grid_anchors": (_i, [_p, _p, _i, _i, _p]),

@@ -80,6 +80,66 @@ def set_tta(model, tta=None):
     return model
 
 
+def set_tiling(model, tiling=None):
+    """Tiled inference for this model's calls on loaded frames (inference_detector, detect_frames), set on the model beside
+    its cfg, like set_tta: tiling=dict(tile=(tw, th), overlap=0.25, full_frame=True, edge_margin=0.0, batch=16, nms_pre=None).
+    Every frame is cut into overlapping tiles of tw x th frame pixels (ops.plan_tiles; overlap in pixels (ow, oh) or one
+    float ratio of the tile); the frame itself (full_frame) and every tile go through the config's test pipeline at its
+    img_scale as rows of one batch, `batch` rows per forward pass; candidates that touch a cut side of their tile within
+    edge_margin pixels are dropped, the others are mapped back to the frame and the config's NMS runs once per frame
+    (DetectorRuntime.detect_tiles).  nms_pre replaces test_cfg's for these calls: a tile holds fewer objects than a frame, and
+    the merged list of a frame is limited to 65536 candidates.  None clears it.  With tiling set, file names, normalised
+    tensors, a set_tta override and a multi-view config are refused.  The plan, the edge rule and the defaults are this
+    project's own starting points; nobody has evaluated them on BOP data.  Returns the model."""
+    from ..ops.tiles import tiling_spec
+    object.__setattr__(model, "tiling", None if tiling is None else tiling_spec(dict(tiling) if isinstance(tiling, dict) else tiling))
+    return model
+
+
+def _tile_pipeline(model):
+    """the frame pipeline a tiled call runs its rows through; refuses what tiling does not compose with"""
+    if getattr(model, "tta", None) is not None:
+        raise NotImplementedError("set_tiling together with a set_tta override: tiles and test-time-augmentation views are not "
+                                  "combined; clear one of them (set_tta(model, None) or set_tiling(model, None))")
+    pipeline = _frame_pipeline(model)
+    if pipeline.views > 1:
+        raise NotImplementedError(f"set_tiling with a config whose MultiScaleFlipAug makes {pipeline.views} views: tiles and "
+                                  "test-time-augmentation views are not combined; use one img_scale and flip=False, or clear the "
+                                  "tiling (set_tiling(model, None))")
+    return pipeline
+
+
+def _refuse_untiled(imgs):
+    """with tiling set, inference_detector takes loaded frames only"""
+    if isinstance(imgs, str) or (isinstance(imgs, (list, tuple)) and any(isinstance(i, str) for i in imgs)):
+        raise NotImplementedError("inference_detector on file names with set_tiling(model, ...): tiled inference is built for "
+                                  "frames in memory; load the images (mmcv.imread order: HxWx3 uint8 BGR) and pass them")
+    if not (_is_frame(imgs) or (isinstance(imgs, (list, tuple)) and all(_is_frame(i) for i in imgs))):
+        raise NotImplementedError("inference_detector on a normalised NCHW tensor with set_tiling(model, ...): tiles are cut "
+                                  "from loaded frames (ndarray or uint8 tensor HxWx3 BGR) in front of the test pipeline; pass "
+                                  "the frames, or clear the tiling (set_tiling(model, None))")
+
+
+def _inference_tiles(model, frames, crops=None):
+    pipeline = _tile_pipeline(model)
+    if crops is None and not frames:
+        return []
+    spec = None
+    if crops is not None:
+        from ..ops.crops import check_frames
+        check_frames(frames)
+        spec = _crop_request(model, crops)
+    plan = pipeline.run_tile_rows(frames, model.tiling)
+    if model.training:
+        model.eval()
+    num_classes = model.bbox_head.num_classes
+    if spec is None:
+        dets = model.runtime().detect_tiles(plan["img"], plan, model.test_cfg)
+        return [bbox2result(b, l, num_classes) for b, l in dets]
+    dets, out, _ = model.runtime().detect_tiles(plan["img"], plan, model.test_cfg, crops=(spec, plan["table"]))
+    return [bbox2result(b, l, num_classes) for b, l in dets], out
+
+
 def _frame_pipeline(model, tta=None):
     """model.cfg.data.test.pipeline with its first stage replaced by LoadImageFromWebcam (radet/apis/inference.py:97-102), built
     once per model, test pipeline and tta= override (the few last ones are kept)"""
@@ -183,11 +243,14 @@ def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
     from its frames on the device behind its NMS; a frame's record holds views of the batch's tensors and the batch's n_total.
     Test-time augmentation -- set_tta(model, dict(img_scale=[...], flip=True, flip_direction=...)), or a config whose
     MultiScaleFlipAug makes several views: every batch runs DetectorRuntime.detect_aug's program -- the forward batch is F * batch_size per
-    scale (F: that scale's unflipped + flipped views) -- still one batch behind the device, on the caller's stream."""
+    scale (F: that scale's unflipped + flipped views) -- still one batch behind the device, on the caller's stream.
+    Tiled inference -- set_tiling(model, dict(tile=(tw, th), ...)): every batch runs DetectorRuntime.detect_tiles' program over
+    the rows of its batch_size frames (full-frame views and tiles), likewise one batch behind the device."""
     from ..ops.crops import check_frames, split_crops
     if batch_size < 1:
         raise ValueError(f"batch_size={batch_size}")
-    pipeline = _frame_pipeline(model, getattr(model, "tta", None))
+    tiling = getattr(model, "tiling", None)
+    pipeline = _tile_pipeline(model) if tiling is not None else _frame_pipeline(model, getattr(model, "tta", None))
     spec = None if crops is None else _crop_request(model, crops)
     if model.training:
         model.eval()
@@ -205,6 +268,12 @@ def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
 
     def prepared():
         for group in batches():
+            if tiling is not None:                               # (the plan carries the table and the frames with the batch)
+                if spec is not None:
+                    check_frames(group)
+                plan = pipeline.run_tile_rows(group, tiling)
+                yield plan["img"], plan
+                continue
             if pipeline.views > 1:
                 if spec is not None:
                     check_frames(group)
@@ -218,7 +287,9 @@ def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
             data, source = _prepare_frames(pipeline, group, True)
             yield _single_view(data) + (source,)             # (the stream carries the table and the frames with the batch)
 
-    if pipeline.views > 1:
+    if tiling is not None:
+        stream = model.runtime().detect_tiles_stream(prepared(), model.test_cfg, crops=spec)
+    elif pipeline.views > 1:
         stream = model.runtime().detect_aug_stream(prepared(), model.test_cfg, crops=spec)
     else:
         stream = model.runtime().detect_stream(prepared(), model.test_cfg, rescale=True, **({} if spec is None else dict(crops=spec)))
@@ -253,8 +324,19 @@ def inference_detector(model, imgs, scale_factor=None, crops=None):
     flip_direction='horizontal' | 'vertical' | 'diagonal' | a list)) overrides those three arguments of the config's stage
     (its transforms stay) for this model's calls.  The frames go through DetectorRuntime.detect_aug: the forward batch is F * batch_size per scale (F = that
     scale's unflipped + flipped views), the views' candidates are mapped back and merged on the GPU and the config's NMS
-    runs once.  How the views compose is this project's rule (detect_aug); with an override set, file names are refused."""
+    runs once.  How the views compose is this project's rule (detect_aug); with an override set, file names are refused.
+    Tiled inference, with loaded frames only: after set_tiling(model, dict(tile=(tw, th), ...)) every frame runs as its
+    full-frame view plus overlapping tiles at the network's resolution, merged by one NMS per frame
+    (DetectorRuntime.detect_tiles); results and crops= stay in the frames' coordinates."""
     tta = getattr(model, "tta", None)
+    if getattr(model, "tiling", None) is not None:
+        if tta is not None:
+            _tile_pipeline(model)                                # (refuses: tiling together with a set_tta override)
+        _refuse_untiled(imgs)
+        if _is_frame(imgs):
+            res = _inference_tiles(model, [imgs], crops)
+            return res[0] if crops is None else (res[0][0], res[1])
+        return _inference_tiles(model, list(imgs), crops)
     if tta is not None:
         names = isinstance(imgs, str) or (isinstance(imgs, (list, tuple)) and any(isinstance(i, str) for i in imgs))
         if names:

@@ -1224,6 +1224,54 @@ def upload_frames(frames, dst_hw, to_rgb, dev, views=1, flips=None):
     return up[:head].view(torch.int32)
 
 
+def tile_desc_rows(frames, rects, row_start, dst_hw, to_rgb, host_base):
+    """The descriptor rows of a TILED batch (tiled inference, ops/tiles.py): rects i32 [R, 4] (x0, y0, tw, th), image-major
+    with row_start i32 [B + 1], are source rectangles inside the frames.  A row of radet_preprocess_frames' table names a byte
+    address, a row stride and an h x w, so a rectangle of a frame is just another row: the frame's address shifted by
+    y0 * stride + 3 * x0, the frame's stride, the rectangle's th x tw -- the kernel reads it where the frame lies.  Frames
+    are placed as frame_desc_rows places them (host frames packed behind host_base, each ONCE; device tensors in place).
+    dst_hw: the resized size per row.  Host arithmetic only.  Returns (int32 [B, PREP_DESC_INTS] the source frames as
+    frame_desc_rows describes them at their own size -- what the RoI crops read --, int32 [R, PREP_DESC_INTS] the rows, byte
+    offset per frame or None, bytes of the upload)."""
+    B = len(frames)
+    rects = np.asarray(rects, np.int64).reshape(-1, 4)
+    if len(row_start) != B + 1 or int(row_start[0]) != 0 or int(row_start[-1]) != len(rects) or len(dst_hw) != len(rects):
+        raise ValueError(f"tile_desc_rows: row_start {list(row_start)} for {B} frames and {len(rects)} rows")
+    src, offs, nbytes = frame_desc_rows(frames, [tuple(int(v) for v in f.shape[:2]) for f in frames], to_rgb, host_base)
+    rows = np.zeros((len(rects), K.PREP_DESC_INTS), np.int32)
+    for b, f in enumerate(frames):
+        h, w = int(f.shape[0]), int(f.shape[1])
+        base = int(src[b, 0:2].view(np.uint32)[0]) | (int(src[b, 0:2].view(np.uint32)[1]) << 32)
+        stride = int(src[b, 2])
+        for r in range(int(row_start[b]), int(row_start[b + 1])):
+            x0, y0, tw, th = (int(v) for v in rects[r])
+            if not (0 <= x0 and 0 <= y0 and 1 <= tw and 1 <= th and x0 + tw <= w and y0 + th <= h):
+                raise ValueError(f"row {r}: the rectangle {(x0, y0, tw, th)} leaves its {w} x {h} frame")
+            addr = base + y0 * stride + 3 * x0
+            rows[r, 0:2] = np.array([addr & 0xFFFFFFFF, addr >> 32], np.uint32).view(np.int32)
+            rows[r, 2:8] = [stride, th, tw, dst_hw[r][0], dst_hw[r][1], K.PREP_TO_RGB if to_rgb else 0]
+    return src, rows, offs, nbytes
+
+
+def upload_tile_rows(frames, rects, row_start, dst_hw, to_rgb, dev):
+    """[the B source frames' table | the R rows' table | host frames, packed, each once] into one device buffer in ONE pinned,
+    non-blocking copy, as upload_frames does for a plain batch.  Returns (table i32 [B + R, PREP_DESC_INTS]: a view of the
+    buffer, which it keeps alive; its first B rows are what crops= reads, the rows' table starts at row B)."""
+    B, R = len(frames), len(rects)
+    head = (B + R) * K.PREP_DESC_INTS * 4
+    _, _, _, nbytes = tile_desc_rows(frames, rects, row_start, dst_hw, to_rgb, 0)
+    up = torch.empty(head + nbytes, dtype=torch.uint8, device=dev)
+    src, rows, offs, _ = tile_desc_rows(frames, rects, row_start, dst_hw, to_rgb, up.data_ptr() + head)
+    stage = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    host[:head] = np.concatenate([src, rows]).reshape(-1).view(np.uint8)
+    for f, o in zip(frames, offs):
+        if o is not None:
+            np.copyto(host[head + o:head + o + f.size].reshape(f.shape), f)
+    up.copy_(stage, non_blocking=True)
+    return up[:head].view(torch.int32).view(B + R, K.PREP_DESC_INTS)
+
+
 class ImagePipeline:
     """A pipeline that starts from files: host planning per sample, one batched device pass per batch.  Or from frames in
     memory (LoadImageFromWebcam first): a test pipeline whose device pass is one upload and one launch (_run_frames)."""
@@ -1776,6 +1824,61 @@ class ImagePipeline:
         if not self.frames:
             raise ValueError("run_frames: not a pipeline that starts from frames in memory")
         return self._run_frames(planned, True)
+
+    def run_tile_rows(self, frames, spec):
+        """Tiled inference (ops/tiles.py; spec: ops.tiles.TileSpec or apis.set_tiling's dict): the rows of a batch of frames --
+        image-major, per frame its full-frame row (spec.full_frame), then its tiles in plan order -- each planned by this
+        pipeline as if its source rectangle were a frame of its own (Resize to the single img_scale, Normalize, Pad: its own
+        img_shape, scale_factor and pad_shape), all written into ONE tensor [R, 3, Hp, Wp] at the largest pad_shape among
+        them by ONE upload (upload_tile_rows: every host frame once) and ONE radet_preprocess_frames launch.  Row r's slice
+        holds the bits the single-view pipeline writes for a copy of frame[y0:y0 + th, x0:x0 + tw].  Nothing waits for the
+        device.  -> dict(img f32 [R, 3, Hp, Wp], img_metas [R], rects i32 [R, 4], edges i32 [R], row_start i32 [B + 1],
+        table i32 [B + R, PREP_DESC_INTS] (its first B rows: the source frames, what crops= reads), frames, and the spec's
+        edge_margin, batch, nms_pre) -- the plan DetectorRuntime.detect_tiles takes."""
+        import random
+        from ..ops.tiles import tile_rows, tiling_spec
+        spec = tiling_spec(spec)
+        if not self.frames or self.views != 1:
+            raise NotImplementedError("tiled inference runs a single-view pipeline that starts from frames in memory "
+                                      "(LoadImageFromWebcam, one img_scale, flip=False); drop the extra views or the tiling")
+        dev = self._dev()
+        frames = [f.numpy() if isinstance(f, torch.Tensor) and not f.is_cuda and f.dtype == torch.uint8 else f
+                  for f in frames]                                  # (a host tensor is a host frame)
+        for f in frames:
+            if not isinstance(f, (np.ndarray, torch.Tensor)) or len(f.shape) != 3 or f.shape[2] != 3 or 0 in f.shape:
+                raise ValueError("tiled inference takes loaded frames: ndarrays or device tensors HxWx3 uint8 (BGR)")
+            if isinstance(f, torch.Tensor) and f.device != dev:
+                raise ValueError(f"a frame on {f.device} in a batch prepared on {dev}")
+        rects, edges, row_start = tile_rows([f.shape[:2] for f in frames], spec)
+        R = len(rects)
+        if R > 65535:
+            raise NotImplementedError(f"a tiled batch of {R} rows: one radet_preprocess_frames launch takes at most 65535; pass "
+                                      "fewer frames per batch")
+        planned = []
+        for b, f in enumerate(frames):
+            for r in range(int(row_start[b]), int(row_start[b + 1])):
+                x0, y0, tw, th = (int(v) for v in rects[r])
+                planned.append(self.plan(dict(img=f[y0:y0 + th, x0:x0 + tw], bbox_fields=[], mask_fields=[], seg_fields=[]),
+                                         random, np.random))      # (a view: planning reads its shape, never its pixels)
+        if not planned:
+            raise ValueError("tiled inference on an empty batch of frames")
+        hw = [tuple(int(v) for v in s.get("resize_hw", s["img"].shape[:2])) for s in planned]
+        cfg0 = planned[0]["img_norm_cfg"]
+        if any(s.get("flip") for s in planned):
+            raise ValueError("a single-view pipeline that starts with LoadImageFromWebcam does not flip")
+        if any(s["pad_shape"][0] < h or s["pad_shape"][1] < w for s, (h, w) in zip(planned, hw)):
+            raise ValueError("pad_shape smaller than the image")
+        B = len(frames)
+        table = upload_tile_rows(frames, rects, row_start, hw, cfg0["to_rgb"], dev)
+        mean = cfg0["mean"].astype(np.float64).astype(np.float32)
+        stdinv = (1.0 / cfg0["std"].astype(np.float64)).astype(np.float32)
+        Hp = max(s["pad_shape"][0] for s in planned)
+        Wp = max(s["pad_shape"][1] for s in planned)
+        out = torch.empty(R, 3, Hp, Wp, dtype=torch.float32, device=dev)
+        K.preprocess_frames(table[B:], R, Hp, Wp, mean, stdinv, out)
+        metas = [{k: s[k] for k in s["_collect"].meta_keys if k in s} for s in planned]
+        return dict(img=out, img_metas=metas, rects=rects, edges=edges, row_start=row_start, table=table, frames=frames,
+                    edge_margin=spec.edge_margin, batch=spec.batch, nms_pre=spec.nms_pre)
 
     def _run_frames(self, planned, collate):
         """device part of a batch of planned frames (LoadImageFromWebcam): the descriptor table and the host frames go up

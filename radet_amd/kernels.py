@@ -1917,6 +1917,50 @@ def merge_views(desc_host, desc, V, B, pool_boxes, pool_scores, pool_ctr, pool_l
               _ptr(out_ctr), _ptr(out_labels), _ptr(out_count), _stream())
 
 
+# ---------------------------------------------------------------------- tiled inference (csrc/tiles.hip)
+TILE_MAX_ROWS = 64                 # include/radet_hip.h
+TILE_DESC_INTS = 11                # {h, w, sx, sy, sx, sy, x0, y0 (f32 bits), edge mask, start, cap}
+TILE_EDGE_L, TILE_EDGE_T, TILE_EDGE_R, TILE_EDGE_B = 1, 2, 4, 8
+
+
+def tile_desc_rows(hw, sf, offsets, edges, starts, caps):
+    """the descriptor rows of radet_merge_tiles for R rows, image-major: hw [R, 2] the rows' img_shape, sf [R, 4] their scale
+    factors, offsets [R, 2] (x0, y0) of the row's source rectangle in its frame, edges [R] TILE_EDGE_* masks, starts / caps [R]
+    in candidates.  Host arithmetic only."""
+    import numpy as np
+    R = len(edges)
+    rows = np.zeros((R, TILE_DESC_INTS), np.int32)
+    rows[:, 0:2] = np.asarray(hw, np.float32).reshape(R, 2).view(np.int32)
+    rows[:, 2:6] = np.asarray(sf, np.float32).reshape(R, 4).view(np.int32)
+    rows[:, 6:8] = np.asarray(offsets, np.float32).reshape(R, 2).view(np.int32)
+    rows[:, 8], rows[:, 9], rows[:, 10] = edges, starts, caps
+    return rows
+
+
+def merge_tiles(desc_host, desc, row_start_host, row_start, B, pool_boxes, pool_scores, pool_ctr, pool_labels, counts,
+                edge_margin, cap_out, out_boxes, out_scores, out_ctr, out_labels, out_count, out_dropped):
+    """the candidates of a tiled batch's rows filtered at the tile borders, back in the frame and packed per image
+    (include/radet_hip.h, radet_merge_tiles).  desc_host: i32 ndarray [R, TILE_DESC_INTS] and row_start_host: i32 ndarray
+    [B + 1], read during the call (the argument checks); desc, row_start: the same words on the device.  The pool is flat:
+    boxes f32 [pool, 4], the others [pool]."""
+    import numpy as np
+    for a in (desc_host, row_start_host):
+        assert isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous
+    assert row_start_host.size == B + 1 and row_start.dtype == torch.int32 and row_start.numel() >= B + 1
+    R = int(row_start_host[B]) if B else 0
+    assert 0 <= R and desc_host.size == R * TILE_DESC_INTS and desc.dtype == torch.int32 and desc.numel() >= desc_host.size
+    pool = int(pool_scores.numel())
+    assert pool_boxes.dtype == torch.float32 and pool_boxes.numel() == 4 * pool and pool_ctr.numel() == pool
+    assert pool_labels.dtype == torch.int64 and pool_labels.numel() == pool and counts.dtype == torch.int32 and counts.numel() >= R
+    assert out_boxes.numel() >= B * cap_out * 4 and min(out_scores.numel(), out_ctr.numel(), out_labels.numel()) >= B * cap_out
+    assert out_labels.dtype == torch.int64 and out_count.dtype == torch.int32 and out_dropped.dtype == torch.int32
+    assert min(out_count.numel(), out_dropped.numel()) >= B
+    _lib.call("radet_merge_tiles", desc_host.ctypes.data, _ptr(desc), row_start_host.ctypes.data, _ptr(row_start), int(B),
+              C.c_size_t(pool), _ptr(pool_boxes), _ptr(pool_scores), _ptr(pool_ctr), _ptr(pool_labels), _ptr(counts),
+              float(edge_margin), int(cap_out), _ptr(out_boxes), _ptr(out_scores), _ptr(out_ctr), _ptr(out_labels), _ptr(out_count),
+              _ptr(out_dropped), _stream())
+
+
 # ---------------------------------------------------------------------- detections -> RoI crops (csrc/crops.hip)
 CROP_ROW_INTS = 6                  # include/radet_hip.h: {b, j, wx0, wy0, ww, wh}
 CROP_MAX_SIDE = 16384

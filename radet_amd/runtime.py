@@ -1230,6 +1230,9 @@ def _detect_graph(self, img, img_metas, test_cfg, rescale=False, crops=None):
     serving is otherwise bound by the host's launch rate (3.2 ms of Python + ctypes enqueue for ~1.7 ms of GPU work
     at batch 1).  Inputs are copied into the graph's static buffers; results are read back like `detect`.  crops= is refused:
     the frames' addresses change from call to call and a captured launch holds the ones it was captured with."""
+    if isinstance(img_metas, dict) and "row_start" in img_metas:
+        raise NotImplementedError("detect_graph with a tile plan: tiled inference is not captured in a graph (the rows, their "
+                                  "number and the frames' addresses are per call); use detect_tiles / detect_tiles_stream")
     if isinstance(img, (list, tuple)):
         if len(img) != 1:
             raise NotImplementedError(f"detect_graph with {len(img)} views: test-time augmentation is not captured in a graph; "
@@ -1455,6 +1458,148 @@ def _detect_aug_stream(self, batches, test_cfg, crops=None):
 
 DetectorRuntime.detect_aug = _detect_aug
 DetectorRuntime.detect_aug_stream = _detect_aug_stream
+
+
+# ---------------------------------------------------------------------- tiled inference
+def _tile_plan(self, imgs, plan, test_cfg):
+    """Host part of detect_tiles, before any launch: the checks, the forward batches, the pool layout and the merge
+    descriptor.  plan: what ImagePipeline.run_tile_rows returns (img_metas [R], rects [R, 4], edges [R], row_start [B + 1])
+    with edge_margin, batch and nms_pre beside them (apis.set_tiling's).
+    -> dict(B, R, nlvl, nms_pre, cap, cap_out, pool, batches [(first row, rows)], desc, row_start (ndarrays), hw, margin)"""
+    R = int(imgs.shape[0])
+    row_start = np.ascontiguousarray(plan["row_start"], dtype=np.int32)
+    B = len(row_start) - 1
+    metas = plan["img_metas"]
+    if B < 1 or R < 1 or int(row_start[0]) != 0 or int(row_start[-1]) != R or len(metas) != R or len(plan["rects"]) != R \
+            or len(plan["edges"]) != R:
+        raise ValueError(f"detect_tiles: {R} rows with row_start {row_start.tolist()}, {len(metas)} metas, {len(plan['rects'])} "
+                         f"rectangles and {len(plan['edges'])} edge masks")
+    rows_b = np.diff(row_start)
+    if rows_b.min() < 1 or rows_b.max() > K.TILE_MAX_ROWS:
+        raise NotImplementedError(f"detect_tiles: {int(rows_b.max())} rows for one frame (1..{K.TILE_MAX_ROWS}): enlarge the tile")
+    batch = int(plan.get("batch") or 16)
+    margin = float(plan.get("edge_margin") or 0.0)
+    if batch < 1 or not np.isfinite(margin) or margin < 0:
+        raise ValueError(f"detect_tiles: batch={batch}, edge_margin={margin}")
+    nlvl = len(self.engine.strides)
+    nms_pre = plan.get("nms_pre")
+    nms_pre = int(nms_pre) if nms_pre else _nms_pre(self, test_cfg, _level_hw(int(imgs.shape[2]), int(imgs.shape[3])))
+    cap = nlvl * nms_pre
+    cap_out = int(rows_b.max()) * cap
+    if cap_out > 65536:
+        raise NotImplementedError(f"tiled inference with {int(rows_b.max())} rows for a frame, nlvl={nlvl} levels and nms_pre="
+                                  f"{nms_pre}: the merged list of {cap_out} candidates per image exceeds the NMS kernel's 65536 "
+                                  f"(16-bit positions); lower nms_pre (set_tiling(..., nms_pre=...)) or enlarge the tile")
+    pool = R * cap
+    if pool >= 2 ** 31:
+        raise NotImplementedError(f"tiled inference: a candidate pool of {pool} entries ({R} rows); lower nms_pre or the batch")
+    hw = np.array([m["img_shape"][:2] for m in metas], np.float32).reshape(R, 2)
+    sf = np.stack([np.asarray(m["scale_factor"], np.float32).reshape(4) for m in metas])
+    rects = np.asarray(plan["rects"], np.int64).reshape(R, 4)
+    desc = K.tile_desc_rows(hw, sf, rects[:, 0:2], np.asarray(plan["edges"], np.int32), np.arange(R, dtype=np.int64) * cap,
+                            np.full(R, cap, np.int32))
+    return dict(B=B, R=R, nlvl=nlvl, nms_pre=nms_pre, cap=cap, cap_out=cap_out, pool=pool, desc=desc, row_start=row_start,
+                batches=[(i0, min(batch, R - i0)) for i0 in range(0, R, batch)], hw=hw, margin=margin, batch=batch)
+
+
+def _tile_launch(self, imgs, tp, test_cfg, upload, counts_out=None):
+    """Device part of detect_tiles on the current stream: the R rows as consecutive forward batches of at most `batch` rows,
+    each followed by one radet_decode_candidates into its block of the pool (row coordinates, clamped to the row's own
+    img_shape -- a box that reaches past a tile lands exactly on its edge); ONE radet_merge_tiles (edge rule, map-back,
+    stable compaction per image); the config's NMS over the merged lists (_nms_launch).  upload: ndarray -> device tensor.
+    Returns the NMS outputs, boxes in the frames' coordinates."""
+    B, R, nlvl, nms_pre, cap, cap_out = tp["B"], tp["R"], tp["nlvl"], tp["nms_pre"], tp["cap"], tp["cap_out"]
+    soft = dict(test_cfg["nms"]).get("type") == "soft_nms"
+    dbytes = max(K.decode_ws_bytes(n, nlvl, nms_pre) for _, n in tp["batches"])
+    key = ("tiles", B, R, cap_out, nms_pre, tp["batch"]) + (("soft",) if soft else ())
+    p = _post_ws(self, key, B, cap_out, soft, dbytes, f"{B} frames as {R} tiled rows, nlvl={nlvl}, nms_pre={nms_pre}",
+                 pool=tp["pool"])
+    if "row_count" not in p:
+        p["row_count"] = torch.zeros(R, dtype=torch.int32, device=self.dev)
+        p["dropped"] = torch.zeros(B, dtype=torch.int32, device=self.dev)
+    hw = upload(tp["hw"])
+    desc = upload(tp["desc"])
+    row_start = upload(tp["row_start"])
+    imgs = imgs.to(self.dev)
+    for i0, n in tp["batches"]:
+        self.forward(imgs[i0:i0 + n])
+        ho = _head_out(self)
+        if ho["B"] != n or ho["nlvl"] != nlvl:
+            raise RuntimeError("detect_tiles: the engine's level geometry differs from the planned one")
+        K.decode_candidates(ho["cls"], ho["reg"], ho["iou"], ho["scales"], ho["ldesc"], nlvl, n, self.num_classes,
+                            float(test_cfg["score_thr"]), nms_pre, hw[i0:i0 + n], None, p["pool_boxes"][i0 * cap:(i0 + n) * cap],
+                            p["pool_scores"][i0 * cap:(i0 + n) * cap], p["pool_ctr"][i0 * cap:(i0 + n) * cap],
+                            p["pool_labels"][i0 * cap:(i0 + n) * cap], p["row_count"][i0:i0 + n], p["dws"])
+    K.merge_tiles(tp["desc"], desc, tp["row_start"], row_start, B, p["pool_boxes"], p["pool_scores"], p["pool_ctr"],
+                  p["pool_labels"], p["row_count"], tp["margin"], cap_out, p["boxes"], p["scores"], p["ctr"], p["labels"],
+                  p["count"], p["dropped"])
+    return _nms_launch(self, p, B, cap_out, test_cfg, counts_out)
+
+
+def _detect_tiles(self, imgs, plan, test_cfg, crops=None):
+    """`detect` over the rows of a tiled batch (imgs f32 [R, 3, Hp, Wp] and plan: ImagePipeline.run_tile_rows' tensor and
+    record, with edge_margin, batch and nms_pre from apis.set_tiling).  Every row -- a frame's full-frame view, then its
+    overlapping tiles -- runs at the network's resolution; the union handed to the NMS holds the candidates the single-view
+    path would hand its NMS for each row (score_thr, the top nms_pre per level and row), minus those that touch a side of
+    their tile that cuts through the frame (radet_merge_tiles' edge rule: the object continues beyond the tile, and a
+    neighbouring tile or the full-frame row sees it whole), mapped back to the frame and concatenated in row order; then the
+    config's own NMS (vote / global_vote / nms / soft_nms) and max_per_img, once per frame.  This composition is this
+    project's rule: the reference has no tiled inference.  Results are in the frames' coordinates (there is no
+    rescale=False).  crops = (CropSpec, descriptor table whose first B rows are the source frames), as in `detect_aug`.
+    Returns what `detect` returns, one entry per FRAME."""
+    with torch.no_grad():
+        tp = _tile_plan(self, imgs, plan, test_cfg)
+        B = tp["B"]
+
+        def upload(a):
+            return torch.from_numpy(a).to(self.dev)
+        counts = None if crops is None else _crop_counts(self, B)
+        outs = _tile_launch(self, imgs, tp, test_cfg, upload, counts_out=counts)
+        if crops is None:
+            return _post_collect(self, *outs)
+        job = _crops_launch(self, outs, counts, crops)
+        host = counts.cpu().numpy()
+        return (_post_collect(self, *outs, counts=host),) + _crops_collect(job, host, B)
+
+
+def _detect_tiles_stream(self, batches, test_cfg, crops=None):
+    """`detect_tiles` over an iterable of tiled batches (imgs, plan) with the host one batch behind the device: batch k + 1's
+    device program is enqueued before the host waits for batch k's counts, which arrive through a pinned copy behind an
+    event, as in detect_aug_stream; everything runs on the caller's stream.  crops: an ops.crops.CropSpec; the crops are cut
+    from the batch's frames (plan['table'], whose first B rows are the source frames) behind its NMS.  Yields what
+    detect_tiles returns, in order."""
+    def upload(a):
+        return torch.from_numpy(a).pin_memory().to(self.dev, non_blocking=True)
+
+    def collect(rec):
+        outs, done, pinned, B, job = rec[:5]    # (the rest keeps the batch's rows, table and frames alive until here)
+        done.synchronize()                      # the host waits for THIS batch only
+        host = pinned.numpy()
+        dets = _post_collect(self, *outs, counts=host)
+        return dets if crops is None else (dets,) + _crops_collect(job, host, B)
+
+    prev = None
+    with torch.no_grad():
+        for imgs, plan in batches:
+            tp = _tile_plan(self, imgs, plan, test_cfg)
+            B = tp["B"]
+            counts = torch.zeros(B, dtype=torch.int32, device=self.dev) if crops is None else _crop_counts(self, B)
+            outs = _tile_launch(self, imgs, tp, test_cfg, upload, counts_out=counts)
+            job = None if crops is None else _crops_launch(self, outs, counts, (crops, plan["table"]))
+            pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
+            pinned.copy_(counts, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            rec = (outs, done, pinned, B, job, plan, imgs)
+            if prev is not None:
+                yield collect(prev)
+            prev = rec
+        if prev is not None:
+            yield collect(prev)
+
+
+DetectorRuntime.detect_tiles = _detect_tiles
+DetectorRuntime.detect_tiles_stream = _detect_tiles_stream
 
 
 def _rows_to_nchw(self, rows, levels, ch):

@@ -20,6 +20,14 @@ beside the same launch without flips.  The single-view call's launch sequence is
 compared with the commit before.
 
     python tools/bench_frames.py --tta [--batch 4] [--iters 20] [--reps 7]
+
+--tiles times tiled inference instead and writes profiles/bench_tiles.json: `inference_detector(frame)` on one 1080 x 1920
+frame with set_tiling(tile=(640, 480), overlap=0.25): 12 tiles + the full frame, one forward batch of 13, one merge, one NMS,
+against `inference_detector` on the 13 copied slices as one batch (what the code could do without tiling: 13 separate
+results in tile coordinates), in alternating rounds; and, between HIP events, radet_merge_tiles on synthetic pools of 8 images
+x 13 and x 64 rows x cap 1000 at 30 % and full fill, beside radet_merge_views on the same candidate volume where it can take it.
+
+    python tools/bench_frames.py --tiles [--iters 5] [--reps 5]
 """
 import argparse
 import json
@@ -175,6 +183,103 @@ def tta_main(args):
     print(json.dumps(out))
 
 
+def tiles_main(args):
+    from radet_amd import kernels as K
+    from radet_amd.apis import inference_detector, set_tiling
+    from radet_amd.models import build_detector
+    from radet_amd.ops.tiles import tile_rows
+    from radet_amd.utils import Config
+    from radet_amd.utils.synth_init import synth_fill
+    dev = torch.device("cuda")
+    rng = np.random.RandomState(0)
+    frame = rng.randint(0, 256, (1080, 1920, 3)).astype(np.uint8)
+    tiling = dict(tile=(640, 480), overlap=0.25, full_frame=True, batch=16)
+    rects, _, row_start = tile_rows([frame.shape[:2]], tiling)
+    slices = [np.ascontiguousarray(frame[y0:y0 + th, x0:x0 + tw]) for x0, y0, tw, th in rects.tolist()]
+    cfg = Config.fromfile(os.path.join(ROOT, "configs", "bop", "r50_ycbv_pbr.py"))
+    cfg.model["pretrained"] = None
+    torch.manual_seed(0)
+    model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).to(dev).eval()
+    synth_fill(model, seed=0)
+    with torch.no_grad():
+        model.bbox_head.atss_cls.bias += 2.0                        # (candidates above the threshold: full lists)
+    model.cfg = Config(dict(data=dict(test=dict(pipeline=pipeline_cfg("LoadImageFromFile")))))
+
+    def tiled_call():
+        set_tiling(model, tiling)
+        try:
+            return inference_detector(model, frame)
+        finally:
+            set_tiling(model, None)
+    paths = dict(tiled=tiled_call, slices_one_batch=lambda: inference_detector(model, slices))
+    for fn in paths.values():
+        wall_ms(fn, 3)
+    tiled_log = log_calls(paths["tiled"])
+    rounds = {k: [] for k in paths}
+    for _ in range(args.reps):
+        for k, fn in paths.items():                                 # alternating: drift hits both alike
+            rounds[k].append(wall_ms(fn, args.iters))
+    row_counts = next(v for k, v in model.runtime()._posts.items() if k[0] == "tiles")["row_count"].cpu().tolist()
+
+    # the merge launch alone on synthetic pools: B images x rows x cap, every row filled to `fill` of its cap, a quarter of
+    # the candidates on a cut edge; radet_merge_views beside it on the same candidate volume (it takes at most 16 views)
+    def pool_case(B, rows, cap, fill):
+        Rn, n = B * rows, B * rows * cap
+        g = torch.Generator(device="cpu").manual_seed(1)
+        lo = torch.rand(n, 2, generator=g) * 200 + 1
+        boxes = torch.cat([lo, lo + 50 + torch.rand(n, 2, generator=g) * 100], 1)
+        boxes[::4, 2] = 640.0
+        p = dict(boxes=boxes.to(dev), scores=torch.rand(n, generator=g).to(dev), ctr=torch.rand(n, generator=g).to(dev),
+                 labels=torch.zeros(n, dtype=torch.long, device=dev),
+                 counts=torch.full((Rn,), int(fill * cap), dtype=torch.int32, device=dev))
+        cap_out = rows * cap
+        outs = (torch.empty(B, cap_out, 4, device=dev), torch.empty(B, cap_out, device=dev), torch.empty(B, cap_out, device=dev),
+                torch.empty(B, cap_out, dtype=torch.long, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
+        dropped = torch.zeros(B, dtype=torch.int32, device=dev)
+        hw, sf = np.tile(np.array([[480.0, 640.0]], np.float32), (Rn, 1)), np.full((Rn, 4), 1.5, np.float32)
+        tdesc = K.tile_desc_rows(hw, sf, np.full((Rn, 2), 426.0), np.full(Rn, 15, np.int32), np.arange(Rn) * cap, np.full(Rn, cap))
+        rs = (np.arange(B + 1) * rows).astype(np.int32)
+        tdev, rdev = torch.from_numpy(tdesc).to(dev), torch.from_numpy(rs).to(dev)
+        fns = dict(merge_tiles=lambda: K.merge_tiles(tdesc, tdev, rs, rdev, B, p["boxes"], p["scores"], p["ctr"], p["labels"],
+                                                     p["counts"], 0.0, cap_out, *outs, dropped))
+        if rows <= K.TTA_MAX_VIEWS:
+            vdesc = K.merge_desc_rows(hw, sf, np.zeros(Rn, np.int32), np.arange(Rn) * cap, np.full(Rn, cap))
+            vdev = torch.from_numpy(vdesc).to(dev)
+            fns["merge_views"] = lambda: K.merge_views(vdesc, vdev, rows, B, p["boxes"], p["scores"], p["ctr"], p["labels"],
+                                                       p["counts"], cap_out, *outs)
+        for fn in fns.values():
+            event_ms(fn, 10)
+        r = {k: [] for k in fns}
+        for _ in range(args.reps):
+            for k, fn in fns.items():                               # interleaved launches, medians
+                r[k].append(event_ms(fn, 50))
+        return dict(images=B, rows_per_image=rows, cap=cap, fill=fill, candidates=int(fill * cap) * Rn,
+                    **{k + "_us": statistics.median(v) * 1e3 for k, v in r.items()},
+                    **{k + "_us_band": [x * 1e3 for x in band(v)] for k, v in r.items()},
+                    **{k + "_us_all": [x * 1e3 for x in v] for k, v in r.items()})
+    cases = [pool_case(8, 13, 1000, 0.3), pool_case(8, 13, 1000, 1.0), pool_case(8, 64, 1000, 0.3), pool_case(8, 64, 1000, 1.0)]
+    med = statistics.median
+    out = dict(case=dict(frame_hw=[1080, 1920], tiling=dict(tile=[640, 480], overlap=0.25, full_frame=True, batch=16),
+                         rows=int(row_start[-1]), nms_pre=int(model.test_cfg["nms_pre"]), candidates_per_row=[min(row_counts), max(row_counts)],
+                         iters=args.iters, reps=args.reps),
+               device=torch.cuda.get_device_name(0), clocks="default governor, not pinned; medians of alternating rounds",
+               yardstick="inference_detector on the 13 copied slices as ONE batch, same process: what the commit before can do for "
+                         "the same rows (13 separate results in tile coordinates, no merge)",
+               tiled_call_ms=med(rounds["tiled"]), slices_one_batch_ms=med(rounds["slices_one_batch"]),
+               tiled_over_yardstick=med(rounds["tiled"]) / med(rounds["slices_one_batch"]),
+               tiled_call_ms_band=band(rounds["tiled"]), slices_one_batch_ms_band=band(rounds["slices_one_batch"]),
+               tiled_call_ms_all=rounds["tiled"], slices_one_batch_ms_all=rounds["slices_one_batch"],
+               tiled_launches=len(tiled_log),
+               tiled_launch_counts={n: tiled_log.count(n) for n in ("radet_preprocess_frames", "radet_decode_candidates",
+                                                                    "radet_merge_tiles", "radet_nms")},
+               merge_launch=cases)
+    path = args.out or os.path.join(ROOT, "profiles", "bench_tiles.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -182,12 +287,16 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--frames", type=int, default=400, help="frames of the end-to-end pass")
     ap.add_argument("--tta", action="store_true", help="time test-time augmentation instead -> profiles/bench_tta.json")
-    ap.add_argument("--out", default=None, help="default: profiles/bench_frames.json (profiles/bench_tta.json with --tta)")
+    ap.add_argument("--tiles", action="store_true", help="time tiled inference instead -> profiles/bench_tiles.json")
+    ap.add_argument("--out", default=None, help="default: profiles/bench_frames.json (profiles/bench_tta.json with --tta, "
+                                                "profiles/bench_tiles.json with --tiles)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frames.py measures on the GPU: no device found")
     if args.tta:
         return tta_main(args)
+    if args.tiles:
+        return tiles_main(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "bench_frames.json")
     from radet_amd.apis import detect_frames
     from radet_amd.datasets.loading import ImagePipeline
