@@ -1,6 +1,8 @@
 """init_detector / inference_detector with the reference's signatures (radet/apis/inference.py), for inputs that are
 already normalised NCHW tensors, for image files, and for frames in memory (ndarray or device tensor HxWx3 uint8 BGR), which
 go through the config's test pipeline as in the reference; detect_frames streams an iterable of frames through it."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -109,35 +111,25 @@ def _tile_pipeline(model):
     return pipeline
 
 
-def _refuse_untiled(imgs):
-    """with tiling set, inference_detector takes loaded frames only"""
-    if isinstance(imgs, str) or (isinstance(imgs, (list, tuple)) and any(isinstance(i, str) for i in imgs)):
-        raise NotImplementedError("inference_detector on file names with set_tiling(model, ...): tiled inference is built for "
-                                  "frames in memory; load the images (mmcv.imread order: HxWx3 uint8 BGR) and pass them")
-    if not (_is_frame(imgs) or (isinstance(imgs, (list, tuple)) and all(_is_frame(i) for i in imgs))):
-        raise NotImplementedError("inference_detector on a normalised NCHW tensor with set_tiling(model, ...): tiles are cut "
-                                  "from loaded frames (ndarray or uint8 tensor HxWx3 BGR) in front of the test pipeline; pass "
-                                  "the frames, or clear the tiling (set_tiling(model, None))")
+# with set_tiling or set_tta, inference_detector takes loaded frames only: what the mode is called, and how anything that is
+# neither a frame nor a file name is refused
+_FRAMES_ONLY = dict(
+    set_tiling=("tiled inference", NotImplementedError,
+                "inference_detector on a normalised NCHW tensor with set_tiling(model, ...): tiles are cut from loaded frames "
+                "(ndarray or uint8 tensor HxWx3 BGR) in front of the test pipeline; pass the frames, or clear the tiling "
+                "(set_tiling(model, None))"),
+    set_tta=("test-time augmentation", ValueError,
+             "inference_detector with set_tta(model, ...) takes loaded frames (ndarray or uint8 tensor HxWx3 BGR)"))
 
 
-def _inference_tiles(model, frames, crops=None):
-    pipeline = _tile_pipeline(model)
-    if crops is None and not frames:
-        return []
-    spec = None
-    if crops is not None:
-        from ..ops.crops import check_frames
-        check_frames(frames)
-        spec = _crop_request(model, crops)
-    plan = pipeline.run_tile_rows(frames, model.tiling)
-    if model.training:
-        model.eval()
-    num_classes = model.bbox_head.num_classes
-    if spec is None:
-        dets = model.runtime().detect_tiles(plan["img"], plan, model.test_cfg)
-        return [bbox2result(b, l, num_classes) for b, l in dets]
-    dets, out, _ = model.runtime().detect_tiles(plan["img"], plan, model.test_cfg, crops=(spec, plan["table"]))
-    return [bbox2result(b, l, num_classes) for b, l in dets], out
+def _loaded_frames_only(imgs, setter):
+    what, error, message = _FRAMES_ONLY[setter]
+    listed = isinstance(imgs, (list, tuple))
+    if isinstance(imgs, str) or (listed and any(isinstance(i, str) for i in imgs)):
+        raise NotImplementedError(f"inference_detector on file names with {setter}(model, ...): {what} is built for frames in "
+                                  "memory; load the images (mmcv.imread order: HxWx3 uint8 BGR) and pass them")
+    if not (_is_frame(imgs) or (listed and all(_is_frame(i) for i in imgs))):
+        raise error(message)
 
 
 def _frame_pipeline(model, tta=None):
@@ -210,27 +202,66 @@ def _single_view(data):
     return imgs, metas
 
 
+_Mode = namedtuple("_Mode", "prepare table one_shot stream module_call")
+
+
+def _frame_mode(model):
+    """How this model's calls on loaded frames run -- tiles (set_tiling), views (a set_tta override, or a config whose
+    MultiScaleFlipAug makes several) or a single view -- chosen once per call; refuses what does not compose.
+    -> prepare(group of frames, with_source) -> the batch as the runtime's stream takes it (with_source: the descriptor table
+    and the frames ride along for the crops; views and tiles always carry them), table(batch) -> that table (its first B rows:
+    the source frames), one_shot(runtime, batch, crops) -> what DetectorRuntime.detect returns (crops: None or (CropSpec,
+    table)), stream(runtime, batches, spec) -> the runtime's generator (spec: None or the CropSpec), module_call: without
+    crops the one-shot is the module's own forward call (simple_test / aug_test), as for a normalised tensor."""
+    tiling = getattr(model, "tiling", None)
+    if tiling is not None:
+        pipeline = _tile_pipeline(model)
+
+        def prepare(group, with_source):
+            plan = pipeline.run_tile_rows(group, tiling)
+            return plan["img"], plan
+        return _Mode(prepare, lambda b: b[1]["table"], lambda rt, b, crops: rt.detect_tiles(b[0], b[1], model.test_cfg, crops=crops),
+                     lambda rt, batches, spec: rt.detect_tiles_stream(batches, model.test_cfg, crops=spec), False)
+    pipeline = _frame_pipeline(model, getattr(model, "tta", None))
+    if pipeline.views > 1:
+        def prepare(group, with_source):
+            data, source = _prepare_frames(pipeline, group, True)
+            return data["img"], data["img_metas"], source
+        return _Mode(prepare, lambda b: b[2][0], lambda rt, b, crops: rt.detect_aug(b[0], b[1], model.test_cfg, True, crops=crops),
+                     lambda rt, batches, spec: rt.detect_aug_stream(batches, model.test_cfg, crops=spec), True)
+
+    def prepare(group, with_source):
+        if not with_source:
+            return _single_view(_prepare_frames(pipeline, group))
+        data, source = _prepare_frames(pipeline, group, True)
+        return _single_view(data) + (source,)
+    return _Mode(prepare, lambda b: b[2][0], lambda rt, b, crops: rt.detect(b[0], b[1], model.test_cfg, True, crops=crops),
+                 lambda rt, batches, spec: rt.detect_stream(batches, model.test_cfg, rescale=True,
+                                                            **({} if spec is None else dict(crops=spec))), True)
+
+
 def _inference_frames(model, frames, crops=None):
-    tta = getattr(model, "tta", None)
-    if crops is None:
-        if not frames:
-            return []
+    """one batch of loaded frames -> their results, or with crops= (results, Crops of the batch)"""
+    spec = None
+    if crops is not None:
+        from ..ops.crops import check_frames
+        check_frames(frames)
+        spec = _crop_request(model, crops)
+    mode = _frame_mode(model)
+    if spec is None and not frames:
+        return []
+    batch = mode.prepare(frames, spec is not None)
+    if spec is None and mode.module_call:
+        imgs, metas = batch[:2]
+        if not isinstance(imgs, (list, tuple)):
+            imgs, metas = [imgs], [metas]
         with torch.no_grad():
-            return model(return_loss=False, rescale=True, **_prepare_frames(_frame_pipeline(model, tta), frames))
-    from ..ops.crops import check_frames
-    check_frames(frames)
-    spec = _crop_request(model, crops)
-    pipeline = _frame_pipeline(model, tta)
-    data, source = _prepare_frames(pipeline, frames, True)
+            return model(img=imgs, img_metas=metas, return_loss=False, rescale=True)
     if model.training:
         model.eval()
-    if pipeline.views > 1:                                   # (the table's first B rows describe the source frames)
-        dets, out, _ = model.runtime().detect_aug(data["img"], data["img_metas"], model.test_cfg, True, crops=(spec, source[0]))
-    else:
-        imgs, metas = _single_view(data)
-        dets, out, _ = model.runtime().detect(imgs, metas, model.test_cfg, True, crops=(spec, source[0]))
-    del source                                               # (detect has waited for the batch: the frames' table can go)
-    return [bbox2result(b, l, model.bbox_head.num_classes) for b, l in dets], out
+    out = mode.one_shot(model.runtime(), batch, None if spec is None else (spec, mode.table(batch)))
+    results = [bbox2result(b, l, model.bbox_head.num_classes) for b, l in (out if spec is None else out[0])]
+    return results if spec is None else (results, out[1])
 
 
 def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
@@ -249,8 +280,7 @@ def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
     from ..ops.crops import check_frames, split_crops
     if batch_size < 1:
         raise ValueError(f"batch_size={batch_size}")
-    tiling = getattr(model, "tiling", None)
-    pipeline = _tile_pipeline(model) if tiling is not None else _frame_pipeline(model, getattr(model, "tta", None))
+    mode = _frame_mode(model)
     spec = None if crops is None else _crop_request(model, crops)
     if model.training:
         model.eval()
@@ -268,31 +298,11 @@ def detect_frames(model, frames, batch_size=8, on_device=False, crops=None):
 
     def prepared():
         for group in batches():
-            if tiling is not None:                               # (the plan carries the table and the frames with the batch)
-                if spec is not None:
-                    check_frames(group)
-                plan = pipeline.run_tile_rows(group, tiling)
-                yield plan["img"], plan
-                continue
-            if pipeline.views > 1:
-                if spec is not None:
-                    check_frames(group)
-                data, source = _prepare_frames(pipeline, group, True)
-                yield data["img"], data["img_metas"], source
-                continue
-            if spec is None:
-                yield _single_view(_prepare_frames(pipeline, group))
-                continue
-            check_frames(group)
-            data, source = _prepare_frames(pipeline, group, True)
-            yield _single_view(data) + (source,)             # (the stream carries the table and the frames with the batch)
+            if spec is not None:
+                check_frames(group)
+            yield mode.prepare(group, spec is not None)      # (the stream carries the table and the frames with the batch)
 
-    if tiling is not None:
-        stream = model.runtime().detect_tiles_stream(prepared(), model.test_cfg, crops=spec)
-    elif pipeline.views > 1:
-        stream = model.runtime().detect_aug_stream(prepared(), model.test_cfg, crops=spec)
-    else:
-        stream = model.runtime().detect_stream(prepared(), model.test_cfg, rescale=True, **({} if spec is None else dict(crops=spec)))
+    stream = mode.stream(model.runtime(), prepared(), spec)
     try:
         for dets in stream:
             per_frame = None
@@ -328,26 +338,15 @@ def inference_detector(model, imgs, scale_factor=None, crops=None):
     Tiled inference, with loaded frames only: after set_tiling(model, dict(tile=(tw, th), ...)) every frame runs as its
     full-frame view plus overlapping tiles at the network's resolution, merged by one NMS per frame
     (DetectorRuntime.detect_tiles); results and crops= stay in the frames' coordinates."""
-    tta = getattr(model, "tta", None)
-    if getattr(model, "tiling", None) is not None:
-        if tta is not None:
-            _tile_pipeline(model)                                # (refuses: tiling together with a set_tta override)
-        _refuse_untiled(imgs)
+    tiling, tta = getattr(model, "tiling", None), getattr(model, "tta", None)
+    if tiling is not None and tta is not None:
+        _tile_pipeline(model)                                    # (refuses: tiling together with a set_tta override)
+    if tiling is not None or tta is not None:
+        _loaded_frames_only(imgs, "set_tiling" if tiling is not None else "set_tta")
+    if crops is not None or tiling is not None:
         if _is_frame(imgs):
-            res = _inference_tiles(model, [imgs], crops)
+            res = _inference_frames(model, [imgs], crops)
             return res[0] if crops is None else (res[0][0], res[1])
-        return _inference_tiles(model, list(imgs), crops)
-    if tta is not None:
-        names = isinstance(imgs, str) or (isinstance(imgs, (list, tuple)) and any(isinstance(i, str) for i in imgs))
-        if names:
-            raise NotImplementedError("inference_detector on file names with set_tta(model, ...): test-time augmentation is built for frames in "
-                                      "memory; load the images (mmcv.imread order: HxWx3 uint8 BGR) and pass them")
-        if not (_is_frame(imgs) or (isinstance(imgs, (list, tuple)) and all(_is_frame(i) for i in imgs))):
-            raise ValueError("inference_detector with set_tta(model, ...) takes loaded frames (ndarray or uint8 tensor HxWx3 BGR)")
-    if crops is not None:
-        if _is_frame(imgs):
-            res, out = _inference_frames(model, [imgs], crops)
-            return res[0], out
         return _inference_frames(model, list(imgs) if isinstance(imgs, (list, tuple)) else imgs, crops)
     if isinstance(imgs, str):
         return _inference_files(model, [imgs])[0]

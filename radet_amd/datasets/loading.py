@@ -1206,22 +1206,31 @@ def frame_desc_rows(frames, dst_hw, to_rgb, host_base, views=1, flips=None):
     return rows, offs, o
 
 
-def upload_frames(frames, dst_hw, to_rgb, dev, views=1, flips=None):
-    """[descriptor table | host frames, packed] into one device buffer in ONE pinned, non-blocking copy (the table needs the
-    buffer's address, so the buffer is allocated first); frames that are device tensors are not copied, the table holds their
-    addresses.  Returns the table, i32 [views * B, PREP_DESC_INTS]: a view of the buffer, which it keeps alive."""
-    head = views * len(frames) * K.PREP_DESC_INTS * 4
-    _, _, nbytes = frame_desc_rows(frames, dst_hw, to_rgb, 0, views, flips)
+def _upload_tables(frames, n_rows, build, dev):
+    """[descriptor table of n_rows rows | host frames, packed, each once] into one device buffer in ONE pinned, non-blocking
+    copy.  The table needs the buffer's address, so the buffer is allocated first (the host frames' bytes are known from their
+    shapes) and build(address of the buffer's pixel part) -> (table i32 [n_rows, PREP_DESC_INTS], byte offset per frame or
+    None, bytes of the pixel part) writes the rows against it; frames that are device tensors are not copied, the table holds
+    their addresses.  Returns the table as i32 [n_rows * PREP_DESC_INTS]: a view of the buffer, which it keeps alive."""
+    head = n_rows * K.PREP_DESC_INTS * 4
+    nbytes = sum(f.size for f in frames if isinstance(f, np.ndarray))
     up = torch.empty(head + nbytes, dtype=torch.uint8, device=dev)
-    rows, offs, _ = frame_desc_rows(frames, dst_hw, to_rgb, up.data_ptr() + head, views, flips)
+    table, offs, packed = build(up.data_ptr() + head)
+    if packed != nbytes or table.size * 4 != head:
+        raise RuntimeError(f"upload: a table of {table.size * 4} bytes and {packed} bytes of frames for {head} + {nbytes}")
     stage = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=True)
     host = stage.numpy()
-    host[:head] = rows.reshape(-1).view(np.uint8)
+    host[:head] = table.reshape(-1).view(np.uint8)
     for f, o in zip(frames, offs):
         if o is not None:
             np.copyto(host[head + o:head + o + f.size].reshape(f.shape), f)
     up.copy_(stage, non_blocking=True)
     return up[:head].view(torch.int32)
+
+
+def upload_frames(frames, dst_hw, to_rgb, dev, views=1, flips=None):
+    """_upload_tables for a plain batch: the table of frame_desc_rows.  Returns it flat, i32 [views * B * PREP_DESC_INTS]."""
+    return _upload_tables(frames, views * len(frames), lambda base: frame_desc_rows(frames, dst_hw, to_rgb, base, views, flips), dev)
 
 
 def tile_desc_rows(frames, rects, row_start, dst_hw, to_rgb, host_base):
@@ -1258,18 +1267,11 @@ def upload_tile_rows(frames, rects, row_start, dst_hw, to_rgb, dev):
     non-blocking copy, as upload_frames does for a plain batch.  Returns (table i32 [B + R, PREP_DESC_INTS]: a view of the
     buffer, which it keeps alive; its first B rows are what crops= reads, the rows' table starts at row B)."""
     B, R = len(frames), len(rects)
-    head = (B + R) * K.PREP_DESC_INTS * 4
-    _, _, _, nbytes = tile_desc_rows(frames, rects, row_start, dst_hw, to_rgb, 0)
-    up = torch.empty(head + nbytes, dtype=torch.uint8, device=dev)
-    src, rows, offs, _ = tile_desc_rows(frames, rects, row_start, dst_hw, to_rgb, up.data_ptr() + head)
-    stage = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=True)
-    host = stage.numpy()
-    host[:head] = np.concatenate([src, rows]).reshape(-1).view(np.uint8)
-    for f, o in zip(frames, offs):
-        if o is not None:
-            np.copyto(host[head + o:head + o + f.size].reshape(f.shape), f)
-    up.copy_(stage, non_blocking=True)
-    return up[:head].view(torch.int32).view(B + R, K.PREP_DESC_INTS)
+
+    def build(base):
+        src, rows, offs, nbytes = tile_desc_rows(frames, rects, row_start, dst_hw, to_rgb, base)
+        return np.concatenate([src, rows]), offs, nbytes
+    return _upload_tables(frames, B + R, build, dev).view(B + R, K.PREP_DESC_INTS)
 
 
 class ImagePipeline:

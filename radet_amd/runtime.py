@@ -942,37 +942,75 @@ def _detect(self, img, img_metas, test_cfg, rescale=False, crops=None):
     with torch.no_grad():
         self.forward(img.to(self.dev))
         hw, sf = _meta_tensors(self, img_metas, rescale)
-        if crops is None:
-            return _post_collect(self, *_post_launch(self, hw, sf, test_cfg))
-        counts = _crop_counts(self, len(img_metas))
-        outs = _post_launch(self, hw, sf, test_cfg, counts_out=counts)
-        job = _crops_launch(self, outs, counts, crops)
-        host = counts.cpu().numpy()
-        return (_post_collect(self, *outs, counts=host),) + _crops_collect(job, host, len(img_metas))
+        B = len(img_metas)
+        outs, counts, job = _launch_with_crops(self, B, crops, lambda c: _post_launch(self, hw, sf, test_cfg, counts_out=c))
+        return _finish(self, outs, job, B, counts.cpu().numpy())
 
 
-def _crop_counts(self, B):
-    """the detection counts of a batch with crops: i32 [B + 2 + B] = counts [B] | the plan's counters: n_out | n_total | where
-    each frame's rows end [B], so that one device-to-host copy brings all the host needs to hand the crops out per frame"""
-    return torch.zeros(B + 2 + B, dtype=torch.int32, device=self.dev)
-
-
-def _crops_launch(self, outs, counts, crops):
-    """the two crop launches behind _post_launch, on the current stream; crops = (CropSpec, descriptor table)"""
+def _launch_with_crops(self, B, crops, launch):
+    """launch(counts_out) -> the NMS outputs of a batch of B images, and with crops = (CropSpec, descriptor table) the two crop
+    launches behind it on the current stream.  -> (outs, counts, job): counts is what the host needs of the batch in ONE
+    device-to-host copy -- the detection counts [B], with crops followed by the crop plan's counters: n_out | n_total | where
+    each frame's rows end [B]; job: the crops' (images, rows), or None"""
+    if crops is None:
+        outs = launch(None)
+        return outs, outs[3], None
     from .ops.crops import launch_crops
     spec, desc = crops
+    counts = torch.zeros(B + 2 + B, dtype=torch.int32, device=self.dev)
+    outs = launch(counts)
     ob, osc, _, oc = outs
-    B, k = int(ob.shape[0]), int(ob.shape[1])
+    k = int(ob.shape[1])
     cap = spec.max_crops if spec.max_crops is not None else B * k
     if cap > K.CROP_MAX_SLOTS:
         raise ValueError(f"crops: {B} x {k} detection slots exceed the kernel's {K.CROP_MAX_SLOTS}; pass max_crops")
-    return launch_crops(spec, ob, osc, oc, desc, cap, counts[B:])
+    return outs, counts, launch_crops(spec, ob, osc, oc, desc, cap, counts[B:])
 
 
-def _crops_collect(job, host_counts, B):
-    """host_counts: _crop_counts' words on the host -> (Crops of the batch, ends [B])"""
+def _finish(self, outs, job, B, host):
+    """what a batch returns, from _launch_with_crops' outs and job and its counts on the host: the detections, or with crops
+    (detections, Crops of the batch, ends [B])"""
+    dets = _post_collect(self, *outs, counts=host)
+    if job is None:
+        return dets
     from .ops.crops import collect_crops
-    return collect_crops(job[0], job[1], host_counts[B], host_counts[B + 1]), host_counts[B + 2:B + 2 + B].copy()
+    return dets, collect_crops(job[0], job[1], host[B], host[B + 1]), host[B + 2:B + 2 + B].copy()
+
+
+def _uploader(self, pinned):
+    """ndarray -> device tensor: a blocking copy, or (pinned) through pinned memory without one, for the streams"""
+    if pinned:
+        return lambda a: torch.from_numpy(a).pin_memory().to(self.dev, non_blocking=True)
+    return lambda a: torch.from_numpy(a).to(self.dev)
+
+
+def _one_behind(self, batches, enqueue):
+    """The loop of the three streams, the host one batch behind the device: enqueue(batch, fetch) puts a batch's whole device
+    program on its streams and calls fetch(counts) where the counts are made -- the counts into pinned memory and the
+    "arrived" event, on the current stream -- and returns (outs, job, B, pinned, done, whatever has to stay alive until the
+    host has waited for the batch).  Batch k is handed out (_finish) once batch k + 1 is enqueued; the host waits for that
+    batch's event only."""
+    def fetch(counts):
+        pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
+        pinned.copy_(counts, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        return pinned, done
+
+    def collect(rec):
+        outs, job, B, pinned, done = rec[:5]
+        done.synchronize()                                      # the host waits for THIS batch only
+        return _finish(self, outs, job, B, pinned.numpy())
+
+    prev = None
+    with torch.no_grad():
+        for batch in batches:
+            rec = enqueue(batch, fetch)
+            if prev is not None:
+                yield collect(prev)
+            prev = rec
+        if prev is not None:
+            yield collect(prev)
 
 
 def _detect_stream(self, batches, test_cfg, rescale=False, crops=None):
@@ -997,89 +1035,55 @@ def _detect_stream(self, batches, test_cfg, rescale=False, crops=None):
     alts = {}                    # id(plan) -> (plan, the other set of head-output buffers)
     post_ev = [None, None]       # events "decode / NMS done" of the batch before last and of the last batch
 
-    def fetch_counts(counts, pinned):   # on the current stream: the detection counts into pinned memory + "arrived" event
-        pinned.copy_(counts, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record()
-        return done
-
-    def collect(rec):
-        outs, done, pinned = rec[:3]    # (rec[3] keeps the batch's size / scale tensors alive until its decode has run)
-        done.synchronize()                                      # the host waits for THIS batch only
-        counts = pinned.numpy()
-        ob, osc, ol, _ = outs
-        dets = [(torch.cat([ob[i, :int(counts[i])], osc[i, :int(counts[i]), None]], -1), ol[i, :int(counts[i])])
-                for i in range(ob.shape[0])]
-        if crops is None:
-            return dets
-        return (dets,) + _crops_collect(rec[4], counts, ob.shape[0])   # (rec[5]: the frames and their table, alive until here)
-
-    def post_launch(hw, sf, src):       # decode + NMS, and the batch's crops behind them: -> (outs, what fetch_counts copies, job)
-        if crops is None:
-            outs = _post_launch(self, hw, sf, test_cfg)
-            return outs, outs[3], None
-        counts = _crop_counts(self, hw.shape[0])
-        outs = _post_launch(self, hw, sf, test_cfg, counts_out=counts)
-        return outs, counts, _crops_launch(self, outs, counts, (crops, src[0]))
-
-    def upload(a):
-        return torch.from_numpy(a).pin_memory().to(self.dev, non_blocking=True)
+    def post_launch(hw, sf, src):       # decode + NMS, and the batch's crops behind them: -> (outs, what fetch copies, job)
+        return _launch_with_crops(self, hw.shape[0], None if crops is None else (crops, src[0]),
+                                  lambda c: _post_launch(self, hw, sf, test_cfg, counts_out=c))
 
     swapped = {}                 # id(plan) -> the plan currently holds its second set
 
-    def run():
-        prev = None
-        with torch.no_grad():
-            for batch in batches:
-                img, img_metas = batch[:2]
-                src = batch[2] if crops is not None else None
-                hw = upload(np.asarray([[float(m["img_shape"][0]), float(m["img_shape"][1])] for m in img_metas], np.float32))
-                sf = upload(np.stack([np.asarray(m["scale_factor"], np.float32).reshape(4) for m in img_metas])) if rescale else None
-                img = img.to(self.dev, non_blocking=True)
-                if overlap:
-                    e = self.engine
-                    e.prepare(img.shape[0], img.shape[2], img.shape[3])
-                    plan = e.buf
-                    if id(plan) not in alts or alts[id(plan)][0] is not plan:
-                        alts[id(plan)] = (plan, {k: torch.empty_like(plan[k]) for k in HEAD_OUT})
-                    other = alts[id(plan)][1]
-                    for k in HEAD_OUT:                               # this batch writes the set the batch before last wrote
-                        plan[k], other[k] = other[k], plan[k]
-                    swapped[id(plan)] = not swapped.get(id(plan), False)
-                    if post_ev[0] is not None:
-                        torch.cuda.current_stream().wait_event(post_ev[0])   # ... once that batch's decode / NMS have read it
-                    self.forward(img)
-                    fwd = torch.cuda.Event()
-                    fwd.record()
-                    with torch.cuda.stream(post):
-                        post.wait_event(fwd)
-                        outs, counts, job = post_launch(hw, sf, src)
-                        ev = torch.cuda.Event()
-                        ev.record()
-                        pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
-                        done = fetch_counts(counts, pinned)
-                    if job is not None:                             # (the crops and their rows are read on the caller's
-                        for t in job:                               # stream next: their memory returns to this one's pool)
-                            t.record_stream(torch.cuda.current_stream())
-                    post_ev[0], post_ev[1] = post_ev[1], ev
-                else:
-                    self.forward(img)
-                    outs, counts, job = post_launch(hw, sf, src)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
-                    with torch.cuda.stream(post):                   # (the copy must not queue behind the next batch's forward pass)
-                        post.wait_event(ev)
-                        done = fetch_counts(counts, pinned)
-                rec = (outs, done, pinned, (hw, sf), job, src)
-                if prev is not None:
-                    yield collect(prev)
-                prev = rec
-            if prev is not None:
-                yield collect(prev)
+    def enqueue(batch, fetch):
+        img, img_metas = batch[:2]
+        src = batch[2] if crops is not None else None
+        hw, sf = _meta_tensors(self, img_metas, rescale, _uploader(self, True))
+        img = img.to(self.dev, non_blocking=True)
+        if overlap:
+            e = self.engine
+            e.prepare(img.shape[0], img.shape[2], img.shape[3])
+            plan = e.buf
+            if id(plan) not in alts or alts[id(plan)][0] is not plan:
+                alts[id(plan)] = (plan, {k: torch.empty_like(plan[k]) for k in HEAD_OUT})
+            other = alts[id(plan)][1]
+            for k in HEAD_OUT:                               # this batch writes the set the batch before last wrote
+                plan[k], other[k] = other[k], plan[k]
+            swapped[id(plan)] = not swapped.get(id(plan), False)
+            if post_ev[0] is not None:
+                torch.cuda.current_stream().wait_event(post_ev[0])   # ... once that batch's decode / NMS have read it
+            self.forward(img)
+            fwd = torch.cuda.Event()
+            fwd.record()
+            with torch.cuda.stream(post):
+                post.wait_event(fwd)
+                outs, counts, job = post_launch(hw, sf, src)
+                ev = torch.cuda.Event()
+                ev.record()
+                pinned, done = fetch(counts)
+            if job is not None:                             # (the crops and their rows are read on the caller's
+                for t in job:                               # stream next: their memory returns to this one's pool)
+                    t.record_stream(torch.cuda.current_stream())
+            post_ev[0], post_ev[1] = post_ev[1], ev
+        else:
+            self.forward(img)
+            outs, counts, job = post_launch(hw, sf, src)
+            ev = torch.cuda.Event()
+            ev.record()
+            with torch.cuda.stream(post):                   # (the copy must not queue behind the next batch's forward pass)
+                post.wait_event(ev)
+                pinned, done = fetch(counts)
+        # (the size / scale tensors stay alive until the batch's decode has run, the frames and their table until its crops have)
+        return outs, job, hw.shape[0], pinned, done, (hw, sf), src
 
     try:
-        yield from run()
+        yield from _one_behind(self, batches, enqueue)
     finally:
         # leave every plan with its own set (captured graphs and the training step hold pointers to it).  After a complete
         # run collect() has host-synchronised the last batch; an abandoned generator (break / exception mid-iteration) can
@@ -1095,12 +1099,21 @@ def _detect_stream(self, batches, test_cfg, rescale=False, crops=None):
                     plan[k], other[k] = other[k], plan[k]
 
 
-def _meta_tensors(self, img_metas, rescale):
-    hw = torch.tensor([[float(m["img_shape"][0]), float(m["img_shape"][1])] for m in img_metas], device=self.dev)
-    sf = None
-    if rescale:
-        sf = torch.tensor(np.stack([np.asarray(m["scale_factor"], np.float32).reshape(4) for m in img_metas]), device=self.dev)
+def _rows_hw_sf(metas, with_sf=True):
+    """the metas of a list of rows on the host: img_shape's (h, w) f32 [R, 2] and, asked for, scale_factor f32 [R, 4]"""
+    hw = np.empty((len(metas), 2), np.float32)
+    sf = np.empty((len(metas), 4), np.float32) if with_sf else None
+    for r, m in enumerate(metas):
+        hw[r] = m["img_shape"][:2]
+        if with_sf:
+            sf[r] = np.asarray(m["scale_factor"], np.float32).reshape(4)
     return hw, sf
+
+
+def _meta_tensors(self, img_metas, rescale, upload=None):
+    upload = upload or _uploader(self, False)
+    hw, sf = _rows_hw_sf(img_metas, rescale)
+    return upload(hw), (upload(sf) if rescale else None)
 
 
 def _post_launch(self, hw, sf, test_cfg, head_out=None, counts_out=None):
@@ -1138,10 +1151,11 @@ def _nms_pre(self, test_cfg, level_hw):
     return nms_pre
 
 
-def _post_ws(self, key, B, cap, soft, extra_bytes, what, pool=0):
+def _post_ws(self, key, B, cap, soft, extra_bytes, what, pool=0, counters=None):
     """The cached buffers of one post-processing geometry: the candidate lists [B, cap] the NMS reads, its workspace, and
-    `extra_bytes` of decode workspace (dws); pool > 0 (test-time augmentation): the views' candidate pool of that many
-    entries in front of them.  The limit (RADET_POST_WS_LIMIT_GB) is checked on cap, the capacity the NMS sees."""
+    `extra_bytes` of decode workspace (dws); pool > 0 (test-time augmentation, tiles): the rows' candidate pool of that many
+    entries in front of them, with the zeroed i32 buffers of `counters` (name -> length: the per-row counts, the merge's
+    own).  The limit (RADET_POST_WS_LIMIT_GB) is checked on cap, the capacity the NMS sees."""
     posts = self.__dict__.setdefault("_posts", {})
     if key not in posts:
         # the NMS workspace holds a dense cap x cap / 64 x 8 B suppression mask per image (+ sort keys): 7 MiB per image at
@@ -1167,6 +1181,8 @@ def _post_ws(self, key, B, cap, soft, extra_bytes, what, pool=0):
         if pool:
             posts[key].update(pool_boxes=torch.empty(pool, 4, device=dev), pool_scores=torch.empty(pool, device=dev),
                               pool_ctr=torch.empty(pool, device=dev), pool_labels=torch.empty(pool, dtype=torch.long, device=dev))
+        for name, n in (counters or {}).items():
+            posts[key][name] = torch.zeros(n, dtype=torch.int32, device=dev)
     return posts[key]
 
 
@@ -1315,9 +1331,33 @@ def _stack_views(ts):
     return torch.cat(ts)
 
 
+# _aug_plan and _tile_plan return one shape of record, a batch of B images as rows (views or tiles) for _rows_launch:
+#   name, B, nlvl, hw [R, 2] (the rows' img_shape), groups [(first row, rows, nms_pre, cap, pool offset)]: the forward batches,
+#   each decoded into its block of the candidate pool; cap_out: the merged list's capacity per image; pool: the pool's entries;
+#   key, what, counters: the workspace's (_post_ws), counters its i32 buffers beside the pool; tables: the host arrays the
+#   merge reads on the device; merge(p, tables on the device): the ONE merge launch; check_nms_pre: nms_pre follows from
+#   test_cfg and the level sizes; split(imgs) -> the groups' tensors
+def _check_pool(mode, cap_out, pool, rows, how=""):
+    """the capacity rules of a merged batch: the NMS kernel's 16-bit positions, the pool's 31-bit offsets; rows() -> how the
+    refusals describe the batch (the merged list's rows, the pool's)"""
+    if cap_out > 65536:
+        raise NotImplementedError(f"{mode} with {rows()[0]}: the merged list of {cap_out} candidates per image exceeds the NMS "
+                                  f"kernel's 65536 (16-bit positions); lower nms_pre{how}")
+    if pool >= 2 ** 31:
+        raise NotImplementedError(f"{mode}: a candidate pool of {pool} entries ({rows()[1]}); lower nms_pre or the batch")
+
+
+def _pool_args(p):
+    return p["pool_boxes"], p["pool_scores"], p["pool_ctr"], p["pool_labels"], p["row_count"]
+
+
+def _list_args(p):
+    return p["boxes"], p["scores"], p["ctr"], p["labels"], p["count"]
+
+
 def _aug_plan(self, imgs, img_metas, test_cfg):
-    """Host part of detect_aug, before any launch: the checks, the groups, the pool layout and the merge descriptor.
-    -> dict(V, B, groups [(v0, v1, nms_pre, cap, pool offset)], cap_out, pool, desc (ndarray), hw, sf0)"""
+    """Host part of detect_aug, before any launch: the checks, the groups of views, the pool layout and the merge descriptor.
+    -> the row plan (above _check_pool; rows view-major, row v * B + b) with V and sf0 beside it"""
     V = len(imgs)
     if V != len(img_metas) or not 1 <= V <= K.TTA_MAX_VIEWS:
         raise ValueError(f"detect_aug: {V} views with {len(img_metas)} lists of metas (1..{K.TTA_MAX_VIEWS} views, one list each)")
@@ -1331,65 +1371,68 @@ def _aug_plan(self, imgs, img_metas, test_cfg):
         if len(shapes) > 1:
             raise ValueError(f"detect_aug: the views of image {b} disagree in ori_shape ({sorted(shapes)})")
     nlvl = len(self.engine.strides)
+    views = _view_groups(imgs)
     groups, pool, cap_out = [], 0, 0
-    hw = np.zeros((V * B, 2), np.float32)
-    sf = np.zeros((V * B, 4), np.float32)
+    hw, sf = _rows_hw_sf([m for metas in img_metas for m in metas])
     flips, starts, caps = (np.zeros(V * B, np.int32) for _ in range(3))
-    pres = []
-    for v0, v1 in _view_groups(imgs):
+    for v0, v1 in views:
         nms_pre = _nms_pre(self, test_cfg, _level_hw(int(imgs[v0].shape[2]), int(imgs[v0].shape[3])))
         cap = nlvl * nms_pre
-        groups.append((v0, v1, nms_pre, cap, pool))
-        pres.append(nms_pre)
+        groups.append((v0 * B, (v1 - v0) * B, nms_pre, cap, pool))
         for v in range(v0, v1):
             for b, m in enumerate(img_metas[v]):
                 r = v * B + b
-                hw[r] = m["img_shape"][:2]
-                sf[r] = np.asarray(m["scale_factor"], np.float32).reshape(4)
                 direction = m.get("flip_direction") if m.get("flip") else None
                 if direction not in K.FLIP_CODES:
                     raise ValueError(f"detect_aug: view {v} has flip_direction {direction!r}")
                 flips[r], starts[r], caps[r] = K.FLIP_CODES[direction], pool + ((v - v0) * B + b) * cap, cap
         pool += (v1 - v0) * B * cap
         cap_out += (v1 - v0) * cap
-    if cap_out > 65536:
-        raise NotImplementedError(f"test-time augmentation with V={V} views, nlvl={nlvl} levels and nms_pre={sorted(set(pres))}: "
-                                  f"the merged list of {cap_out} candidates per image exceeds the NMS kernel's 65536 (16-bit "
-                                  f"positions); lower nms_pre")
-    if pool >= 2 ** 31:
-        raise NotImplementedError(f"test-time augmentation: a candidate pool of {pool} entries (batch {B}); lower nms_pre or the batch")
-    return dict(V=V, B=B, nlvl=nlvl, groups=groups, cap_out=cap_out, pool=pool, desc=K.merge_desc_rows(hw, sf, flips, starts, caps),
-                hw=hw, sf0=sf[:B].copy())
+    pres = sorted({g[2] for g in groups})
+    _check_pool("test-time augmentation", cap_out, pool,
+                lambda: (f"V={V} views, nlvl={nlvl} levels and nms_pre={pres}", f"batch {B}"))
+    desc = K.merge_desc_rows(hw, sf, flips, starts, caps)
+
+    def merge(p, tables):
+        K.merge_views(desc, tables["desc"], V, B, *_pool_args(p), cap_out, *_list_args(p))
+
+    def split(imgs):                    # a group's views as one forward batch
+        return (_stack_views([t.to(self.dev) for t in imgs[v0:v1]]) for v0, v1 in views)
+    return dict(name="detect_aug", B=B, nlvl=nlvl, hw=hw, groups=groups, cap_out=cap_out, pool=pool,
+                key=("aug", B, tuple(g[:4] for g in groups)), what=f"batch {B} with {V} views, nlvl={nlvl}, nms_pre={pres}",
+                counters=dict(row_count=V * B), tables=dict(desc=desc), merge=merge, check_nms_pre=True, split=split,
+                V=V, sf0=sf[:B].copy())
 
 
-def _aug_launch(self, imgs, plan, test_cfg, upload, counts_out=None):
-    """Device part of detect_aug on the current stream: per group of views one forward pass and, behind it, one
-    radet_decode_candidates into the group's block of the pool (view coordinates, clamped to the view's own img_shape);
-    ONE radet_merge_views; the config's NMS over the merged lists (_nms_launch).  upload: ndarray -> device tensor.
-    Returns the NMS outputs, boxes in the frames' coordinates."""
-    V, B, nlvl, cap_out, pool = plan["V"], plan["B"], plan["nlvl"], plan["cap_out"], plan["pool"]
+def _rows_launch(self, batches, plan, test_cfg, upload, counts_out=None):
+    """Device part of detect_aug and detect_tiles on the current stream: per forward group (batches yields their tensors) one
+    forward pass and, behind it, one radet_decode_candidates into the group's block of the pool (row coordinates, clamped to
+    the row's own img_shape -- a box that reaches past a tile lands exactly on its edge); the plan's ONE merge launch
+    (radet_merge_views / radet_merge_tiles: map-back, stable compaction per image); the config's NMS over the merged lists
+    (_nms_launch).  upload: ndarray -> device tensor.  Returns the NMS outputs, boxes in the frames' coordinates."""
+    B, nlvl, cap_out = plan["B"], plan["nlvl"], plan["cap_out"]
     soft = dict(test_cfg["nms"]).get("type") == "soft_nms"
-    dbytes = max(K.decode_ws_bytes((v1 - v0) * B, nlvl, pre) for v0, v1, pre, _, _ in plan["groups"])
-    key = ("aug", B, tuple(g[:4] for g in plan["groups"])) + (("soft",) if soft else ())
-    p = _post_ws(self, key, B, cap_out, soft, dbytes, f"batch {B} with {V} views, nlvl={nlvl}, nms_pre="
-                 f"{sorted({g[2] for g in plan['groups']})}", pool=pool)
-    if "view_count" not in p:
-        p["view_count"] = torch.zeros(V * B, dtype=torch.int32, device=self.dev)
+    dbytes = max(K.decode_ws_bytes(n, nlvl, pre) for _, n, pre, _, _ in plan["groups"])
+    p = _post_ws(self, plan["key"] + (("soft",) if soft else ()), B, cap_out, soft, dbytes, plan["what"], pool=plan["pool"],
+                 counters=plan["counters"])
     hw = upload(plan["hw"])
-    desc = upload(plan["desc"])
-    for v0, v1, nms_pre, cap, off in plan["groups"]:
-        self.forward(_stack_views([t.to(self.dev) for t in imgs[v0:v1]]))
+    tables = {k: upload(a) for k, a in plan["tables"].items()}
+    for img, (r0, n, nms_pre, cap, off) in zip(batches, plan["groups"]):
+        self.forward(img)
         ho = _head_out(self)
-        n = (v1 - v0) * B
-        if ho["B"] != n or ho["nlvl"] != nlvl or _nms_pre(self, test_cfg, ho["level_hw"]) != nms_pre:
-            raise RuntimeError("detect_aug: the engine's level geometry differs from the planned one")
+        if ho["B"] != n or ho["nlvl"] != nlvl or (plan["check_nms_pre"] and _nms_pre(self, test_cfg, ho["level_hw"]) != nms_pre):
+            raise RuntimeError(f"{plan['name']}: the engine's level geometry differs from the planned one")
         K.decode_candidates(ho["cls"], ho["reg"], ho["iou"], ho["scales"], ho["ldesc"], nlvl, n, self.num_classes,
-                            float(test_cfg["score_thr"]), nms_pre, hw[v0 * B:v1 * B], None, p["pool_boxes"][off:off + n * cap],
-                            p["pool_scores"][off:off + n * cap], p["pool_ctr"][off:off + n * cap],
-                            p["pool_labels"][off:off + n * cap], p["view_count"][v0 * B:v1 * B], p["dws"])
-    K.merge_views(plan["desc"], desc, V, B, p["pool_boxes"], p["pool_scores"], p["pool_ctr"], p["pool_labels"], p["view_count"],
-                  cap_out, p["boxes"], p["scores"], p["ctr"], p["labels"], p["count"])
+                            float(test_cfg["score_thr"]), nms_pre, hw[r0:r0 + n], None,
+                            *(t[off:off + n * cap] for t in _pool_args(p)[:4]), p["row_count"][r0:r0 + n], p["dws"])
+    plan["merge"](p, tables)
     return _nms_launch(self, p, B, cap_out, test_cfg, counts_out)
+
+
+def _rows_batch(self, imgs, plan, test_cfg, pinned, crops):
+    """a planned batch's whole device program: _rows_launch and, with crops, the crop launches -> _launch_with_crops' triple"""
+    return _launch_with_crops(self, plan["B"], crops, lambda c: _rows_launch(self, plan["split"](imgs), plan, test_cfg,
+                                                                             _uploader(self, pinned), c))
 
 
 def _detect_aug(self, imgs, img_metas, test_cfg, rescale=False, crops=None):
@@ -1405,19 +1448,10 @@ def _detect_aug(self, imgs, img_metas, test_cfg, rescale=False, crops=None):
         plan = _aug_plan(self, imgs, img_metas, test_cfg)
         if plan["V"] == 1:
             return _detect(self, imgs[0], img_metas[0], test_cfg, rescale, crops)
-        B = plan["B"]
-
-        def upload(a):
-            return torch.from_numpy(a).to(self.dev)
-        counts = None if crops is None else _crop_counts(self, B)
-        outs = _aug_launch(self, imgs, plan, test_cfg, upload, counts_out=counts)
-        job = None if crops is None else _crops_launch(self, outs, counts, crops)
+        outs, counts, job = _rows_batch(self, imgs, plan, test_cfg, False, crops)
         if not rescale:
-            outs = (outs[0] * upload(plan["sf0"])[:, None, :],) + tuple(outs[1:])
-        if crops is None:
-            return _post_collect(self, *outs)
-        host = counts.cpu().numpy()
-        return (_post_collect(self, *outs, counts=host),) + _crops_collect(job, host, B)
+            outs = (outs[0] * _uploader(self, False)(plan["sf0"])[:, None, :],) + tuple(outs[1:])
+        return _finish(self, outs, job, plan["B"], counts.cpu().numpy())
 
 
 def _detect_aug_stream(self, batches, test_cfg, crops=None):
@@ -1426,34 +1460,12 @@ def _detect_aug_stream(self, batches, test_cfg, crops=None):
     counts, which arrive through a pinned copy behind an event, as in detect_stream.  Everything runs on the caller's stream:
     the decode / NMS overlap of detect_stream on a second stream is absent here.  crops: an ops.crops.CropSpec; the crops are
     cut from the batch's frames (the table's first B rows) behind its NMS.  Yields what detect_aug returns, in order."""
-    def upload(a):
-        return torch.from_numpy(a).pin_memory().to(self.dev, non_blocking=True)
-
-    def collect(rec):
-        outs, done, pinned, B, job = rec[:5]    # (the rest keeps the batch's views, table and frames alive until here)
-        done.synchronize()                      # the host waits for THIS batch only
-        host = pinned.numpy()
-        dets = _post_collect(self, *outs, counts=host)
-        return dets if crops is None else (dets,) + _crops_collect(job, host, B)
-
-    prev = None
-    with torch.no_grad():
-        for imgs, metas, source in batches:
-            plan = _aug_plan(self, imgs, metas, test_cfg)
-            B = plan["B"]
-            counts = torch.zeros(B, dtype=torch.int32, device=self.dev) if crops is None else _crop_counts(self, B)
-            outs = _aug_launch(self, imgs, plan, test_cfg, upload, counts_out=counts)
-            job = None if crops is None else _crops_launch(self, outs, counts, (crops, source[0]))
-            pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
-            pinned.copy_(counts, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-            rec = (outs, done, pinned, B, job, source, imgs)
-            if prev is not None:
-                yield collect(prev)
-            prev = rec
-        if prev is not None:
-            yield collect(prev)
+    def enqueue(batch, fetch):
+        imgs, metas, source = batch
+        plan = _aug_plan(self, imgs, metas, test_cfg)
+        outs, counts, job = _rows_batch(self, imgs, plan, test_cfg, True, None if crops is None else (crops, source[0]))
+        return (outs, job, plan["B"]) + fetch(counts) + (batch,)   # (the batch's views, table and frames stay alive with it)
+    return _one_behind(self, batches, enqueue)
 
 
 DetectorRuntime.detect_aug = _detect_aug
@@ -1465,7 +1477,7 @@ def _tile_plan(self, imgs, plan, test_cfg):
     """Host part of detect_tiles, before any launch: the checks, the forward batches, the pool layout and the merge
     descriptor.  plan: what ImagePipeline.run_tile_rows returns (img_metas [R], rects [R, 4], edges [R], row_start [B + 1])
     with edge_margin, batch and nms_pre beside them (apis.set_tiling's).
-    -> dict(B, R, nlvl, nms_pre, cap, cap_out, pool, batches [(first row, rows)], desc, row_start (ndarrays), hw, margin)"""
+    -> the row plan (above _check_pool; rows image-major, as the plan has them) with R and nms_pre beside it"""
     R = int(imgs.shape[0])
     row_start = np.ascontiguousarray(plan["row_start"], dtype=np.int32)
     B = len(row_start) - 1
@@ -1482,58 +1494,30 @@ def _tile_plan(self, imgs, plan, test_cfg):
     if batch < 1 or not np.isfinite(margin) or margin < 0:
         raise ValueError(f"detect_tiles: batch={batch}, edge_margin={margin}")
     nlvl = len(self.engine.strides)
-    nms_pre = plan.get("nms_pre")
-    nms_pre = int(nms_pre) if nms_pre else _nms_pre(self, test_cfg, _level_hw(int(imgs.shape[2]), int(imgs.shape[3])))
+    own_pre = plan.get("nms_pre")
+    nms_pre = int(own_pre) if own_pre else _nms_pre(self, test_cfg, _level_hw(int(imgs.shape[2]), int(imgs.shape[3])))
     cap = nlvl * nms_pre
     cap_out = int(rows_b.max()) * cap
-    if cap_out > 65536:
-        raise NotImplementedError(f"tiled inference with {int(rows_b.max())} rows for a frame, nlvl={nlvl} levels and nms_pre="
-                                  f"{nms_pre}: the merged list of {cap_out} candidates per image exceeds the NMS kernel's 65536 "
-                                  f"(16-bit positions); lower nms_pre (set_tiling(..., nms_pre=...)) or enlarge the tile")
-    pool = R * cap
-    if pool >= 2 ** 31:
-        raise NotImplementedError(f"tiled inference: a candidate pool of {pool} entries ({R} rows); lower nms_pre or the batch")
-    hw = np.array([m["img_shape"][:2] for m in metas], np.float32).reshape(R, 2)
-    sf = np.stack([np.asarray(m["scale_factor"], np.float32).reshape(4) for m in metas])
+    _check_pool("tiled inference", cap_out, R * cap,
+                lambda: (f"{int(rows_b.max())} rows for a frame, nlvl={nlvl} levels and nms_pre={nms_pre}", f"{R} rows"),
+                " (set_tiling(..., nms_pre=...)) or enlarge the tile")
+    hw, sf = _rows_hw_sf(metas)
     rects = np.asarray(plan["rects"], np.int64).reshape(R, 4)
     desc = K.tile_desc_rows(hw, sf, rects[:, 0:2], np.asarray(plan["edges"], np.int32), np.arange(R, dtype=np.int64) * cap,
                             np.full(R, cap, np.int32))
-    return dict(B=B, R=R, nlvl=nlvl, nms_pre=nms_pre, cap=cap, cap_out=cap_out, pool=pool, desc=desc, row_start=row_start,
-                batches=[(i0, min(batch, R - i0)) for i0 in range(0, R, batch)], hw=hw, margin=margin, batch=batch)
 
+    def merge(p, tables):               # (the edge rule, map-back, stable compaction per image)
+        K.merge_tiles(desc, tables["desc"], row_start, tables["row_start"], B, *_pool_args(p), margin, cap_out, *_list_args(p),
+                      p["dropped"])
 
-def _tile_launch(self, imgs, tp, test_cfg, upload, counts_out=None):
-    """Device part of detect_tiles on the current stream: the R rows as consecutive forward batches of at most `batch` rows,
-    each followed by one radet_decode_candidates into its block of the pool (row coordinates, clamped to the row's own
-    img_shape -- a box that reaches past a tile lands exactly on its edge); ONE radet_merge_tiles (edge rule, map-back,
-    stable compaction per image); the config's NMS over the merged lists (_nms_launch).  upload: ndarray -> device tensor.
-    Returns the NMS outputs, boxes in the frames' coordinates."""
-    B, R, nlvl, nms_pre, cap, cap_out = tp["B"], tp["R"], tp["nlvl"], tp["nms_pre"], tp["cap"], tp["cap_out"]
-    soft = dict(test_cfg["nms"]).get("type") == "soft_nms"
-    dbytes = max(K.decode_ws_bytes(n, nlvl, nms_pre) for _, n in tp["batches"])
-    key = ("tiles", B, R, cap_out, nms_pre, tp["batch"]) + (("soft",) if soft else ())
-    p = _post_ws(self, key, B, cap_out, soft, dbytes, f"{B} frames as {R} tiled rows, nlvl={nlvl}, nms_pre={nms_pre}",
-                 pool=tp["pool"])
-    if "row_count" not in p:
-        p["row_count"] = torch.zeros(R, dtype=torch.int32, device=self.dev)
-        p["dropped"] = torch.zeros(B, dtype=torch.int32, device=self.dev)
-    hw = upload(tp["hw"])
-    desc = upload(tp["desc"])
-    row_start = upload(tp["row_start"])
-    imgs = imgs.to(self.dev)
-    for i0, n in tp["batches"]:
-        self.forward(imgs[i0:i0 + n])
-        ho = _head_out(self)
-        if ho["B"] != n or ho["nlvl"] != nlvl:
-            raise RuntimeError("detect_tiles: the engine's level geometry differs from the planned one")
-        K.decode_candidates(ho["cls"], ho["reg"], ho["iou"], ho["scales"], ho["ldesc"], nlvl, n, self.num_classes,
-                            float(test_cfg["score_thr"]), nms_pre, hw[i0:i0 + n], None, p["pool_boxes"][i0 * cap:(i0 + n) * cap],
-                            p["pool_scores"][i0 * cap:(i0 + n) * cap], p["pool_ctr"][i0 * cap:(i0 + n) * cap],
-                            p["pool_labels"][i0 * cap:(i0 + n) * cap], p["row_count"][i0:i0 + n], p["dws"])
-    K.merge_tiles(tp["desc"], desc, tp["row_start"], row_start, B, p["pool_boxes"], p["pool_scores"], p["pool_ctr"],
-                  p["pool_labels"], p["row_count"], tp["margin"], cap_out, p["boxes"], p["scores"], p["ctr"], p["labels"],
-                  p["count"], p["dropped"])
-    return _nms_launch(self, p, B, cap_out, test_cfg, counts_out)
+    def split(imgs):                    # the R rows as consecutive forward batches of at most `batch` rows
+        imgs = imgs.to(self.dev)
+        return (imgs[i0:i0 + batch] for i0 in range(0, R, batch))
+    return dict(name="detect_tiles", B=B, nlvl=nlvl, hw=hw, cap_out=cap_out, pool=R * cap,
+                groups=[(i0, min(batch, R - i0), nms_pre, cap, i0 * cap) for i0 in range(0, R, batch)],
+                key=("tiles", B, R, cap_out, nms_pre, batch), what=f"{B} frames as {R} tiled rows, nlvl={nlvl}, nms_pre={nms_pre}",
+                counters=dict(row_count=R, dropped=B), tables=dict(desc=desc, row_start=row_start), merge=merge,
+                check_nms_pre=not own_pre, split=split, R=R, nms_pre=nms_pre)
 
 
 def _detect_tiles(self, imgs, plan, test_cfg, crops=None):
@@ -1549,17 +1533,8 @@ def _detect_tiles(self, imgs, plan, test_cfg, crops=None):
     Returns what `detect` returns, one entry per FRAME."""
     with torch.no_grad():
         tp = _tile_plan(self, imgs, plan, test_cfg)
-        B = tp["B"]
-
-        def upload(a):
-            return torch.from_numpy(a).to(self.dev)
-        counts = None if crops is None else _crop_counts(self, B)
-        outs = _tile_launch(self, imgs, tp, test_cfg, upload, counts_out=counts)
-        if crops is None:
-            return _post_collect(self, *outs)
-        job = _crops_launch(self, outs, counts, crops)
-        host = counts.cpu().numpy()
-        return (_post_collect(self, *outs, counts=host),) + _crops_collect(job, host, B)
+        outs, counts, job = _rows_batch(self, imgs, tp, test_cfg, False, crops)
+        return _finish(self, outs, job, tp["B"], counts.cpu().numpy())
 
 
 def _detect_tiles_stream(self, batches, test_cfg, crops=None):
@@ -1568,34 +1543,12 @@ def _detect_tiles_stream(self, batches, test_cfg, crops=None):
     event, as in detect_aug_stream; everything runs on the caller's stream.  crops: an ops.crops.CropSpec; the crops are cut
     from the batch's frames (plan['table'], whose first B rows are the source frames) behind its NMS.  Yields what
     detect_tiles returns, in order."""
-    def upload(a):
-        return torch.from_numpy(a).pin_memory().to(self.dev, non_blocking=True)
-
-    def collect(rec):
-        outs, done, pinned, B, job = rec[:5]    # (the rest keeps the batch's rows, table and frames alive until here)
-        done.synchronize()                      # the host waits for THIS batch only
-        host = pinned.numpy()
-        dets = _post_collect(self, *outs, counts=host)
-        return dets if crops is None else (dets,) + _crops_collect(job, host, B)
-
-    prev = None
-    with torch.no_grad():
-        for imgs, plan in batches:
-            tp = _tile_plan(self, imgs, plan, test_cfg)
-            B = tp["B"]
-            counts = torch.zeros(B, dtype=torch.int32, device=self.dev) if crops is None else _crop_counts(self, B)
-            outs = _tile_launch(self, imgs, tp, test_cfg, upload, counts_out=counts)
-            job = None if crops is None else _crops_launch(self, outs, counts, (crops, plan["table"]))
-            pinned = torch.empty(counts.shape, dtype=counts.dtype).pin_memory()
-            pinned.copy_(counts, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-            rec = (outs, done, pinned, B, job, plan, imgs)
-            if prev is not None:
-                yield collect(prev)
-            prev = rec
-        if prev is not None:
-            yield collect(prev)
+    def enqueue(batch, fetch):
+        imgs, plan = batch
+        tp = _tile_plan(self, imgs, plan, test_cfg)
+        outs, counts, job = _rows_batch(self, imgs, tp, test_cfg, True, None if crops is None else (crops, plan["table"]))
+        return (outs, job, tp["B"]) + fetch(counts) + (batch,)   # (the batch's rows, table and frames stay alive with it)
+    return _one_behind(self, batches, enqueue)
 
 
 DetectorRuntime.detect_tiles = _detect_tiles

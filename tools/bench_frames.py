@@ -136,10 +136,11 @@ def tta_main(args):
     data = _prepare_frames(_frame_pipeline(model, tta), frames)
     plan = _aug_plan(rt, data["img"], data["img_metas"], model.test_cfg)
     p = next(v for k, v in rt._posts.items() if k[0] == "aug")
-    desc = torch.from_numpy(plan["desc"]).to(dev)
+    host_desc = plan["tables"]["desc"]
+    desc = torch.from_numpy(host_desc).to(dev)
 
     def merge():
-        K.merge_views(plan["desc"], desc, V, B, p["pool_boxes"], p["pool_scores"], p["pool_ctr"], p["pool_labels"], p["view_count"],
+        K.merge_views(host_desc, desc, V, B, p["pool_boxes"], p["pool_scores"], p["pool_ctr"], p["pool_labels"], p["row_count"],
                       plan["cap_out"], p["boxes"], p["scores"], p["ctr"], p["labels"], p["count"])
     # the preparation launch: V * B rows with the second half flipped, beside the same rows unflipped
     buf = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).to(dev)
@@ -159,7 +160,7 @@ def tta_main(args):
     for _ in range(args.reps):
         for k, fn in launches.items():
             lrounds[k].append(event_ms(fn, 50))
-    counts = p["view_count"].cpu().tolist()
+    counts = p["row_count"].cpu().tolist()
     med = statistics.median
     out = dict(case=dict(batch=B, views=V, frame_hw=[480, 640], tta=dict(img_scale=[[640, 480]], flip=True, flip_direction="horizontal"),
                          forward_batch=V * B, nms_pre=int(model.test_cfg["nms_pre"]), merged_capacity=plan["cap_out"],
