@@ -821,6 +821,56 @@ int radet_crop_plan(const float* boxes, const float* scores, const int* counts, 
 int radet_crop_frames(const int* rows, const int* counters, const int* desc, int B, int cap, int Ho, int Wo, int flags,
                       unsigned fill, float m0, float m1, float m2, float s0, float s1, float s2, void* out, void* stream);
 
+/* ---- detections drawn on frames (csrc/draw.hip), one launch: box outlines and "name|score" labels.  These are this
+ *      project's own pixel rules (the reference draws with matplotlib / mmcv / cv2; parity with them is unpinned), pinned bit
+ *      for bit to the NumPy restatement tests/_draw_ref.py.
+ *      src_desc / dst_desc (device) = B rows of PREP_DESC_INTS ints as above (address, row stride, h, w; the other fields are
+ *      not read): any byte alignment, frames may be views into larger tensors.  A destination row names the same h x w as
+ *      its source row (a frame whose rows disagree is skipped).  Out of place every byte of the h x w x 3 pixels of every
+ *      destination frame is written (copy + overlay in one pass); with DRAW_INPLACE dst_desc == src_desc and a pixel tile
+ *      that nothing covers stores nothing (without the flag, a frame whose destination row names its source row's address and
+ *      stride is in place likewise: one table may mix both).  Bytes between the rows of a view are never touched.  max_h / max_w: the largest
+ *      h / w of the table (the grid; pixels beyond them are not visited).  Frames with h or w <= 0 draw nothing.
+ *      Detections in the padded NMS layout: boxes f32 [B,K,4] (16-byte aligned), scores f32 [B,K], labels i64 [B,K],
+ *      counts i32 [B].
+ *   Which are drawn.  Detection j < min(counts[b], K) is VALID when its four coordinates and its score are finite,
+ *      score > score_thr (strict), 0 <= label < (n_names > 0 ? n_names : 100000) (and < n_palette when box_colour < 0), and
+ *      x2i >= x1i, y2i >= y1i where  vi = (int)clamp(v, -2^20, 2^20)  (truncation toward zero: numpy's astype(int32)).
+ *      The first max_dets (<= DRAW_MAX_DETS) valid detections in rank order are DRAWN; r = their rank among the drawn.
+ *   Outline.  t = thickness >= 1, lo = t / 2, hi = (t - 1) / 2.  Pixel (x, y) is on detection r's outline when it is inside
+ *      [x1i - lo, x2i + hi] x [y1i - lo, y2i + hi] and not strictly inside (x1i + hi, x2i - lo) x (y1i + hi, y2i - lo).
+ *      Opaque; the lowest r whose outline covers a pixel gives its colour: box_colour = b | g << 8 | r << 16, or with
+ *      box_colour < 0 the three bytes palette[label] (u8 [n_palette,3], BGR).
+ *   Label (Hc > 0).  atlas u8 [S,Hc,Wa] holds one strip of coverage per row-block, strip s being widths[s] (i32 [S], clamped
+ *      to [0, Wa]) columns wide: strips 0-9 the digits, 10 '.', 11 '|', 12 'class ', 13 + c the name of class c.  The text is
+ *      with n_names > 0 the strips {13 + label, 11, d, 10, d, d}, else {12, the label's decimal digits, 11, d, 10, d, d};
+ *      d.dd shows  cents = clamp((int)floor((double)score * 100.0 + 0.5), 0, 100)  -- ties round UP (0.125 -> 0.13), where
+ *      Python's ':.02f' rounds half to even.  Wt = the sum of the strips' widths (at most DRAW_MAX_TEXT_W), p = pad, the
+ *      label rectangle is lw x lh = (Wt + 2p) x (Hc + 2p) at  lx = max(0, min(x1i, w - lw)),  ly = max(0, min(y1i, h - lh)).
+ *      Blend, exact in integers, per channel, a in [0, 65025]:  out = (colour * a + pixel * (65025 - a) + 32512) / 65025.
+ *      Above ALL outlines the labels are composited from the last drawn rank down to rank 0, each as: the rectangle in black
+ *      with a = a_bg * 255 (a_bg in [0, 255]), then the text in text_colour with a = 255 * coverage at text pixel
+ *      (x - lx - p, y - ly - p) inside [0, Wt) x [0, Hc).  Hc == 0 draws no labels (atlas, widths may be NULL).
+ *   Gather form: one workgroup per 128 x 8 pixel tile and frame derives the frame's drawn detections, culls them against its
+ *      tile into LDS in rank order (ballot + popcount across its wavefronts) and every pixel is computed and stored by
+ *      exactly one thread: no atomics, no workspace, no host synchronisation, capturable, the same bytes on every run.
+ *   RADET_ERR_ARG before any launch: B outside [0, 65535], K < 0, thickness outside [1, DRAW_MAX_THICKNESS], max_dets outside
+ *      [0, DRAW_MAX_DETS], a_bg outside [0, 255], a colour above 0xFFFFFF, box_colour < 0 without a palette, pad outside
+ *      [0, DRAW_MAX_PAD], Hc outside [0, DRAW_MAX_GLYPH_H], with Hc > 0 a NULL atlas / widths, Wa outside [1, DRAW_MAX_TEXT_W]
+ *      or S < 13 + n_names, a NaN score_thr, unknown flags, max_h > 65535 * 8, a NULL table or boxes not 16-byte aligned with
+ *      something to do.  B == 0 or max_h == 0 or max_w == 0: RADET_OK, no launch. */
+#define DRAW_MAX_DETS 256
+#define DRAW_MAX_THICKNESS 255
+#define DRAW_MAX_TEXT_W 4096
+#define DRAW_MAX_GLYPH_H 256
+#define DRAW_MAX_PAD 64
+#define DRAW_INPLACE 1
+int radet_draw_detections(const int* src_desc, const int* dst_desc, int B, int max_h, int max_w, const float* boxes,
+                          const float* scores, const int64_t* labels, const int* counts, int K, int thickness, int box_colour,
+                          const uint8_t* palette, int n_palette, int text_colour, int a_bg, float score_thr, int max_dets,
+                          int n_names, int pad, int flags, const uint8_t* atlas, const int* widths, int S, int Hc, int Wa,
+                          void* stream);
+
 /* ---- stand-alone box / loss operators behind the registered classes (used on their own; inside the detector the same
  *      arithmetic runs fused in radet_head_loss / radet_decode_candidates) ------------------------------------------ */
 /* bbox_overlaps / BboxOverlaps2D (radet/core/bbox/iou_calculators/iou2d_calculator.py:43-159): boxes [batch, M, 4] and

@@ -144,6 +144,8 @@ SIGNATURES = {
     "radet_merge_tiles": (_i, [_p, _p, _p, _p, _i, _sz, _p, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "radet_crop_plan": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p]),
     "radet_crop_frames": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p]),
+    "radet_draw_detections": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _f, _i, _i, _i, _i, _p, _p, _i, _i,
+                                   _i, _p]),
     "radet_grid_anchors": (_i, [_p, _p, _i, _i, _p]),
     "radet_bbox_overlaps": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "radet_tblr_encode": (_i, [_p, _p, _p, _i, _p, _i, _p]),

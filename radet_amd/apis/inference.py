@@ -363,3 +363,121 @@ def inference_detector(model, imgs, scale_factor=None, crops=None):
     metas = [dict(img_shape=(H, W, 3), pad_shape=(H, W, 3), scale_factor=sf, flip=False) for _ in range(B)]
     with torch.no_grad():
         return model(img=[imgs], img_metas=[metas], return_loss=False, rescale=True)
+
+
+class _DrawGroup:
+    """One batch of draw_frames: its host frames go up ONCE, in one pinned non-blocking copy, as device views -- what
+    detect_frames reads and what the overlay is drawn into --, followed in the same allocation by the destinations of the
+    caller's device frames (unless inplace).  sources[i]: what the detector reads; dests[i]: where frame i's overlay lands."""
+
+    def __init__(self, frames, dev, inplace):
+        sizes = [int(f.shape[0]) * int(f.shape[1]) * 3 for f in frames]
+        host = [isinstance(f, np.ndarray) for f in frames]
+        n_up = sum(s for s, h in zip(sizes, host) if h)
+        n_out = 0 if inplace else sum(s for s, h in zip(sizes, host) if not h)
+        self.buf = torch.empty(max(n_up + n_out, 1), dtype=torch.uint8, device=dev)
+        self.sources, self.dests, self.slices = [], [], []
+        stage = torch.empty(max(n_up, 1), dtype=torch.uint8, pin_memory=True)
+        arr, up, out = stage.numpy(), 0, n_up
+        for f, n, h in zip(frames, sizes, host):
+            shape = (int(f.shape[0]), int(f.shape[1]), 3)
+            if h:
+                np.copyto(arr[up:up + n].reshape(shape), f)
+                view = self.buf[up:up + n].view(shape)
+                self.sources.append(view)
+                self.dests.append(view)
+                self.slices.append((up, n))
+                up += n
+            else:
+                self.sources.append(f)
+                self.dests.append(f if inplace else self.buf[out:out + n].view(shape))
+                self.slices.append(None if inplace else (out, n))
+                out += 0 if inplace else n
+        if n_up:
+            self.buf[:n_up].copy_(stage[:n_up], non_blocking=True)
+
+    def to_host(self):
+        """the annotated frames as host arrays: ONE copy of the batch's allocation (frames drawn in place in the caller's
+        own tensors come back one by one)"""
+        stage = torch.empty(self.buf.numel(), dtype=torch.uint8, pin_memory=True)
+        stage.copy_(self.buf, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        arr = stage.numpy()
+        return [d.cpu().numpy() if s is None else arr[s[0]:s[0] + s[1]].reshape(tuple(d.shape)) for d, s in zip(self.dests, self.slices)]
+
+
+def draw_frames(model, frames, batch_size=8, on_device=False, inplace=False, **style):
+    """Generator over an iterable of frames, as detect_frames: yields (result, annotated frame) per frame, in order -- the
+    frame's detections drawn on it (box outlines, "name|score" labels) by ONE HIP launch per batch on the caller's stream,
+    enqueued when the batch's detections are handed out.  result is what detect_frames yields (on_device=True: the (dets,
+    labels) device tensors and the annotated frame as a device u8 [H,W,3] tensor; False: the per-class list and an ndarray,
+    a batch's annotated frames brought back in one copy).
+    Host frames of a batch go up once, in one pinned copy, as device views: detect_frames(on_device=True) reads those views
+    and the overlay is drawn into them, so nothing is uploaded twice and the caller's arrays stay as they are.  Device frames
+    from the caller are copied by the same launch, or with inplace=True drawn on where they are (device tensors only).
+    **style: draw_detections' keyword arguments (class_names -- default: the model's CLASSES --, score_thr, bbox_color,
+    text_color, thickness, font_size, label_alpha, max_dets, atlas).  set_tta / set_tiling work unchanged underneath."""
+    from collections import deque
+    from ..ops.crops import check_frames, frame_table
+    from .. import kernels as K
+    from ..ops.draw import Painter, check_device_frames, pad_detections
+    if batch_size < 1:
+        raise ValueError(f"batch_size={batch_size}")
+    unknown = set(style) - {"class_names", "score_thr", "bbox_color", "text_color", "thickness", "font_size", "label_alpha",
+                            "max_dets", "atlas"}
+    if unknown:
+        raise TypeError(f"draw_frames: unknown style arguments {sorted(unknown)}")
+    if "class_names" not in style and getattr(model, "CLASSES", None) is not None:
+        style["class_names"] = [str(c) for c in model.CLASSES]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    painter = Painter(dev, **style)
+    num_classes = model.bbox_head.num_classes
+    groups = deque()
+
+    def staged():
+        def stage(group):
+            check_frames(group)
+            if inplace:
+                check_device_frames(group, "inplace=True")
+            groups.append(_DrawGroup(group, dev, inplace))
+            return groups[-1].sources
+        group = []
+        for f in frames:
+            group.append(f)
+            if len(group) == batch_size:
+                yield from stage(group)
+                group = []
+        if group:
+            yield from stage(group)
+
+    stream = detect_frames(model, staged(), batch_size=batch_size, on_device=True)
+    try:
+        dets = []
+        for res in stream:
+            dets.append(res)
+            g = groups[0]
+            if len(dets) < len(g.sources):
+                continue
+            groups.popleft()
+            B = len(dets)
+            boxes, scores, labels, counts = pad_detections(dets, dev)
+            table, keep = frame_table(g.sources + g.dests, dev)          # (device views only: the table is the upload)
+            n = B * K.PREP_DESC_INTS
+            painter.launch(table[:n], table[n:], B, max(int(f.shape[0]) for f in g.sources),
+                           max(int(f.shape[1]) for f in g.sources), boxes, scores, labels, counts, False)
+            del keep
+            shown = g.dests if on_device else g.to_host()
+            for (b, l), img in zip(dets, shown):
+                yield ((b, l) if on_device else bbox2result(b, l, num_classes)), img
+            dets = []
+    finally:
+        stream.close()
+
+
+def show_result_pyplot(model, img, result, score_thr=0.3, fig_size=(15, 10), title="result", block=True, wait_time=0):
+    """radet/apis/inference.py:163: the result drawn over img (model.show_result) and shown with matplotlib; `block` is
+    ignored as in the reference"""
+    if hasattr(model, "module"):
+        model = model.module
+    return model.show_result(img, result, score_thr=score_thr, show=True, wait_time=wait_time, fig_size=fig_size, win_name=title,
+                             bbox_color=(72, 101, 241), text_color=(72, 101, 241))

@@ -1996,6 +1996,39 @@ def crop_frames(rows, counters, desc, B, cap, size, out, fill=0, mean=None, stdi
               _stream())
 
 
+# ---------------------------------------------------------------------- detections drawn on frames (csrc/draw.hip)
+DRAW_MAX_DETS = 256                # include/radet_hip.h
+DRAW_MAX_THICKNESS = 255
+DRAW_MAX_TEXT_W = 4096
+DRAW_MAX_GLYPH_H = 256
+DRAW_MAX_PAD = 64
+DRAW_INPLACE = 1
+DRAW_STRIP_DOT, DRAW_STRIP_BAR, DRAW_STRIP_CLASS, DRAW_STRIP_NAME0 = 10, 11, 12, 13
+
+
+def draw_detections(src_desc, dst_desc, B, max_h, max_w, boxes, scores, labels, counts, thickness, box_colour, palette,
+                    text_colour, a_bg, score_thr, max_dets, n_names, pad, inplace, atlas, widths):
+    """one launch: the detections boxes f32 [B,K,4], scores f32 [B,K], labels i64 [B,K], counts i32 [B] drawn on the frames of
+    src_desc i32 [B, PREP_DESC_INTS] into those of dst_desc (the same table with inplace).  box_colour: b | g << 8 | r << 16,
+    or None with palette u8 [n,3]; atlas u8 [S,Hc,Wa] with widths i32 [S], or None for no labels (include/radet_hip.h)"""
+    Kd = int(boxes.shape[1])
+    assert boxes.dtype == torch.float32 and tuple(boxes.shape) == (B, Kd, 4) and scores.dtype == torch.float32
+    assert tuple(scores.shape) == (B, Kd) and labels.dtype == torch.int64 and tuple(labels.shape) == (B, Kd)
+    assert counts.dtype == torch.int32 and counts.numel() == B
+    assert all(d.dtype == torch.int32 and d.numel() >= B * PREP_DESC_INTS for d in (src_desc, dst_desc))
+    assert (box_colour is None) != (palette is None)
+    assert palette is None or (palette.dtype == torch.uint8 and palette.dim() == 2 and palette.shape[1] == 3 and palette.is_contiguous())
+    S = Hc = Wa = 0
+    if atlas is not None:
+        S, Hc, Wa = (int(v) for v in atlas.shape)
+        assert atlas.dtype == torch.uint8 and atlas.is_contiguous() and widths.dtype == torch.int32 and widths.numel() == S
+    _lib.call("radet_draw_detections", _ptr(src_desc), _ptr(dst_desc), int(B), int(max_h), int(max_w), _ptr(boxes), _ptr(scores),
+              _ptr(labels), _ptr(counts), Kd, int(thickness), -1 if box_colour is None else int(box_colour),
+              None if palette is None else _ptr(palette), 0 if palette is None else int(palette.shape[0]), int(text_colour),
+              int(a_bg), float(score_thr), int(max_dets), int(n_names), int(pad), DRAW_INPLACE if inplace else 0,
+              None if atlas is None else _ptr(atlas), None if atlas is None else _ptr(widths), S, Hc, Wa, _stream())
+
+
 # ---------------------------------------------------------------------- COCO-protocol evaluation (csrc/cocoeval.hip)
 COCO_MAX_GT = 512                  # RADET_COCO_MAX_GT of include/radet_hip.h: ground truths per (category, image) segment
 COCO_ERR_OVERSIZE = -3             # RADET_ERR_COCO_OVERSIZE

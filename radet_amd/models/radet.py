@@ -155,6 +155,23 @@ class RADet(nn.Module):
         dets = self.runtime().detect_aug(imgs, img_metas, self.test_cfg, rescale)
         return [bbox2result(b, l, self.bbox_head.num_classes) for b, l in dets]
 
+    def show_result(self, img, result, score_thr=0.3, bbox_color=(72, 101, 241), text_color=(72, 101, 241), mask_color=None,
+                    thickness=2, font_scale=0.5, font_size=13, win_name="", fig_size=(15, 10), show=False, wait_time=0,
+                    out_file=None):
+        """BaseDetector.show_result (detectors/base.py:270): the per-class `result` drawn over `img` (a file name or a BGR
+        ndarray) by core.visualization.imshow_det_bboxes, with this model's CLASSES as names; returns the BGR ndarray.  An
+        out_file switches show off, as in the reference."""
+        from ..core.visualization import imshow_det_bboxes, result_to_dets
+        bboxes, labels = result_to_dets(result)
+        classes = getattr(self, "CLASSES", None)
+        names = None if classes is None else [str(c) for c in classes]
+        if out_file is not None:
+            show = False
+        return imshow_det_bboxes(img, bboxes, labels, None, class_names=names, score_thr=score_thr, bbox_color=bbox_color,
+                                 text_color=text_color, mask_color=mask_color, thickness=thickness, font_scale=font_scale,
+                                 font_size=font_size, win_name=win_name, fig_size=fig_size, show=show, wait_time=wait_time,
+                                 out_file=out_file)
+
     def _parse_losses(self, losses):
         """detectors/base.py:185-216, same (loss, log_vars) result.  The logged scalars of the step are stacked into ONE
         tensor: one all-reduce (mean over the ranks) and one device -> host copy for all of them, instead of one

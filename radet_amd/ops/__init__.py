@@ -10,7 +10,7 @@ from .. import kernels as K
 
 __all__ = ["vote_nms", "global_vote_nms", "cluster_nms", "batched_nms", "soft_nms", "MBD_box2distance", "GDT_box2distance", "MBD", "GDT",
            "mbd_batch", "gdt_batch", "border_seeds", "resize_batch", "gaussian_blur9_batch", "sobel_edge_batch", "crop_detections",
-           "Crops", "merge_view_candidates", "plan_tiles", "merge_tile_candidates"]
+           "Crops", "merge_view_candidates", "plan_tiles", "merge_tile_candidates", "draw_detections", "build_atlas"]
 
 _MAX = 65536      # 16-bit positions in the kernel's sort keys (above 8192 the sorts run in global memory)
 
@@ -465,3 +465,4 @@ class GDT_box2distance:
 from .crops import Crops, crop_detections  # noqa: E402  (RoI crops of detections: its own module, it needs _dev from here)
 from .tta import merge_view_candidates  # noqa: E402  (test-time augmentation: the views' candidates merged per image)
 from .tiles import merge_tile_candidates, plan_tiles  # noqa: E402  (tiled inference: the tile plan, the rows' candidates merged per image)
+from .draw import build_atlas, draw_detections  # noqa: E402  (detections drawn on frames: one overlay launch)
