@@ -1433,22 +1433,26 @@ extern "C" int radet_relu_bwd_a(const float* dy, const float* addend, const floa
 extern "C" int radet_relu_bwd(const float* dy, const float* addend, const float* act, float* dx, size_t n, void* stream) {
     return radet_relu_bwd_a(dy, addend, act, dx, n, nullptr, stream);
 }
-// largest magnitude of n floats (n % 4 == 0) -> raises *amax (for tensors whose producer does not track it; not reset here)
-__global__ void absmax_kernel(const float* __restrict__ x, size_t n4, unsigned* amax) {
+// largest magnitude of n floats (x 16-byte aligned) -> raises *amax (for tensors whose producer does not track it; not reset
+// here).  float4 loads over the first n / 4 * 4 floats; the last n % 4 (an NHWC buffer of 3 or 21 channels at the module-API
+// boundary) are read one by one by the first three lanes of workgroup 0.
+__global__ void absmax_kernel(const float* __restrict__ x, size_t n4, int tail, unsigned* amax) {
     float am = 0.f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const float4 v = reinterpret_cast<const float4*>(x)[i];
         am = fmaxf(fmaxf(am, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
+    if (blockIdx.x == 0 && (int)threadIdx.x < tail) am = fmaxf(am, fabsf(x[4 * n4 + threadIdx.x]));
     radet_amax_publish(am, amax);
 }
 extern "C" int radet_amax_slot_words(void) { return RADET_AMAX_WORDS * RADET_AMAX_STRIDE; }
 extern "C" int radet_absmax(const float* x, size_t n, void* amax, void* stream) {
-    if (n % 4 || amax == nullptr) return RADET_ERR_ARG;
+    if (amax == nullptr) return RADET_ERR_ARG;
     if (n == 0) return RADET_OK;
     const size_t n4 = n / 4;
     const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(absmax_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n4, (unsigned*)amax);
+    hipLaunchKernelGGL(absmax_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, (hipStream_t)stream, x, n4, (int)(n % 4),
+                       (unsigned*)amax);
     return radet_check_launch();
 }
 extern "C" int radet_relu_bwd_h(const void* dy, const void* addend, const void* act, void* dx, size_t n, void* stream) {

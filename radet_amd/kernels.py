@@ -756,7 +756,7 @@ def amax_slot(t, compute=False):
 
 
 def absmax(t, slot):
-    """raise `slot` to the largest magnitude of the fp32 tensor t (contiguous, numel % 4 == 0)"""
+    """raise `slot` to the largest magnitude of the fp32 tensor t (contiguous, any element count)"""
     assert t.dtype == torch.float32 and t.is_contiguous()
     _lib.call("radet_absmax", _ptr(t), C.c_size_t(t.numel()), _ptr(slot), _stream())
 
@@ -1335,7 +1335,7 @@ def nchw_to_nhwc(x, y, B, ch, H, W):
         return
     _lib.call("radet_nchw_to_nhwc", _ptr(x), _ptr(y), B, ch, H, W, _stream())
     sl = amax_slot(y)
-    if sl is not None and y.numel() % 4 == 0:          # data entering an engine buffer from outside: its amax slot follows
+    if sl is not None:                                 # data entering an engine buffer from outside: its amax slot follows
         absmax(y, sl)
 
 
