@@ -69,9 +69,9 @@ typedef struct RadetConvDesc {
  * non-negative float that is >= every |element| (the largest magnitude, or any bound on it), e = 141 - biased_exponent(slot)
  * (0 for a zero slot).  Slots are maintained by the kernels that WRITE a tensor: they raise one of the 64 words (chosen by
  * workgroup and wave: thousands of waves raising ONE address serialise) with atomicMax on the bit pattern -- order
- * independent, hence deterministic -- in conv epilogues (RadetScales.y_amax), the _a variants of the elementwise kernels and
- * radet_absmax; or they store a bound they can derive before writing into word 0 (GroupNorm: radet_gn_relu_fwd_q / _bwd_q,
- * radet_split_pairs; the other words must be zero).  The caller zeroes a slot before the first kernel of a step that
+ * independent, hence deterministic -- in conv epilogues (RadetScales.y_amax), the y_amax / dst_amax / dx_amax arguments of the
+ * elementwise layer kernels and radet_absmax; or they store a bound they can derive before writing into word 0 (GroupNorm:
+ * planes_amax of radet_gn_relu_fwd / _bwd with RADET_LAYER_PAIRS, radet_split_pairs; the other words must be zero).  The caller zeroes a slot before the first kernel of a step that
  * raises it.  Host struct of device pointers (each to a 64-word slot): */
 #define RADET_AMAX_WORDS 64
 typedef struct RadetScales {
@@ -243,10 +243,23 @@ typedef struct RadetWgradJob {
 int radet_conv2d_wgrad_group(const RadetWgradJob* jobs, int njobs, int flags, void* stream);
 int radet_fold_weights(const RadetConvDesc* table_dev, int nconv, void* stream);
 int radet_unfold_grads(const RadetConvDesc* table_dev, int nconv, int max_cout, void* stream);
-/* stem: 7x7/2 conv (3->64) + folded BN + ReLU, NCHW image in, NHWC out (resnet.py:558-570,627-629) */
-int radet_stem_conv_bn_relu(const float* img_nchw, const float* wf_ohwi, const float* bias, float* y_nhwc, int B,
-                            int H, int W, void* stream);
-int radet_maxpool3x3s2(const float* x, float* y, int B, int H, int W, int C, void* stream); /* resnet.py:570,630 */
+/* ---- the memory-bound layers: stem, max-pool, GroupNorm + ReLU forward / backward, upsample-add forward / backward, ReLU
+ * backward -- one entry point each.  `flags` is a packed word, RADET_LAYER_* below; any other bit is refused with -1.  The
+ * `*_amax` arguments are amax slots (see RadetScales) and may be NULL; a slot that a kernel RAISES to the largest magnitude it
+ * stores is not reset here.  Every argument check precedes the first HIP call. */
+enum {
+    RADET_LAYER_BF16 = 0x1,    /* bf16 storage: the activation tensors are bf16, not fp32 (parameters, statistics and workspaces
+                                  stay fp32).  Refused together with a plane output, an amax slot or RADET_LAYER_PAIRS. */
+    RADET_LAYER_PAIRS = 0x2    /* the optional plane output holds fp16 plane pairs (scaled; its amax slot is required), not bf16
+                                  plane triples.  Max-pool and GroupNorm only. */
+};
+/* stem: 7x7/2 conv (3->64) + folded BN + ReLU, NCHW fp32 image in, NHWC out (resnet.py:558-570,627-629); y_amax is raised */
+int radet_stem_conv_bn_relu(const float* img_nchw, const float* wf_ohwi, const float* bias, void* y_nhwc, int B, int H, int W,
+                            int flags, void* y_amax, void* stream);
+/* max-pool 3x3 / 2 (resnet.py:570,630), C % 4 == 0; y_amax is raised.  yq (may be NULL; needs RADET_LAYER_PAIRS, C % 32 == 0,
+ * yq_amax and x_amax): the output once more as fp16 plane pairs, scaled by x's amax slot x_amax, whose bits go to yq_amax */
+int radet_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, int flags, void* y_amax, void* yq, void* yq_amax,
+                       const void* x_amax, void* stream);
 /* Trainable stem (ResNet(frozen_stages=-1): conv1 / bn1 get gradients, resnet.py:572-588).  Backward of the max-pool fused with
  * the stem's ReLU: ds = [s > 0] * (dpool routed to the first maximum of each 3x3 / 2 window in row-major order -- the element
  * torch's MaxPool2d backward picks); s = stem output [B,H,W,C], dpool [B,Ho,Wo,C], fp32, C % 4 == 0. */
@@ -260,40 +273,34 @@ int radet_stem_wgrad(const float* img_nchw, const float* ds, float* slabs, float
 
 /* ---- GroupNorm(32, 256) + ReLU over a multi-level buffer (atss_head.py:32,60-76 via mmcv ConvModule) */
 int radet_gn_workspace_floats(int B, const int* seg_desc, int nseg);
-int radet_gn_relu_fwd(const float* z, const float* gamma, const float* beta, float* y, float* stats /*[nseg*B][32][2]*/,
-                      float* partial_ws, int B, int C, int groups, float eps, int relu, const int* seg_desc, int nseg,
-                      void* stream);
-int radet_gn_relu_bwd(const float* dy, const float* z, const float* stats, const float* gamma, const float* beta,
-                      float* dz, float* dgamma, float* dbeta, float* partial_ws, int B, int C, int groups, int relu,
-                      const int* seg_desc, int nseg, void* stream);
+/* forward of one tensor (z1 == NULL) or of two tensors of one geometry (cls_convs[i].gn / reg_convs[i].gn) in one pair of
+ * launches.  Per tensor: z in; y (z's type, may be NULL) and / or planes (may be NULL, fp32 z only) out -- bf16 plane triples, or
+ * with RADET_LAYER_PAIRS fp16 plane pairs scaled by the power of two of a bound on |y| that needs no pass over the data
+ * (max|gamma| sqrt(n - 1) + max|beta| for the n values of a group), which is stored to planes_amax; stats [nseg*B][32][2];
+ * y_amax is raised to y's largest magnitude, zhat_amax to the largest normalised magnitude.  C == 256, groups == 32. */
+int radet_gn_relu_fwd(const void* z0, const float* gamma0, const float* beta0, void* y0, void* planes0, float* stats0,
+                      float* partial_ws0, void* y_amax0, void* planes_amax0, void* zhat_amax0, const void* z1,
+                      const float* gamma1, const float* beta1, void* y1, void* planes1, float* stats1, float* partial_ws1,
+                      void* y_amax1, void* planes_amax1, void* zhat_amax1, int B, int C, int groups, float eps, int relu,
+                      int flags, const int* seg_desc, int nseg, void* stream);
+/* backward: dz in dy's type (may be NULL) and / or as planes (may be NULL, fp32 only) -- bf16 plane triples, or with
+ * RADET_LAYER_PAIRS fp16 plane pairs scaled by the bound rstd_max max|gamma| dy_amax (2 + zhat_max), stored to planes_amax;
+ * dy_amax = the amax slot of dy (required with pairs), zhat_amax from the forward call (NULL: sqrt(n - 1)). */
+int radet_gn_relu_bwd(const void* dy, const void* z, const float* stats, const float* gamma, const float* beta, void* dz,
+                      void* planes, float* dgamma, float* dbeta, float* partial_ws, int B, int C, int groups, int relu,
+                      int flags, const int* seg_desc, int nseg, void* stream, const void* dy_amax, const void* zhat_amax,
+                      void* planes_amax);
 
-/* ---- FPN top-down: dst += nearest_upsample(src) and its adjoint (fpn.py:182-191) */
-int radet_upsample_add(float* dst, const float* src, int B, int Ho, int Wo, int Hi, int Wi, int C, void* stream);
-int radet_upsample_add_bwd(float* dsrc, const float* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C, void* stream);
-/* ReLU backward for a junction with no producing GEMM: dx = (dy + addend?) * [act > 0]; n % 4 == 0 */
-int radet_relu_bwd(const float* dy, const float* addend, const float* act, float* dx, size_t n, void* stream);
-/* bf16-storage variants (activation tensors are bf16; parameters, statistics and workspaces stay fp32) and the row
- * converter used at the fp32 boundaries (loss gradients, module outputs) */
-int radet_stem_conv_bn_relu_h(const float* img_nchw, const float* wf_ohwi, const float* bias, void* y_nhwc, int B, int H,
-                              int W, void* stream);
-int radet_maxpool3x3s2_h(const void* x, void* y, int B, int H, int W, int C, void* stream);
-/* Two tensors of one geometry (cls_convs[i].gn / reg_convs[i].gn, atss_head.py:60-76) in one pair of launches. */
-int radet_gn_relu_fwd_pair(const float* z0, const float* gamma0, const float* beta0, float* y0, float* stats0,
-                           float* partial_ws0, const float* z1, const float* gamma1, const float* beta1, float* y1,
-                           float* stats1, float* partial_ws1, int B, int C, int groups, float eps, int relu,
-                           const int* seg_desc, int nseg, void* stream);
-int radet_gn_relu_fwd_pair_h(const void* z0, const float* gamma0, const float* beta0, void* y0, float* stats0,
-                             float* partial_ws0, const void* z1, const float* gamma1, const float* beta1, void* y1,
-                             float* stats1, float* partial_ws1, int B, int C, int groups, float eps, int relu,
-                             const int* seg_desc, int nseg, void* stream);
-int radet_gn_relu_fwd_h(const void* z, const float* gamma, const float* beta, void* y, float* stats, float* partial_ws,
-                        int B, int C, int groups, float eps, int relu, const int* seg_desc, int nseg, void* stream);
-int radet_gn_relu_bwd_h(const void* dy, const void* z, const float* stats, const float* gamma, const float* beta, void* dz,
-                        float* dgamma, float* dbeta, float* partial_ws, int B, int C, int groups, int relu,
-                        const int* seg_desc, int nseg, void* stream);
-int radet_upsample_add_h(void* dst, const void* src, int B, int Ho, int Wo, int Hi, int Wi, int C, void* stream);
-int radet_upsample_add_bwd_h(void* dsrc, const void* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C, void* stream);
-int radet_relu_bwd_h(const void* dy, const void* addend, const void* act, void* dx, size_t n, void* stream);
+/* ---- FPN top-down: dst += nearest_upsample(src) and its adjoint (fpn.py:182-191); C % 4 == 0; the written tensor's slot
+ * (dst_amax / dsrc_amax) is raised */
+int radet_upsample_add(void* dst, const void* src, int B, int Ho, int Wo, int Hi, int Wi, int C, int flags, void* dst_amax,
+                       void* stream);
+int radet_upsample_add_bwd(void* dsrc, const void* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C, int flags,
+                           void* dsrc_amax, void* stream);
+/* ReLU backward for a junction with no producing GEMM: dx = (dy + addend?) * [act > 0]; n % 4 == 0; dx_amax is raised */
+int radet_relu_bwd(const void* dy, const void* addend, const void* act, void* dx, size_t n, int flags, void* dx_amax,
+                   void* stream);
+/* the row converter used at the fp32 boundaries of the bf16-storage mode (loss gradients, module outputs) */
 int radet_convert_rows(const void* src, void* dst, size_t rows, int ncols, int src_ld, int src_off, int dst_ld,
                        int dst_off, int to_bf16, void* stream);
 /* ---- bf16 plane triples ("planes"): the operand format of the default fp32 arithmetic's conv GEMMs.  An fp32 value x is
@@ -315,51 +322,9 @@ int radet_merge_planes(const void* src_planes, float* dst, size_t rows, int C, i
 int radet_split_pairs(const float* src, void* dst_pairs, size_t rows, int C, int src_ld, const void* src_amax, void* dst_amax,
                       void* stream);
 int radet_merge_pairs(const void* src_pairs, float* dst, size_t rows, int C, int dst_ld, const void* amax, void* stream);
-/* GroupNorm + ReLU with plane-pair outputs.  forward: y (fp32, may be NULL; y_amax, may be NULL, is raised to its largest
- * magnitude) and / or yq (plane pairs, may be NULL) scaled by the power of two of a bound on |y| that needs no pass over the
- * data -- max|gamma| sqrt(n - 1) + max|beta| for the n values of a group -- which is stored to yq_amax; zhat_amax (may be
- * NULL) is raised to the largest normalised magnitude.  backward: dz (fp32, may be NULL) and / or dzq (plane pairs) scaled by
- * the bound rstd_max max|gamma| dy_amax (2 + zhat_max), stored to dzq_amax; dy_amax = the amax slot of dy (required with
- * dzq), zhat_amax from the forward call (NULL: sqrt(n - 1)). */
-int radet_gn_relu_fwd_q(const float* z, const float* gamma, const float* beta, float* y, void* yq, float* stats,
-                        float* partial_ws, int B, int C, int groups, float eps, int relu, const int* seg_desc, int nseg,
-                        void* stream, void* y_amax, void* yq_amax, void* zhat_amax);
-int radet_gn_relu_fwd_pair_q(const float* z0, const float* gamma0, const float* beta0, float* y0, void* yq0, float* stats0,
-                             float* partial_ws0, void* y_amax0, void* yq_amax0, void* zhat_amax0, const float* z1,
-                             const float* gamma1, const float* beta1, float* y1, void* yq1, float* stats1,
-                             float* partial_ws1, void* y_amax1, void* yq_amax1, void* zhat_amax1, int B, int C, int groups,
-                             float eps, int relu, const int* seg_desc, int nseg, void* stream);
-int radet_gn_relu_bwd_q(const float* dy, const float* z, const float* stats, const float* gamma, const float* beta, float* dz,
-                        void* dzq, float* dgamma, float* dbeta, float* partial_ws, int B, int C, int groups, int relu,
-                        const int* seg_desc, int nseg, void* stream, const void* dy_amax, const void* zhat_amax,
-                        void* dzq_amax);
-/* Elementwise kernels that also raise the amax slot of the tensor they write (not reset here), and a stand-alone pass for
- * tensors whose producer does not (n % 4 == 0). */
-int radet_maxpool3x3s2_a(const float* x, float* y, int B, int H, int W, int C, void* y_amax, void* stream);
-/* the max-pool with its output once more as fp16 plane pairs (scaled by x's amax slot, whose bits go to yq_amax), and the
- * stem with an amax slot for its output */
-int radet_maxpool3x3s2_q(const float* x, float* y, int B, int H, int W, int C, void* y_amax, void* yq, void* yq_amax,
-                         const void* x_amax, void* stream);
-int radet_stem_conv_bn_relu_a(const float* img_nchw, const float* wf_ohwi, const float* bias, float* y_nhwc, int B, int H, int W,
-                              void* y_amax, void* stream);
-int radet_upsample_add_a(float* dst, const float* src, int B, int Ho, int Wo, int Hi, int Wi, int C, void* dst_amax,
-                         void* stream);
-int radet_upsample_add_bwd_a(float* dsrc, const float* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C, void* dsrc_amax,
-                             void* stream);
-int radet_relu_bwd_a(const float* dy, const float* addend, const float* act, float* dx, size_t n, void* dx_amax, void* stream);
+/* A stand-alone amax pass for tensors whose producer raises no slot (any n). */
 int radet_absmax(const float* x, size_t n, void* amax, void* stream);
 int radet_amax_slot_words(void);   /* 32-bit words to allocate (and zero) per amax slot */
-/* GroupNorm + ReLU with plane outputs: y / dz as fp32 (may be NULL) and / or as planes (yp / dzp, may be NULL) */
-int radet_gn_relu_fwd_p(const float* z, const float* gamma, const float* beta, float* y, void* yp, float* stats,
-                        float* partial_ws, int B, int C, int groups, float eps, int relu, const int* seg_desc, int nseg,
-                        void* stream);
-int radet_gn_relu_fwd_pair_p(const float* z0, const float* gamma0, const float* beta0, float* y0, void* yp0, float* stats0,
-                             float* partial_ws0, const float* z1, const float* gamma1, const float* beta1, float* y1,
-                             void* yp1, float* stats1, float* partial_ws1, int B, int C, int groups, float eps, int relu,
-                             const int* seg_desc, int nseg, void* stream);
-int radet_gn_relu_bwd_p(const float* dy, const float* z, const float* stats, const float* gamma, const float* beta,
-                        float* dz, void* dzp, float* dgamma, float* dbeta, float* partial_ws, int B, int C, int groups,
-                        int relu, const int* seg_desc, int nseg, void* stream);
 int radet_nchw_to_nhwc(const float* x, float* y, int B, int C, int H, int W, void* stream);
 int radet_nhwc_to_nchw(const float* x, float* y, int B, int C, int H, int W, void* stream);
 

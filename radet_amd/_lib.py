@@ -58,15 +58,6 @@ SIGNATURES = {
     "radet_conv2d_wgrad_s": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "radet_split_pairs": (_i, [_p, _p, _sz, _i, _i, _p, _p, _p]),
     "radet_merge_pairs": (_i, [_p, _p, _sz, _i, _i, _p, _p]),
-    "radet_gn_relu_fwd_q": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _i, _p, _p, _p, _p]),
-    "radet_gn_relu_fwd_pair_q": (_i, [_p] * 20 + [_i, _i, _i, _f, _i, _p, _i, _p]),
-    "radet_gn_relu_bwd_q": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
-    "radet_maxpool3x3s2_a": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
-    "radet_maxpool3x3s2_q": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    "radet_stem_conv_bn_relu_a": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p]),
-    "radet_upsample_add_a": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
-    "radet_upsample_add_bwd_a": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
-    "radet_relu_bwd_a": (_i, [_p, _p, _p, _p, _sz, _p, _p]),
     "radet_absmax": (_i, [_p, _sz, _p, _p]),
     "radet_amax_slot_words": (_i, []),
     "radet_pred3x3_patch": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p]),
@@ -75,19 +66,17 @@ SIGNATURES = {
     "radet_conv2d_wgrad_group": (_i, [_p, _i, _i, _p]),
     "radet_fold_weights": (_i, [_p, _i, _p]),
     "radet_unfold_grads": (_i, [_p, _i, _i, _p]),
-    "radet_stem_conv_bn_relu": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-    "radet_maxpool3x3s2": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "radet_stem_conv_bn_relu": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "radet_maxpool3x3s2": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "radet_maxpool3x3s2_bwd_relu": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "radet_stem_wgrad_splits": (_i, [_i, _i, _i]),
     "radet_stem_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "radet_gn_workspace_floats": (_i, [_i, _p, _i]),
-    "radet_gn_relu_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _i, _p]),
-    "radet_gn_relu_fwd_pair": (_i, [_p] * 12 + [_i, _i, _i, _f, _i, _p, _i, _p]),
-    "radet_gn_relu_fwd_pair_h": (_i, [_p] * 12 + [_i, _i, _i, _f, _i, _p, _i, _p]),
-    "radet_gn_relu_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
-    "radet_upsample_add": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "radet_upsample_add_bwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "radet_relu_bwd": (_i, [_p, _p, _p, _p, _sz, _p]),
+    "radet_gn_relu_fwd": (_i, [_p] * 20 + [_i, _i, _i, _f, _i, _i, _p, _i, _p]),
+    "radet_gn_relu_bwd": (_i, [_p] * 10 + [_i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "radet_upsample_add": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "radet_upsample_add_bwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "radet_relu_bwd": (_i, [_p, _p, _p, _p, _sz, _i, _p, _p]),
     "radet_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "radet_nhwc_to_nchw": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "radet_head_loss_ws_ints": (_i, [_i]),
@@ -110,19 +99,9 @@ SIGNATURES = {
     "radet_cutout_f32": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p]),
     "radet_gaussian_blur9_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "radet_sobel_edge": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
-    "radet_stem_conv_bn_relu_h": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-    "radet_maxpool3x3s2_h": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "radet_gn_relu_fwd_h": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _i, _p]),
-    "radet_gn_relu_bwd_h": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
-    "radet_upsample_add_h": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "radet_upsample_add_bwd_h": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "radet_relu_bwd_h": (_i, [_p, _p, _p, _p, _sz, _p]),
     "radet_convert_rows": (_i, [_p, _p, _sz, _i, _i, _i, _i, _i, _i, _p]),
     "radet_split_planes": (_i, [_p, _p, _sz, _i, _i, _p]),
     "radet_merge_planes": (_i, [_p, _p, _sz, _i, _i, _p]),
-    "radet_gn_relu_fwd_p": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _i, _p]),
-    "radet_gn_relu_fwd_pair_p": (_i, [_p] * 14 + [_i, _i, _i, _f, _i, _p, _i, _p]),
-    "radet_gn_relu_bwd_p": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
     "radet_mbd_ws_bytes": (_sz, [_sz]),
     "radet_mbd": (_i, [_p, _p, _i, _p, _p, _f, _i, _i, _p, _sz, _p, _p]),
     "radet_gdt": (_i, [_p, _p, _i, _p, _p, _p, _p, _p]),

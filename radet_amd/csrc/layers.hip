@@ -148,28 +148,38 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ img
   if (y_amax) radet_amax_publish(am, y_amax);                  // (persistent workgroups: one atomic per wave and launch)
 }
 
-extern "C" int radet_stem_conv_bn_relu_a(const float* img_nchw, const float* wf_ohwi, const float* bias, float* y_nhwc,
-                                         int B, int H, int W, void* y_amax, void* stream) {
+// ---- host side of the seven layer entry points (stem, max-pool, GroupNorm forward / backward, upsample-add forward / backward,
+// ReLU backward): one C function per operation; the storage type and the form of the optional plane output come in its
+// RADET_LAYER_* flag word (radet_hip.h), the amax slots as pointers that may be NULL.  Every check precedes the first HIP call.
+
+// the flag word is refused when it has a bit outside `known`, or asks for bf16 storage together with anything the bf16
+// instantiations do not take (`extras`: a plane output or an amax slot was given; fp16 pairs)
+static bool layer_flags_bad(int flags, int known, bool extras) {
+    if (flags & ~known) return true;
+    return (flags & RADET_LAYER_BF16) && (extras || (flags & RADET_LAYER_PAIRS));
+}
+
+// grid of the grid-stride elementwise kernels: one thread of 256 per item, at most 4096 workgroups
+static dim3 grid1d(size_t items) {
+    const size_t blocks = (items + 255) / 256;
+    return dim3((unsigned)(blocks < 4096 ? blocks : 4096));
+}
+
+template <class T>
+static int stem_launch(const float* img, const float* wf, const float* bias, void* y, int B, int H, int W, void* y_amax,
+                       void* stream) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const int ntiles = ((Wo + STEM_TC - 1) / STEM_TC) * ((Ho + STEM_TR - 1) / STEM_TR) * B;
     dim3 grid(ntiles < 512 ? ntiles : 512);                      // 2 workgroups per CU (57 KiB of LDS each)
-    hipLaunchKernelGGL(stem_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, img_nchw, wf_ohwi, bias, y_nhwc, H, W,
-                       Ho, Wo, B, (unsigned*)y_amax);
+    hipLaunchKernelGGL(stem_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, img, wf, bias, (T*)y, H, W, Ho, Wo, B,
+                       (unsigned*)y_amax);
     return radet_check_launch();
 }
-extern "C" int radet_stem_conv_bn_relu(const float* img_nchw, const float* wf_ohwi, const float* bias, float* y_nhwc,
-                                       int B, int H, int W, void* stream) {
-    return radet_stem_conv_bn_relu_a(img_nchw, wf_ohwi, bias, y_nhwc, B, H, W, nullptr, stream);
-}
-
-extern "C" int radet_stem_conv_bn_relu_h(const float* img_nchw, const float* wf_ohwi, const float* bias, void* y_nhwc,
-                                         int B, int H, int W, void* stream) {
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int ntiles = ((Wo + STEM_TC - 1) / STEM_TC) * ((Ho + STEM_TR - 1) / STEM_TR) * B;
-    dim3 grid(ntiles < 512 ? ntiles : 512);
-    hipLaunchKernelGGL(stem_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, img_nchw, wf_ohwi, bias,
-                       (__bf16*)y_nhwc, H, W, Ho, Wo, B);
-    return radet_check_launch();
+extern "C" int radet_stem_conv_bn_relu(const float* img_nchw, const float* wf_ohwi, const float* bias, void* y_nhwc, int B,
+                                       int H, int W, int flags, void* y_amax, void* stream) {
+    if (layer_flags_bad(flags, RADET_LAYER_BF16, y_amax != nullptr)) return RADET_ERR_ARG;
+    return (flags & RADET_LAYER_BF16) ? stem_launch<__bf16>(img_nchw, wf_ohwi, bias, y_nhwc, B, H, W, nullptr, stream)
+                                      : stem_launch<float>(img_nchw, wf_ohwi, bias, y_nhwc, B, H, W, y_amax, stream);
 }
 
 // ------------------------------------------------------------------------------------------ maxpool
@@ -232,42 +242,26 @@ __global__ void maxpool_kernel(const T* __restrict__ x, T* __restrict__ y, int B
     if (amax) radet_amax_publish(am, amax);
 }
 
-// _a variants (this one and radet_upsample_add_a / _bwd_a, radet_relu_bwd_a below): the same kernels, which also raise the
-// output tensor's amax slot (4 bytes, device) to the largest magnitude they store -- the scale source of the fp16 hi / lo
-// conv arithmetic (common.h "h2").  The slot is NOT reset here.
-extern "C" int radet_maxpool3x3s2_a(const float* x, float* y, int B, int H, int W, int C, void* y_amax, void* stream) {
+template <class T>
+static int maxpool_launch(const void* x, void* y, int B, int H, int W, int C, void* y_amax, void* yq, void* yq_amax,
+                          const void* x_amax, void* stream) {
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const size_t total = (size_t)B * Ho * ((Wo + 1) / 2) * (C / 4);
+    hipLaunchKernelGGL(maxpool_kernel<T>, grid1d(total), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, B, H, W, C / 4,
+                       Ho, Wo, (unsigned*)y_amax, (_Float16*)yq, (unsigned*)yq_amax, (const unsigned*)x_amax);
+    return radet_check_launch();
+}
+// y_amax (may be NULL; here and in radet_upsample_add / _bwd, radet_relu_bwd below): the output tensor's amax slot, raised to
+// the largest magnitude the kernel stores -- the scale source of the fp16 hi / lo conv arithmetic (common.h "h2").  The slot
+// is NOT reset here.  yq (may be NULL; RADET_LAYER_PAIRS): the output once more as fp16 plane pairs (rows [2][C],
+// C % 32 == 0) scaled by the power of two of x's amax slot (x_amax; its bits are stored to yq_amax)
+extern "C" int radet_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, int flags, void* y_amax, void* yq,
+                                  void* yq_amax, const void* x_amax, void* stream) {
+    if (layer_flags_bad(flags, RADET_LAYER_BF16 | RADET_LAYER_PAIRS, y_amax || yq || yq_amax || x_amax)) return RADET_ERR_ARG;
     if (C % 4) return RADET_ERR_ARG;
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const size_t total = (size_t)B * Ho * ((Wo + 1) / 2) * (C / 4);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(maxpool_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C / 4, Ho, Wo,
-                       (unsigned*)y_amax);
-    return radet_check_launch();
-}
-extern "C" int radet_maxpool3x3s2(const float* x, float* y, int B, int H, int W, int C, void* stream) {
-    return radet_maxpool3x3s2_a(x, y, B, H, W, C, nullptr, stream);
-}
-// ... and the output once more as fp16 plane pairs yq (rows [2][C], C % 32 == 0) scaled by the power of two of x's amax slot
-// (x_amax; its bits are stored to yq_amax)
-extern "C" int radet_maxpool3x3s2_q(const float* x, float* y, int B, int H, int W, int C, void* y_amax, void* yq, void* yq_amax,
-                                    const void* x_amax, void* stream) {
-    if (C % 32 || yq == nullptr || yq_amax == nullptr || x_amax == nullptr) return RADET_ERR_ARG;
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const size_t total = (size_t)B * Ho * ((Wo + 1) / 2) * (C / 4);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(maxpool_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C / 4, Ho, Wo,
-                       (unsigned*)y_amax, (_Float16*)yq, (unsigned*)yq_amax, (const unsigned*)x_amax);
-    return radet_check_launch();
-}
-
-extern "C" int radet_maxpool3x3s2_h(const void* x, void* y, int B, int H, int W, int C, void* stream) {
-    if (C % 4) return RADET_ERR_ARG;
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const size_t total = (size_t)B * Ho * ((Wo + 1) / 2) * (C / 4);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(maxpool_kernel<__bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, (__bf16*)y,
-                       B, H, W, C / 4, Ho, Wo);
-    return radet_check_launch();
+    if (yq != nullptr && (C % 32 || !(flags & RADET_LAYER_PAIRS) || yq_amax == nullptr || x_amax == nullptr)) return RADET_ERR_ARG;
+    if (flags & RADET_LAYER_BF16) return maxpool_launch<__bf16>(x, y, B, H, W, C, nullptr, nullptr, nullptr, nullptr, stream);
+    return maxpool_launch<float>(x, y, B, H, W, C, y_amax, yq, yq ? yq_amax : nullptr, yq ? x_amax : nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------ trainable stem (frozen_stages = -1)
@@ -926,106 +920,73 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnFwdArgs<T> args, 
     }
 }
 
-template <class T>
-static int gn_relu_fwd_impl(const T* z, const float* gamma, const float* beta, T* y, float* stats,
-                            float* partial_ws, int B, int C, int groups, float eps, int relu, const int* seg_desc,
-                            int nseg, void* stream, const GnFwdSet<T>* second = nullptr, __bf16* yp = nullptr,
-                            unsigned* yq_amax = nullptr, unsigned* y_amax = nullptr, unsigned* zhat_amax = nullptr) {
-    if (C != 256 || groups != 32 || (y == nullptr && yp == nullptr)) return RADET_ERR_ARG;
-    RadetSegs segs;
-    if (nseg < 1 || nseg > RADET_MAX_SEG) return RADET_ERR_ARG;
-    segs.nseg = nseg;
+// seg_desc (nseg x {Hi, Wi, Ho, Wo, in_row_off, row_begin}) -> RadetSegs; false when nseg is out of range
+static bool gn_segs(const int* seg_desc, int nseg, int B, RadetSegs* segs) {
+    if (nseg < 1 || nseg > RADET_MAX_SEG) return false;
+    segs->nseg = nseg;
     for (int l = 0; l < nseg; ++l) {
         const int* d = seg_desc + 6 * l;
-        segs.s[l].Hi = d[0]; segs.s[l].Wi = d[1]; segs.s[l].Ho = d[2]; segs.s[l].Wo = d[3];
-        segs.s[l].in_row_off = d[4]; segs.s[l].row_begin = d[5]; segs.s[l].row_end = d[5] + B * d[2] * d[3];
+        segs->s[l].Hi = d[0]; segs->s[l].Wi = d[1]; segs->s[l].Ho = d[2]; segs->s[l].Wo = d[3];
+        segs->s[l].in_row_off = d[4]; segs->s[l].row_begin = d[5]; segs->s[l].row_end = d[5] + B * d[2] * d[3];
     }
+    return true;
+}
+
+// One tensor's pointers of radet_gn_relu_fwd, as they arrive.  z: fp32 (bf16 with RADET_LAYER_BF16).  Outputs: y (z's type, may
+// be NULL) and / or planes (may be NULL; fp32 z only) -- the tower activations are read by conv GEMMs only, which take plane
+// operands (radet_conv2d_igemm RADET_TILE_P3): bf16 plane triples (rows [3][256]), or with RADET_LAYER_PAIRS (fp16 hi / lo
+// arithmetic, common.h "h2") fp16 plane pairs (rows [2][256]), and planes_amax then receives the bound on |y| whose power of
+// two scales them.  y_amax (may be NULL) is raised to y's largest magnitude, zhat_amax (may be NULL) to the largest |zhat| --
+// radet_gn_relu_bwd's bound on dz uses it.
+struct GnFwdPtrs {
+    const void* z;
+    const float *gamma, *beta;
+    void *y, *planes;
+    float *stats, *ws;
+    void *y_amax, *planes_amax, *zhat_amax;
+};
+static bool gn_fwd_set_bad(const GnFwdPtrs& s, int flags) {
+    if (s.y == nullptr && s.planes == nullptr) return true;
+    if ((flags & RADET_LAYER_PAIRS) && s.planes != nullptr && s.planes_amax == nullptr) return true;
+    return layer_flags_bad(flags, RADET_LAYER_BF16 | RADET_LAYER_PAIRS, s.planes || s.y_amax || s.planes_amax || s.zhat_amax);
+}
+template <class T>
+static GnFwdSet<T> gn_fwd_set(const GnFwdPtrs& s, int flags) {
+    const bool pairs = (flags & RADET_LAYER_PAIRS) && s.planes != nullptr;
+    return GnFwdSet<T>{(const T*)s.z, s.ws, s.gamma, s.beta, (T*)s.y, s.stats, (__bf16*)s.planes,
+                       pairs ? (unsigned*)s.planes_amax : nullptr, (unsigned*)s.y_amax, (unsigned*)s.zhat_amax};
+}
+
+template <class T>
+static int gn_fwd_launch(const GnFwdPtrs& a, const GnFwdPtrs* b, int B, float eps, int relu, int flags, const RadetSegs& segs,
+                         void* stream) {
     const int chunks = gn_total_chunks(segs, B);
     hipStream_t st = (hipStream_t)stream;
     GnFwdArgs<T> args;
-    args.p[0] = GnFwdSet<T>{z, partial_ws, gamma, beta, y, stats, yp, yq_amax, y_amax, zhat_amax};
-    args.p[1] = second ? *second : args.p[0];
-    const int sets = second ? 2 : 1;
+    args.p[0] = gn_fwd_set<T>(a, flags);
+    args.p[1] = b ? gn_fwd_set<T>(*b, flags) : args.p[0];
+    const int sets = b ? 2 : 1;
     hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(chunks, sets), dim3(256), 0, st, args, segs, B);
     hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(chunks, sets), dim3(256), 0, st, args, segs, B, eps, relu);
     return radet_check_launch();
 }
 
-// GroupNorm + ReLU of two tensors of the same geometry in one pair of launches (cls_convs[i] / reg_convs[i]: two
-// separate launches on two streams cost a fork and a join, 10-17 us of idle device each, around 23 us of kernels)
-extern "C" int radet_gn_relu_fwd_pair(const float* z0, const float* gamma0, const float* beta0, float* y0, float* stats0,
-                                      float* partial_ws0, const float* z1, const float* gamma1, const float* beta1,
-                                      float* y1, float* stats1, float* partial_ws1, int B, int C, int groups, float eps,
-                                      int relu, const int* seg_desc, int nseg, void* stream) {
-    const GnFwdSet<float> second{z1, partial_ws1, gamma1, beta1, y1, stats1, nullptr};
-    return gn_relu_fwd_impl<float>(z0, gamma0, beta0, y0, stats0, partial_ws0, B, C, groups, eps, relu, seg_desc, nseg,
-                                   stream, &second);
-}
-
-extern "C" int radet_gn_relu_fwd_pair_h(const void* z0, const float* gamma0, const float* beta0, void* y0, float* stats0,
-                                        float* partial_ws0, const void* z1, const float* gamma1, const float* beta1,
-                                        void* y1, float* stats1, float* partial_ws1, int B, int C, int groups, float eps,
-                                        int relu, const int* seg_desc, int nseg, void* stream) {
-    const GnFwdSet<__bf16> second{(const __bf16*)z1, partial_ws1, gamma1, beta1, (__bf16*)y1, stats1, nullptr};
-    return gn_relu_fwd_impl<__bf16>((const __bf16*)z0, gamma0, beta0, (__bf16*)y0, stats0, partial_ws0, B, C, groups, eps,
-                                    relu, seg_desc, nseg, stream, &second);
-}
-
-extern "C" int radet_gn_relu_fwd(const float* z, const float* gamma, const float* beta, float* y, float* stats,
-                                 float* partial_ws, int B, int C, int groups, float eps, int relu, const int* seg_desc,
-                                 int nseg, void* stream) {
-    return gn_relu_fwd_impl<float>(z, gamma, beta, y, stats, partial_ws, B, C, groups, eps, relu, seg_desc, nseg, stream);
-}
-
-extern "C" int radet_gn_relu_fwd_h(const void* z, const float* gamma, const float* beta, void* y, float* stats,
-                                   float* partial_ws, int B, int C, int groups, float eps, int relu, const int* seg_desc,
-                                   int nseg, void* stream) {
-    return gn_relu_fwd_impl<__bf16>((const __bf16*)z, gamma, beta, (__bf16*)y, stats, partial_ws, B, C, groups, eps, relu,
-                                    seg_desc, nseg, stream);
-}
-
-// fp32 in, outputs as fp32 (y, may be NULL) and / or bf16 plane triples (yp, may be NULL): the tower activations are read
-// by conv GEMMs only, which take plane operands (radet_conv2d_igemm tile_override 0x2000000)
-extern "C" int radet_gn_relu_fwd_p(const float* z, const float* gamma, const float* beta, float* y, void* yp, float* stats,
-                                   float* partial_ws, int B, int C, int groups, float eps, int relu, const int* seg_desc,
-                                   int nseg, void* stream) {
-    return gn_relu_fwd_impl<float>(z, gamma, beta, y, stats, partial_ws, B, C, groups, eps, relu, seg_desc, nseg, stream,
-                                   nullptr, (__bf16*)yp);
-}
-extern "C" int radet_gn_relu_fwd_pair_p(const float* z0, const float* gamma0, const float* beta0, float* y0, void* yp0,
-                                        float* stats0, float* partial_ws0, const float* z1, const float* gamma1,
-                                        const float* beta1, float* y1, void* yp1, float* stats1, float* partial_ws1, int B,
-                                        int C, int groups, float eps, int relu, const int* seg_desc, int nseg, void* stream) {
-    if (y1 == nullptr && yp1 == nullptr) return RADET_ERR_ARG;
-    const GnFwdSet<float> second{z1, partial_ws1, gamma1, beta1, y1, stats1, (__bf16*)yp1};
-    return gn_relu_fwd_impl<float>(z0, gamma0, beta0, y0, stats0, partial_ws0, B, C, groups, eps, relu, seg_desc, nseg,
-                                   stream, &second, (__bf16*)yp0);
-}
-
-// fp16 hi / lo arithmetic (common.h "h2"): fp32 in; outputs y (fp32, may be NULL; y_amax, may be NULL, is raised to its largest
-// magnitude) and / or yq (fp16 plane pairs, rows [2][256], may be NULL; yq_amax receives the bound on |y| whose power of two
-// scales them); zhat_amax (may be NULL) is raised to the largest |zhat| -- radet_gn_relu_bwd_q's bound on dz uses it.
-extern "C" int radet_gn_relu_fwd_q(const float* z, const float* gamma, const float* beta, float* y, void* yq, float* stats,
-                                   float* partial_ws, int B, int C, int groups, float eps, int relu, const int* seg_desc,
-                                   int nseg, void* stream, void* y_amax, void* yq_amax, void* zhat_amax) {
-    if (yq != nullptr && yq_amax == nullptr) return RADET_ERR_ARG;
-    return gn_relu_fwd_impl<float>(z, gamma, beta, y, stats, partial_ws, B, C, groups, eps, relu, seg_desc, nseg, stream,
-                                   nullptr, (__bf16*)yq, yq ? (unsigned*)yq_amax : nullptr, (unsigned*)y_amax,
-                                   (unsigned*)zhat_amax);
-}
-extern "C" int radet_gn_relu_fwd_pair_q(const float* z0, const float* gamma0, const float* beta0, float* y0, void* yq0,
-                                        float* stats0, float* partial_ws0, void* y_amax0, void* yq_amax0, void* zhat_amax0,
-                                        const float* z1, const float* gamma1, const float* beta1, float* y1, void* yq1,
-                                        float* stats1, float* partial_ws1, void* y_amax1, void* yq_amax1, void* zhat_amax1,
-                                        int B, int C, int groups, float eps, int relu, const int* seg_desc, int nseg,
-                                        void* stream) {
-    if ((y1 == nullptr && yq1 == nullptr) || (yq0 != nullptr && yq_amax0 == nullptr) || (yq1 != nullptr && yq_amax1 == nullptr))
-        return RADET_ERR_ARG;
-    const GnFwdSet<float> second{z1, partial_ws1, gamma1, beta1, y1, stats1, (__bf16*)yq1, yq1 ? (unsigned*)yq_amax1 : nullptr,
-                                 (unsigned*)y_amax1, (unsigned*)zhat_amax1};
-    return gn_relu_fwd_impl<float>(z0, gamma0, beta0, y0, stats0, partial_ws0, B, C, groups, eps, relu, seg_desc, nseg,
-                                   stream, &second, (__bf16*)yq0, yq0 ? (unsigned*)yq_amax0 : nullptr, (unsigned*)y_amax0,
-                                   (unsigned*)zhat_amax0);
+// GroupNorm + ReLU of one tensor (z1 == NULL), or of two tensors of the same geometry in one pair of launches (cls_convs[i] /
+// reg_convs[i]: two separate launches on two streams cost a fork and a join, 10-17 us of idle device each, around 23 us of
+// kernels)
+extern "C" int radet_gn_relu_fwd(const void* z0, const float* gamma0, const float* beta0, void* y0, void* planes0, float* stats0,
+                                 float* partial_ws0, void* y_amax0, void* planes_amax0, void* zhat_amax0, const void* z1,
+                                 const float* gamma1, const float* beta1, void* y1, void* planes1, float* stats1,
+                                 float* partial_ws1, void* y_amax1, void* planes_amax1, void* zhat_amax1, int B, int C, int groups,
+                                 float eps, int relu, int flags, const int* seg_desc, int nseg, void* stream) {
+    const GnFwdPtrs a{z0, gamma0, beta0, y0, planes0, stats0, partial_ws0, y_amax0, planes_amax0, zhat_amax0};
+    const GnFwdPtrs b{z1, gamma1, beta1, y1, planes1, stats1, partial_ws1, y_amax1, planes_amax1, zhat_amax1};
+    const GnFwdPtrs* second = z1 ? &b : nullptr;
+    RadetSegs segs;
+    if (C != 256 || groups != 32 || gn_fwd_set_bad(a, flags) || (second && gn_fwd_set_bad(b, flags))) return RADET_ERR_ARG;
+    if (!gn_segs(seg_desc, nseg, B, &segs)) return RADET_ERR_ARG;
+    return (flags & RADET_LAYER_BF16) ? gn_fwd_launch<__bf16>(a, second, B, eps, relu, flags, segs, stream)
+                                      : gn_fwd_launch<float>(a, second, B, eps, relu, flags, segs, stream);
 }
 
 extern "C" int radet_gn_workspace_floats(int B, const int* seg_desc, int nseg) {
@@ -1239,64 +1200,41 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
 }
 
 template <class T>
-static int gn_relu_bwd_impl(const T* dy, const T* z, const float* stats, const float* gamma,
-                            const float* beta, T* dz, float* dgamma, float* dbeta, float* partial_ws, int B,
-                            int C, int groups, int relu, const int* seg_desc, int nseg, void* stream,
-                            __bf16* dzp = nullptr, const unsigned* dy_amax = nullptr, const unsigned* zhat_amax = nullptr,
-                            unsigned* dzq_amax = nullptr) {
-    if (C != 256 || groups != 32 || (dz == nullptr && dzp == nullptr)) return RADET_ERR_ARG;
-    RadetSegs segs;
-    if (nseg < 1 || nseg > RADET_MAX_SEG) return RADET_ERR_ARG;
-    segs.nseg = nseg;
-    for (int l = 0; l < nseg; ++l) {
-        const int* d = seg_desc + 6 * l;
-        segs.s[l].Hi = d[0]; segs.s[l].Wi = d[1]; segs.s[l].Ho = d[2]; segs.s[l].Wo = d[3];
-        segs.s[l].in_row_off = d[4]; segs.s[l].row_begin = d[5]; segs.s[l].row_end = d[5] + B * d[2] * d[3];
-    }
+static int gn_bwd_launch(const void* dy, const void* z, const float* stats, const float* gamma, const float* beta, void* dz,
+                         void* planes, float* dgamma, float* dbeta, float* partial_ws, int B, int relu, const RadetSegs& segs,
+                         void* stream, const void* dy_amax, const void* zhat_amax, void* planes_amax) {
     const int chunks = gn_total_chunks(segs, B);
     float* gpart = partial_ws;
     float* cpart = partial_ws + (size_t)chunks * 64;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gn_bwd_stats_kernel<T>, dim3(chunks), dim3(256), 0, st, dy, z, stats, gamma, beta, gpart, cpart,
-                       segs, B, relu);
-    hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3(chunks + 32), dim3(256), 0, st, dy, z, stats, gamma, beta, gpart, dz, dzp,
-                       segs, B, relu, dy_amax, zhat_amax, dzq_amax, cpart, chunks, dgamma, dbeta);
+    hipLaunchKernelGGL(gn_bwd_stats_kernel<T>, dim3(chunks), dim3(256), 0, st, (const T*)dy, (const T*)z, stats, gamma, beta,
+                       gpart, cpart, segs, B, relu);
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3(chunks + 32), dim3(256), 0, st, (const T*)dy, (const T*)z, stats, gamma,
+                       beta, gpart, (T*)dz, (__bf16*)planes, segs, B, relu, (const unsigned*)dy_amax,
+                       (const unsigned*)zhat_amax, (unsigned*)planes_amax, cpart, chunks, dgamma, dbeta);
     return radet_check_launch();
 }
 
-extern "C" int radet_gn_relu_bwd(const float* dy, const float* z, const float* stats, const float* gamma,
-                                 const float* beta, float* dz, float* dgamma, float* dbeta, float* partial_ws, int B,
-                                 int C, int groups, int relu, const int* seg_desc, int nseg, void* stream) {
-    return gn_relu_bwd_impl<float>(dy, z, stats, gamma, beta, dz, dgamma, dbeta, partial_ws, B, C, groups, relu, seg_desc,
-                                   nseg, stream);
-}
-
-// fp32 in, dz as fp32 (may be NULL) and / or bf16 plane triples (dzp, may be NULL)
-extern "C" int radet_gn_relu_bwd_p(const float* dy, const float* z, const float* stats, const float* gamma,
-                                   const float* beta, float* dz, void* dzp, float* dgamma, float* dbeta, float* partial_ws,
-                                   int B, int C, int groups, int relu, const int* seg_desc, int nseg, void* stream) {
-    return gn_relu_bwd_impl<float>(dy, z, stats, gamma, beta, dz, dgamma, dbeta, partial_ws, B, C, groups, relu, seg_desc,
-                                   nseg, stream, (__bf16*)dzp);
-}
-
-// fp16 hi / lo arithmetic: dz as fp32 (may be NULL) and / or fp16 plane pairs dzq (rows [2][256]) scaled by the power of two of
-// a bound on |dz| built from dy_amax (the amax slot of dy, required with dzq), zhat_amax (from radet_gn_relu_fwd_q; NULL: the
-// hard bound sqrt(n - 1)) and the forward statistics; the bound is written to dzq_amax
-extern "C" int radet_gn_relu_bwd_q(const float* dy, const float* z, const float* stats, const float* gamma,
-                                   const float* beta, float* dz, void* dzq, float* dgamma, float* dbeta, float* partial_ws,
-                                   int B, int C, int groups, int relu, const int* seg_desc, int nseg, void* stream,
-                                   const void* dy_amax, const void* zhat_amax, void* dzq_amax) {
-    if (dzq != nullptr && (dy_amax == nullptr || dzq_amax == nullptr)) return RADET_ERR_ARG;
-    return gn_relu_bwd_impl<float>(dy, z, stats, gamma, beta, dz, dgamma, dbeta, partial_ws, B, C, groups, relu, seg_desc,
-                                   nseg, stream, (__bf16*)dzq, (const unsigned*)dy_amax, (const unsigned*)zhat_amax,
-                                   dzq ? (unsigned*)dzq_amax : nullptr);
-}
-
-extern "C" int radet_gn_relu_bwd_h(const void* dy, const void* z, const float* stats, const float* gamma,
-                                   const float* beta, void* dz, float* dgamma, float* dbeta, float* partial_ws, int B,
-                                   int C, int groups, int relu, const int* seg_desc, int nseg, void* stream) {
-    return gn_relu_bwd_impl<__bf16>((const __bf16*)dy, (const __bf16*)z, stats, gamma, beta, (__bf16*)dz, dgamma, dbeta,
-                                    partial_ws, B, C, groups, relu, seg_desc, nseg, stream);
+// dy, z: fp32 (bf16 with RADET_LAYER_BF16).  dz in their type (may be NULL) and / or as planes (may be NULL; fp32 only): bf16
+// plane triples, or with RADET_LAYER_PAIRS fp16 plane pairs (rows [2][256]) scaled by the power of two of a bound on |dz|
+// built from dy_amax (the amax slot of dy, required with pairs), zhat_amax (from radet_gn_relu_fwd; NULL: the hard bound
+// sqrt(n - 1)) and the forward statistics; the bound is written to planes_amax
+extern "C" int radet_gn_relu_bwd(const void* dy, const void* z, const float* stats, const float* gamma, const float* beta,
+                                 void* dz, void* planes, float* dgamma, float* dbeta, float* partial_ws, int B, int C,
+                                 int groups, int relu, int flags, const int* seg_desc, int nseg, void* stream,
+                                 const void* dy_amax, const void* zhat_amax, void* planes_amax) {
+    const bool pairs = (flags & RADET_LAYER_PAIRS) && planes != nullptr;
+    RadetSegs segs;
+    if (C != 256 || groups != 32 || (dz == nullptr && planes == nullptr)) return RADET_ERR_ARG;
+    if (layer_flags_bad(flags, RADET_LAYER_BF16 | RADET_LAYER_PAIRS, planes || dy_amax || zhat_amax || planes_amax))
+        return RADET_ERR_ARG;
+    if (pairs && (dy_amax == nullptr || planes_amax == nullptr)) return RADET_ERR_ARG;
+    if (!gn_segs(seg_desc, nseg, B, &segs)) return RADET_ERR_ARG;
+    if (flags & RADET_LAYER_BF16)
+        return gn_bwd_launch<__bf16>(dy, z, stats, gamma, beta, dz, nullptr, dgamma, dbeta, partial_ws, B, relu, segs, stream,
+                                     nullptr, nullptr, nullptr);
+    return gn_bwd_launch<float>(dy, z, stats, gamma, beta, dz, planes, dgamma, dbeta, partial_ws, B, relu, segs, stream, dy_amax,
+                                zhat_amax, pairs ? planes_amax : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------ upsample-add
@@ -1358,51 +1296,33 @@ __global__ void upsample_add_bwd_kernel(T* __restrict__ dsrc, const T* __restric
     if (amax) radet_amax_publish(am, amax);
 }
 
-extern "C" int radet_upsample_add_a(float* dst, const float* src, int B, int Ho, int Wo, int Hi, int Wi, int C,
-                                    void* dst_amax, void* stream) {
-    if (C % 4) return RADET_ERR_ARG;
-    const size_t total = (size_t)B * Ho * Wo * (C / 4);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(upsample_add_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dst, src, B, Ho, Wo, Hi,
-                       Wi, C / 4, (float)Hi / (float)Ho, (float)Wi / (float)Wo, (unsigned*)dst_amax);
+template <class T>
+static int upsample_add_launch(void* dst, const void* src, int B, int Ho, int Wo, int Hi, int Wi, int C, void* dst_amax,
+                               void* stream) {
+    hipLaunchKernelGGL(upsample_add_kernel<T>, grid1d((size_t)B * Ho * Wo * (C / 4)), dim3(256), 0, (hipStream_t)stream, (T*)dst,
+                       (const T*)src, B, Ho, Wo, Hi, Wi, C / 4, (float)Hi / (float)Ho, (float)Wi / (float)Wo, (unsigned*)dst_amax);
     return radet_check_launch();
 }
-extern "C" int radet_upsample_add(float* dst, const float* src, int B, int Ho, int Wo, int Hi, int Wi, int C,
-                                  void* stream) {
-    return radet_upsample_add_a(dst, src, B, Ho, Wo, Hi, Wi, C, nullptr, stream);
+extern "C" int radet_upsample_add(void* dst, const void* src, int B, int Ho, int Wo, int Hi, int Wi, int C, int flags,
+                                  void* dst_amax, void* stream) {
+    if (layer_flags_bad(flags, RADET_LAYER_BF16, dst_amax != nullptr) || C % 4) return RADET_ERR_ARG;
+    return (flags & RADET_LAYER_BF16) ? upsample_add_launch<__bf16>(dst, src, B, Ho, Wo, Hi, Wi, C, nullptr, stream)
+                                      : upsample_add_launch<float>(dst, src, B, Ho, Wo, Hi, Wi, C, dst_amax, stream);
 }
 
-extern "C" int radet_upsample_add_h(void* dst, const void* src, int B, int Ho, int Wo, int Hi, int Wi, int C, void* stream) {
-    if (C % 4) return RADET_ERR_ARG;
-    const size_t total = (size_t)B * Ho * Wo * (C / 4);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(upsample_add_kernel<__bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (__bf16*)dst,
-                       (const __bf16*)src, B, Ho, Wo, Hi, Wi, C / 4, (float)Hi / (float)Ho, (float)Wi / (float)Wo);
+template <class T>
+static int upsample_add_bwd_launch(void* dsrc, const void* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C, void* dsrc_amax,
+                                   void* stream) {
+    hipLaunchKernelGGL(upsample_add_bwd_kernel<T>, grid1d((size_t)B * Hi * Wi * (C / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (T*)dsrc, (const T*)ddst, B, Ho, Wo, Hi, Wi, C / 4, (float)Hi / (float)Ho, (float)Wi / (float)Wo,
+                       (unsigned*)dsrc_amax);
     return radet_check_launch();
 }
-
-extern "C" int radet_upsample_add_bwd_a(float* dsrc, const float* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C,
-                                        void* dsrc_amax, void* stream) {
-    if (C % 4) return RADET_ERR_ARG;
-    const size_t total = (size_t)B * Hi * Wi * (C / 4);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(upsample_add_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dsrc, ddst, B, Ho,
-                       Wo, Hi, Wi, C / 4, (float)Hi / (float)Ho, (float)Wi / (float)Wo, (unsigned*)dsrc_amax);
-    return radet_check_launch();
-}
-extern "C" int radet_upsample_add_bwd(float* dsrc, const float* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C,
-                                      void* stream) {
-    return radet_upsample_add_bwd_a(dsrc, ddst, B, Ho, Wo, Hi, Wi, C, nullptr, stream);
-}
-
-extern "C" int radet_upsample_add_bwd_h(void* dsrc, const void* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C,
-                                        void* stream) {
-    if (C % 4) return RADET_ERR_ARG;
-    const size_t total = (size_t)B * Hi * Wi * (C / 4);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(upsample_add_bwd_kernel<__bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (__bf16*)dsrc,
-                       (const __bf16*)ddst, B, Ho, Wo, Hi, Wi, C / 4, (float)Hi / (float)Ho, (float)Wi / (float)Wo);
-    return radet_check_launch();
+extern "C" int radet_upsample_add_bwd(void* dsrc, const void* ddst, int B, int Ho, int Wo, int Hi, int Wi, int C, int flags,
+                                      void* dsrc_amax, void* stream) {
+    if (layer_flags_bad(flags, RADET_LAYER_BF16, dsrc_amax != nullptr) || C % 4) return RADET_ERR_ARG;
+    return (flags & RADET_LAYER_BF16) ? upsample_add_bwd_launch<__bf16>(dsrc, ddst, B, Ho, Wo, Hi, Wi, C, nullptr, stream)
+                                      : upsample_add_bwd_launch<float>(dsrc, ddst, B, Ho, Wo, Hi, Wi, C, dsrc_amax, stream);
 }
 
 // ------------------------------------------------------------------------------------------ relu backward
@@ -1421,17 +1341,17 @@ __global__ void relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ 
     }
     if (amax) radet_amax_publish(am, amax);
 }
-extern "C" int radet_relu_bwd_a(const float* dy, const float* addend, const float* act, float* dx, size_t n, void* dx_amax,
-                                void* stream) {
-    if (n % 4) return RADET_ERR_ARG;
-    const size_t n4 = n / 4;
-    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(relu_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, addend, act, dx, n4,
-                       (unsigned*)dx_amax);
+template <class T>
+static int relu_bwd_launch(const void* dy, const void* addend, const void* act, void* dx, size_t n, void* dx_amax, void* stream) {
+    hipLaunchKernelGGL(relu_bwd_kernel<T>, grid1d(n / 4), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)addend,
+                       (const T*)act, (T*)dx, n / 4, (unsigned*)dx_amax);
     return radet_check_launch();
 }
-extern "C" int radet_relu_bwd(const float* dy, const float* addend, const float* act, float* dx, size_t n, void* stream) {
-    return radet_relu_bwd_a(dy, addend, act, dx, n, nullptr, stream);
+extern "C" int radet_relu_bwd(const void* dy, const void* addend, const void* act, void* dx, size_t n, int flags, void* dx_amax,
+                              void* stream) {
+    if (layer_flags_bad(flags, RADET_LAYER_BF16, dx_amax != nullptr) || n % 4) return RADET_ERR_ARG;
+    return (flags & RADET_LAYER_BF16) ? relu_bwd_launch<__bf16>(dy, addend, act, dx, n, nullptr, stream)
+                                      : relu_bwd_launch<float>(dy, addend, act, dx, n, dx_amax, stream);
 }
 // largest magnitude of n floats (x 16-byte aligned) -> raises *amax (for tensors whose producer does not track it; not reset
 // here).  float4 loads over the first n / 4 * 4 floats; the last n % 4 (an NHWC buffer of 3 or 21 channels at the module-API
@@ -1453,14 +1373,6 @@ extern "C" int radet_absmax(const float* x, size_t n, void* amax, void* stream) 
     const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
     hipLaunchKernelGGL(absmax_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, (hipStream_t)stream, x, n4, (int)(n % 4),
                        (unsigned*)amax);
-    return radet_check_launch();
-}
-extern "C" int radet_relu_bwd_h(const void* dy, const void* addend, const void* act, void* dx, size_t n, void* stream) {
-    if (n % 4) return RADET_ERR_ARG;
-    const size_t n4 = n / 4;
-    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(relu_bwd_kernel<__bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy,
-                       (const __bf16*)addend, (const __bf16*)act, (__bf16*)dx, n4);
     return radet_check_launch();
 }
 

@@ -489,8 +489,8 @@ class Engine:
                     self.buf[f"{t}.y{i}"] = K.Planes(R, f, device=dev, kind=pkind)
                 else:
                     new(f"{t}.y{i}", R, f)
-                if self.h2:
-                    self.buf[f"{t}.zhat{i}"] = slot(aux=True)     # largest normalised magnitude (bounds the backward's dz)
+                if self.h2 and self.p3:
+                    self.buf[f"{t}.zhat{i}"] = slot(aux=True)     # largest normalised magnitude (bounds the backward's pair dz)
                 self.buf[f"{t}.stats{i}"] = torch.empty(len(hw) * B * 64, device=dev)
             new(f"{t}.dy", R, f)
             for nm in (f"{t}.dz0", f"{t}.dz1"):  # two alternating GN-backward outputs: the async wgrad of layer i may still
@@ -1079,47 +1079,48 @@ class Engine:
             self.side_collect()
             self._join(self._side_stream)
 
-    # GroupNorm + ReLU of the towers on fp32 tensors (every path but the default plane-pair one: RADET_P3=0, RADET_TOWER_MODE).
-    # With the fp16 hi / lo arithmetic the tensors they write are conv operands and need their amax slots raised: the forward
-    # kernel's _q variant does it for y, the backward's dz gets a stand-alone pass (these are comparison modes, not the default).
-    def _gn_fwd(self, z, gamma, beta, y, stats, ws):
-        if self.h2 and not K._isp(y):
-            K.gn_relu_fwd_q(self.plv, z, gamma, beta, y, None, stats, ws)
-        else:
-            K.gn_relu_fwd(self.plv, z, gamma, beta, y, stats, ws)
+    def _gn_fwd_set(self, t, i, ws):
+        """tower t's GroupNorm i as a K.GnFwd: buf[t.y<i>] is an fp32 tensor, or -- where only tower GEMMs read it -- Planes; the
+        zhat slot exists where the backward pass scales plane pairs with it"""
+        b, p = self.buf, self.p
+        gn = f"bbox_head.{t}_convs.{i}.gn"
+        y = b[f"{t}.y{i}"]
+        pl = K._isp(y)
+        return K.GnFwd(b[f"{t}.z{i}"], p[gn + ".weight"], p[gn + ".bias"], b[f"{t}.stats{i}"], ws, y=None if pl else y,
+                       planes=y if pl else None, zhat_amax=b.get(f"{t}.zhat{i}"))
 
-    def _gn_bwd(self, dy, z, stats, gamma, beta, dz, dgamma, dbeta, ws):
-        K.gn_relu_bwd(self.plv, dy, z, stats, gamma, beta, dz, dgamma, dbeta, ws)
-        if self.h2 and not K._isp(dz) and dz.dtype == torch.float32:
+    def _gn_bwd(self, t, i, ws, dz):
+        """backward of tower t's GroupNorm i: buf[t.dy] -> dz (fp32 tensor or Planes) and the parameter gradients.  An fp32 dz
+        under the fp16 hi / lo arithmetic is a conv operand whose amax slot no kernel raises: a stand-alone pass does (the
+        fp32-tensor towers are comparison modes, RADET_P3=0 / RADET_TOWER_MODE, not the default)."""
+        b, p, g = self.buf, self.p, self.g
+        gn = f"bbox_head.{t}_convs.{i}.gn"
+        pl = K._isp(dz)
+        K.gn_relu_bwd(self.plv, b[f"{t}.dy"], b[f"{t}.z{i}"], b[f"{t}.stats{i}"], p[gn + ".weight"], p[gn + ".bias"],
+                      g[gn + ".weight"], g[gn + ".bias"], ws, dz=None if pl else dz, planes=dz if pl else None,
+                      zhat_amax=b.get(f"{t}.zhat{i}"))
+        if self.h2 and not pl and dz.dtype == torch.float32:
             sl = K.amax_slot(dz)
             if sl is not None:
                 K.absmax(dz, sl)
 
     def _tower_fwd_layer(self, t, tower, i, x, ws):
-        b, p = self.buf, self.p
+        b = self.buf
         c = tower[i]
         z, y = b[f"{t}.z{i}"], b[f"{t}.y{i}"]
         self._tower_launch(K.conv_fwd, c.geom, x, c.wf, None, z, tile=self._ttile(c))
-        gn = f"bbox_head.{t}_convs.{i}.gn"
-        self._gn_fwd(z, p[gn + ".weight"], p[gn + ".bias"], y, b[f"{t}.stats{i}"], ws)
+        K.gn_relu_fwd(self.plv, self._gn_fwd_set(t, i, ws))
         return y
 
     tower_fwd_streams = os.environ.get("RADET_TOWER_FWD_STREAMS", "1") != "0"
 
     def _tower_fwd_layer_p(self, t, tower, i, x, ws):
         """one tower layer with plane operands on the current stream: GEMM (256 x 128 tiles, no split-K) + GroupNorm + ReLU"""
-        b, p = self.buf, self.p
+        b = self.buf
         c = tower[i]
         z, y = b[f"{t}.z{i}"], b[f"{t}.y{i}"]
         self._tower_launch(K.conv_fwd, c.geom, x, c.wf, None, z, tile=self.tower_tile | K.SYMBOL | K.splitk(1) | self.tower_stages)
-        gn = f"bbox_head.{t}_convs.{i}.gn"
-        pl = K._isp(y)                  # the last layer's output feeds the predictor convs: fp32
-        if self.h2:
-            K.gn_relu_fwd_q(self.plv, z, p[gn + ".weight"], p[gn + ".bias"], None if pl else y, y if pl else None,
-                            b[f"{t}.stats{i}"], ws, zhat_amax=b[f"{t}.zhat{i}"])
-            return y
-        K.gn_relu_fwd_p(self.plv, z, p[gn + ".weight"], p[gn + ".bias"], None if pl else y, y if pl else None,
-                        b[f"{t}.stats{i}"], ws)
+        K.gn_relu_fwd(self.plv, self._gn_fwd_set(t, i, ws))     # (the last layer's output feeds the predictor convs: fp32)
         return y
 
     # "streams": cls / reg towers on two HIP streams; "pair": cls+reg layer = one grouped launch (forward and backward);
@@ -1132,33 +1133,14 @@ class Engine:
 
     def _tower_pair_fwd(self, i, xc, xr):
         """cls_convs[i] and reg_convs[i] as ONE grouped GEMM launch, then the two GroupNorm+ReLU."""
-        b, p = self.buf, self.p
+        b = self.buf
         cc, cr = self.cls_tower[i], self.reg_tower[i]
         zc, yc, zr, yr = b[f"cls.z{i}"], b[f"cls.y{i}"], b[f"reg.z{i}"], b[f"reg.y{i}"]
         self._tower_launch(K.conv_fwd_pair, cc.geom, dict(x=xc, w=cc.wf, y=zc), dict(x=xr, w=cr.wf, y=zr),
                            tile=self._ttile(cc))
-        gc, gr = f"bbox_head.cls_convs.{i}.gn", f"bbox_head.reg_convs.{i}.gn"
-        if self.p3:
-            pl = K._isp(yc)             # the last layer's output feeds the predictor convs: fp32
-            if self.h2:
-                K.gn_relu_fwd_pair_q(self.plv, (zc, p[gc + ".weight"], p[gc + ".bias"], None if pl else yc, yc if pl else None,
-                                                b[f"cls.stats{i}"], self.gn_ws, b[f"cls.zhat{i}"]),
-                                     (zr, p[gr + ".weight"], p[gr + ".bias"], None if pl else yr, yr if pl else None,
-                                      b[f"reg.stats{i}"], self.gn_ws2, b[f"reg.zhat{i}"]))
-                return yc, yr
-            K.gn_relu_fwd_pair_p(self.plv, (zc, p[gc + ".weight"], p[gc + ".bias"], None if pl else yc, yc if pl else None,
-                                            b[f"cls.stats{i}"], self.gn_ws),
-                                 (zr, p[gr + ".weight"], p[gr + ".bias"], None if pl else yr, yr if pl else None,
-                                  b[f"reg.stats{i}"], self.gn_ws2))
-            return yc, yr
         # both GroupNorms in one pair of launches (on two streams the fork and the join idled the device for longer
         # than the 23 us of kernels they overlapped)
-        if self.h2:       # (fp32 y: the _q kernel raises its amax slot)
-            K.gn_relu_fwd_pair_q(self.plv, (zc, p[gc + ".weight"], p[gc + ".bias"], yc, None, b[f"cls.stats{i}"], self.gn_ws, None),
-                                 (zr, p[gr + ".weight"], p[gr + ".bias"], yr, None, b[f"reg.stats{i}"], self.gn_ws2, None))
-            return yc, yr
-        K.gn_relu_fwd_pair(self.plv, (zc, p[gc + ".weight"], p[gc + ".bias"], yc, b[f"cls.stats{i}"], self.gn_ws),
-                           (zr, p[gr + ".weight"], p[gr + ".bias"], yr, b[f"reg.stats{i}"], self.gn_ws2))
+        K.gn_relu_fwd(self.plv, self._gn_fwd_set("cls", i, self.gn_ws), self._gn_fwd_set("reg", i, self.gn_ws2))
         return yc, yr
 
     def head_forward(self, P):
@@ -1301,12 +1283,10 @@ class Engine:
             K.conv_dgrad(pr.geom, dri, pr.wft, dy, k_channels=self.ri_pad)
 
     def _tower_bwd_layer(self, t, tower, i, ws, dP, addend):
-        b, p, g = self.buf, self.p, self.g
+        b = self.buf
         c = tower[i]
         dy, dz = b[f"{t}.dy"], b[f"{t}.dz"]
-        gn = f"bbox_head.{t}_convs.{i}.gn"
-        self._gn_bwd(dy, b[f"{t}.z{i}"], b[f"{t}.stats{i}"], p[gn + ".weight"], p[gn + ".bias"], dz,
-                     g[gn + ".weight"], g[gn + ".bias"], ws)
+        self._gn_bwd(t, i, ws, dz)
         x = b[f"{t}.y{i - 1}"] if i > 0 else b["P"]
         # the weight-gradient GEMM stays ON the tower's chain: moved to a stream of its own (overlapping the other
         # tower's dgrad and GroupNorm) the all-taps kernel's large workgroups starve the dependent chain -- measured
@@ -1332,22 +1312,14 @@ class Engine:
             # grouped cls + reg dgrad (400 tiles of 256 x 128 that own a CU each = two rounds, the second 56 % full) held
             # every CU while both chains' next GroupNorms waited for it; as single launches the tiles of one chain's dgrad, the
             # other's and the weight gradients interleave CU by CU: step -2.5 % (same box, same run)
-            p, g = self.p, self.g
             cs = self._chain_stream()
             wg_done = {}
 
             def layer(t, tower, ws, i):
-                gn = f"bbox_head.{t}_convs.{i}.gn"
                 ev = wg_done.get((t, i + 2))          # dz[i & 1] was last read by the wgrad of layer i + 2
                 if ev is not None:
                     K.ev_wait(ev)
-                if self.h2:
-                    K.gn_relu_bwd_q(self.plv, b[f"{t}.dy"], b[f"{t}.z{i}"], b[f"{t}.stats{i}"], p[gn + ".weight"],
-                                    p[gn + ".bias"], None, b[f"{t}.dz{i & 1}"], g[gn + ".weight"], g[gn + ".bias"], ws,
-                                    zhat_amax=b[f"{t}.zhat{i}"])
-                else:
-                    K.gn_relu_bwd_p(self.plv, b[f"{t}.dy"], b[f"{t}.z{i}"], b[f"{t}.stats{i}"], p[gn + ".weight"],
-                                    p[gn + ".bias"], None, b[f"{t}.dz{i & 1}"], g[gn + ".weight"], g[gn + ".bias"], ws)
+                self._gn_bwd(t, i, ws, b[f"{t}.dz{i & 1}"])
                 x = b[f"{t}.y{i - 1}"] if i > 0 else b["Pp"]
                 wg_done[(t, i)] = self._wgrad_async(tower[i].geom, b[f"{t}.dz{i & 1}"], x, tower[i].slabs, None)
                 if i > 0:
@@ -1367,7 +1339,6 @@ class Engine:
                 K.conv_dgrad(self.reg_tower[0].geom, b["reg.dz0"], self.reg_tower[0].wft, dP, addend=dP, tile=self.tower_tile | K.splitk(1))
             self._join(cs)
         elif self.tower_mode in ("pair", "pairbwd"):
-            p, g = self.p, self.g
             tagged = self.tower_mode == "pair"        # "pairbwd": only the forward launches are tagged / timed (like hybrid)
             launch = self._tower_launch if tagged else (lambda fn, *a, **k: fn(*a, **k))
             self._tower_bwd_head_async("cls")
@@ -1380,20 +1351,10 @@ class Engine:
             for i in range(n - 1, -1, -1):
                 pending = []
                 for t, tower in (("cls", self.cls_tower), ("reg", self.reg_tower)):
-                    gn = f"bbox_head.{t}_convs.{i}.gn"
                     ev = wg_done.get((t, i + 2))          # dz[i & 1] was last read by the wgrad of layer i + 2
                     if ev is not None:
                         K.ev_wait(ev)
-                    if self.p3 and self.h2:
-                        K.gn_relu_bwd_q(self.plv, b[f"{t}.dy"], b[f"{t}.z{i}"], b[f"{t}.stats{i}"], p[gn + ".weight"],
-                                        p[gn + ".bias"], None, b[f"{t}.dz{i & 1}"], g[gn + ".weight"], g[gn + ".bias"], self.gn_ws,
-                                        zhat_amax=b[f"{t}.zhat{i}"])
-                    elif self.p3:
-                        K.gn_relu_bwd_p(self.plv, b[f"{t}.dy"], b[f"{t}.z{i}"], b[f"{t}.stats{i}"], p[gn + ".weight"],
-                                        p[gn + ".bias"], None, b[f"{t}.dz{i & 1}"], g[gn + ".weight"], g[gn + ".bias"], self.gn_ws)
-                    else:
-                        self._gn_bwd(b[f"{t}.dy"], b[f"{t}.z{i}"], b[f"{t}.stats{i}"], p[gn + ".weight"],
-                                     p[gn + ".bias"], b[f"{t}.dz{i & 1}"], g[gn + ".weight"], g[gn + ".bias"], self.gn_ws)
+                    self._gn_bwd(t, i, self.gn_ws, b[f"{t}.dz{i & 1}"])
                     x = b[f"{t}.y{i - 1}"] if i > 0 else (b["Pp"] if self.p3 else b["P"])
                     if gn_first:
                         pending.append((t, tower, x))

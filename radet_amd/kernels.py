@@ -1,5 +1,6 @@
 """Thin Python launchers over the C ABI (include/radet_hip.h): torch tensors are used only as device
 buffers (data_ptr) and for the current HIP stream.  No arithmetic happens in PyTorch here."""
+import collections
 import ctypes as C
 import os
 
@@ -39,6 +40,9 @@ WG_DEEP, WG_WINDOWS = 0x2000, 0x4000      # all-taps pair kernel: conv_wgrad9d_k
 # template argument TAG of conv_igemmg_kernel:
 TAG_SYMBOL, TAG_BF16_MATH, TAG_H16, TAG_X3, TAG_P3, TAG_KDIV, TAG_H2, TAG_PAIRS = 1, 2, 4, 8, 16, 32, 64, 128
 # ---------------------------------------------------------------------- end of the launch flag words
+# flag word of the layer entry points (stem, max-pool, GroupNorm, upsample-add, ReLU backward): RADET_LAYER_<N> is LAYER_<N>
+LAYER_BF16 = 0x1                          # the activation tensors are bf16 (no plane output, no amax slot)
+LAYER_PAIRS = 0x2                         # the optional plane output holds fp16 plane pairs, not bf16 plane triples
 
 TILE_SHAPE = {1: (128, 128), 2: (128, 64), 3: (64, 64), 4: (128, 32), 5: (128, 128), 6: (256, 128), 7: (64, 64), 8: (64, 64)}   # rows x Cout
 WG_TILE_SHAPE = {1: (128, 128), 2: (64, 64), 3: (128, 64)}                                                                   # Cout x Cin
@@ -1176,18 +1180,15 @@ def unfold_grads(table_dev, n, max_cout):
     _lib.call("radet_unfold_grads", _ptr(table_dev), n, max_cout, _stream())
 
 
-def _h(name, t):
-    """entry point for the tensor's storage type"""
-    return name + "_h" if _is16(t) else name
+def _layer(t):
+    """(flag word, amax slot address) for the tensor t a layer kernel writes: its registered slot is raised; bf16 storage has none"""
+    return (LAYER_BF16, None) if _is16(t) else (0, _ptr(amax_slot(t)))
 
 
 def stem(img, wf, bias, y, B, H, W):
     ho, wo = (H + 1) // 2, (W + 1) // 2
-    if _is16(y):
-        fn = lambda: _lib.call("radet_stem_conv_bn_relu_h", _ptr(img), _ptr(wf), _ptr(bias), _ptr(y), B, H, W, _stream())  # noqa: E731
-    else:
-        sl = amax_slot(y)
-        fn = lambda: _lib.call("radet_stem_conv_bn_relu_a", _ptr(img), _ptr(wf), _ptr(bias), _ptr(y), B, H, W, _ptr(sl), _stream())  # noqa: E731
+    flags, sl = _layer(y)
+    fn = lambda: _lib.call("radet_stem_conv_bn_relu", _ptr(img), _ptr(wf), _ptr(bias), _ptr(y), B, H, W, flags, sl, _stream())  # noqa: E731
     _timed("stem_kernel", 2.0 * B * ho * wo * 64 * 147, fn, 4.0 * (B * 3 * H * W + 64 * 147 + B * ho * wo * 64))
 
 
@@ -1200,15 +1201,11 @@ def convert_rows(src, dst, ncols=None, src_off=0, dst_off=0):
 
 
 def maxpool(x, y, B, H, W, Cch, yq=None):
-    """yq (Planes "h2", optional): the output once more as plane pairs, scaled by x's amax slot"""
-    if _is16(x):
-        _lib.call("radet_maxpool3x3s2_h", _ptr(x), _ptr(y), B, H, W, Cch, _stream())
-        return
-    if yq is not None:
-        _lib.call("radet_maxpool3x3s2_q", _ptr(x), _ptr(y), B, H, W, Cch, _ptr(amax_slot(y)), _ptr(yq.t), _ptr(yq.amax),
-                  _ptr(amax_slot(x, True)), _stream())
-        return
-    _lib.call("radet_maxpool3x3s2_a", _ptr(x), _ptr(y), B, H, W, Cch, _ptr(amax_slot(y)), _stream())
+    """yq (Planes "h2", optional, fp32 x only): the output once more as plane pairs, scaled by x's amax slot"""
+    flags, sl = _layer(y)
+    q = (None, None, None) if yq is None else (_ptr(yq.t), _ptr(yq.amax), _ptr(amax_slot(x, True)))
+    _lib.call("radet_maxpool3x3s2", _ptr(x), _ptr(y), B, H, W, Cch, flags | (LAYER_PAIRS if yq is not None else 0), sl, *q,
+              _stream())
 
 
 def maxpool_bwd_relu(s, dpool, ds, B, H, W, Cch):
@@ -1234,96 +1231,62 @@ def _gn_desc(levels):
     return _desc([(h, w, h, w, o, o) for (h, w), o in zip(levels.hw, levels.offsets)])
 
 
-def gn_relu_fwd(levels, z, gamma, beta, y, stats, ws, eps=1e-5, relu=True):
+class GnFwd(collections.namedtuple("GnFwd", "z gamma beta stats ws y planes zhat_amax", defaults=(None, None, None))):
+    """One tensor of a GroupNorm + ReLU forward launch.  z: fp32 or bf16 rows; stats / ws: its statistics and workspace.  Outputs: y
+    (tensor of z's type or None) and / or planes (Planes or None, fp32 z only; kind "h2": scaled by a bound on |y| that is
+    written to planes.amax).  zhat_amax: slot raised to the largest |zhat| (the backward's bound on dz uses it)."""
+    __slots__ = ()
+
+    def pointers(self):
+        pl = self.planes
+        return (_ptr(self.z), _ptr(self.gamma), _ptr(self.beta), _ptr(self.y), _ptr_any(pl), _ptr(self.stats), _ptr(self.ws),
+                None if _is16(self.z) else _ptr(amax_slot(self.y)), None if pl is None else _ptr(pl.amax), _ptr(self.zhat_amax))
+
+
+def _gn_flags(z, *planes):
+    """RADET_LAYER_* word of a GroupNorm launch: bf16 storage from the tensor's dtype, pairs from the kind of its plane outputs"""
+    kinds = {pl.kind for pl in planes if pl is not None}
+    assert len(kinds) <= 1, "one launch writes bf16 plane triples or fp16 plane pairs, not both"
+    return (LAYER_BF16 if _is16(z) else 0) | (LAYER_PAIRS if "h2" in kinds else 0)
+
+
+def gn_relu_fwd(levels, a, b=None, eps=1e-5, relu=True):
+    """GroupNorm + ReLU of the GnFwd a -- and of b, a second tensor of the same geometry, in the same pair of launches.  The amax
+    slot registered for an fp32 y is raised whatever else the launch writes (the engine registers activation slots only under the
+    fp16 hi / lo arithmetic, whose conv GEMMs read them)."""
     d, n = _gn_desc(levels)
-    _lib.call(_h("radet_gn_relu_fwd", z), _ptr(z), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(stats), _ptr(ws), levels.B, 256, 32,
-              eps, int(relu), d, n, _stream())
+    _lib.call("radet_gn_relu_fwd", *a.pointers(), *(b.pointers() if b is not None else (None,) * 10), levels.B, 256, 32, eps,
+              int(relu), _gn_flags(a.z, a.planes, b.planes if b is not None else None), d, n, _stream())
 
 
-def gn_relu_fwd_pair(levels, a, b, eps=1e-5, relu=True):
-    """GroupNorm + ReLU of two tensors of one geometry in one pair of launches; a / b = (z, gamma, beta, y, stats, ws)."""
+def gn_relu_bwd(levels, dy, z, stats, gamma, beta, dgamma, dbeta, ws, *, dz=None, planes=None, zhat_amax=None, dy_amax=None,
+                relu=True):
+    """dz as a tensor of dy's type (or None) and / or as Planes (or None, fp32 only).  Planes of kind "h2" are scaled by a bound
+    built from dy's amax slot -- dy_amax, else the registered one, else computed here -- and zhat_amax (the forward's); the bound
+    goes to planes.amax.  The outputs are keyword-only: ten positional arguments in the earlier order (dz, dgamma, dbeta, ws)
+    are a TypeError, not a launch that takes the workspace for dz."""
     d, n = _gn_desc(levels)
-    _lib.call(_h("radet_gn_relu_fwd_pair", a[0]), *[_ptr(t) for t in a], *[_ptr(t) for t in b], levels.B, 256, 32, eps,
-              int(relu), d, n, _stream())
-
-
-def gn_relu_fwd_p(levels, z, gamma, beta, y, yp, stats, ws, eps=1e-5, relu=True):
-    """fp32 z -> y (fp32 tensor or None) and / or yp (Planes or None)"""
-    d, n = _gn_desc(levels)
-    _lib.call("radet_gn_relu_fwd_p", _ptr(z), _ptr(gamma), _ptr(beta), _ptr(y), _ptr_any(yp), _ptr(stats), _ptr(ws), levels.B,
-              256, 32, eps, int(relu), d, n, _stream())
-
-
-def gn_relu_fwd_pair_p(levels, a, b, eps=1e-5, relu=True):
-    """a / b = (z, gamma, beta, y or None, yp (Planes) or None, stats, ws)"""
-    d, n = _gn_desc(levels)
-    _lib.call("radet_gn_relu_fwd_pair_p", *[_ptr_any(t) for t in a], *[_ptr_any(t) for t in b], levels.B, 256, 32, eps,
-              int(relu), d, n, _stream())
-
-
-def gn_relu_fwd_q(levels, z, gamma, beta, y, yq, stats, ws, zhat_amax=None, eps=1e-5, relu=True):
-    """fp16 hi / lo arithmetic: fp32 z -> y (fp32 tensor or None; its registered amax slot is raised) and / or yq (Planes of
-    kind "h2" or None: scaled by a bound on |y|, written to yq.amax); zhat_amax: slot raised to the largest |zhat|"""
-    d, n = _gn_desc(levels)
-    _lib.call("radet_gn_relu_fwd_q", _ptr(z), _ptr(gamma), _ptr(beta), _ptr(y), _ptr_any(yq), _ptr(stats), _ptr(ws), levels.B,
-              256, 32, eps, int(relu), d, n, _stream(), _ptr(amax_slot(y)), _ptr(yq.amax) if yq is not None else None,
-              _ptr(zhat_amax))
-
-
-def gn_relu_fwd_pair_q(levels, a, b, eps=1e-5, relu=True):
-    """a / b = (z, gamma, beta, y or None, yq (Planes "h2") or None, stats, ws, zhat_amax or None)"""
-    d, n = _gn_desc(levels)
-
-    def q(t):
-        z, gm, bt, y, yq, stats, ws, zh = t
-        return [_ptr(z), _ptr(gm), _ptr(bt), _ptr(y), _ptr_any(yq), _ptr(stats), _ptr(ws), _ptr(amax_slot(y)),
-                _ptr(yq.amax) if yq is not None else None, _ptr(zh)]
-    _lib.call("radet_gn_relu_fwd_pair_q", *q(a), *q(b), levels.B, 256, 32, eps, int(relu), d, n, _stream())
-
-
-def gn_relu_bwd_q(levels, dy, z, stats, gamma, beta, dz, dzq, dgamma, dbeta, ws, zhat_amax=None, dy_amax=None, relu=True):
-    """like gn_relu_bwd with dz as fp32 (or None) and / or Planes "h2" dzq (scaled by a bound built from dy's amax slot --
-    dy_amax, else the registered one, else computed here -- and zhat_amax; the bound goes to dzq.amax)"""
-    d, n = _gn_desc(levels)
-    da = dy_amax if dy_amax is not None else (amax_slot(dy, compute=True) if dzq is not None else None)
-    _lib.call("radet_gn_relu_bwd_q", _ptr(dy), _ptr(z), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(dz), _ptr_any(dzq),
-              _ptr(dgamma), _ptr(dbeta), _ptr(ws), levels.B, 256, 32, int(relu), d, n, _stream(), _ptr(da), _ptr(zhat_amax),
-              _ptr(dzq.amax) if dzq is not None else None)
-
-
-def gn_relu_bwd_p(levels, dy, z, stats, gamma, beta, dz, dzp, dgamma, dbeta, ws, relu=True):
-    """like gn_relu_bwd with dz as fp32 (or None) and / or Planes dzp (or None)"""
-    d, n = _gn_desc(levels)
-    _lib.call("radet_gn_relu_bwd_p", _ptr(dy), _ptr(z), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(dz), _ptr_any(dzp),
-              _ptr(dgamma), _ptr(dbeta), _ptr(ws), levels.B, 256, 32, int(relu), d, n, _stream())
-
-
-def gn_relu_bwd(levels, dy, z, stats, gamma, beta, dz, dgamma, dbeta, ws, relu=True):
-    d, n = _gn_desc(levels)
-    _lib.call(_h("radet_gn_relu_bwd", dy), _ptr(dy), _ptr(z), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(dz), _ptr(dgamma),
-              _ptr(dbeta), _ptr(ws), levels.B, 256, 32, int(relu), d, n, _stream())
+    flags = _gn_flags(dy, planes)
+    if dy_amax is None and flags & LAYER_PAIRS:
+        dy_amax = amax_slot(dy, compute=True)
+    _lib.call("radet_gn_relu_bwd", _ptr(dy), _ptr(z), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(dz), _ptr_any(planes),
+              _ptr(dgamma), _ptr(dbeta), _ptr(ws), levels.B, 256, 32, int(relu), flags, d, n, _stream(), _ptr(dy_amax),
+              _ptr(zhat_amax), None if planes is None else _ptr(planes.amax))
 
 
 def upsample_add(dst, src, B, ho, wo, hi, wi, ch):
-    if _is16(dst):
-        _lib.call("radet_upsample_add_h", _ptr(dst), _ptr(src), B, ho, wo, hi, wi, ch, _stream())
-        return
-    _lib.call("radet_upsample_add_a", _ptr(dst), _ptr(src), B, ho, wo, hi, wi, ch, _ptr(amax_slot(dst)), _stream())
+    flags, sl = _layer(dst)
+    _lib.call("radet_upsample_add", _ptr(dst), _ptr(src), B, ho, wo, hi, wi, ch, flags, sl, _stream())
 
 
 def upsample_add_bwd(dsrc, ddst, B, ho, wo, hi, wi, ch):
-    if _is16(dsrc):
-        _lib.call("radet_upsample_add_bwd_h", _ptr(dsrc), _ptr(ddst), B, ho, wo, hi, wi, ch, _stream())
-        return
-    _lib.call("radet_upsample_add_bwd_a", _ptr(dsrc), _ptr(ddst), B, ho, wo, hi, wi, ch, _ptr(amax_slot(dsrc)), _stream())
+    flags, sl = _layer(dsrc)
+    _lib.call("radet_upsample_add_bwd", _ptr(dsrc), _ptr(ddst), B, ho, wo, hi, wi, ch, flags, sl, _stream())
 
 
 def relu_bwd(dy, addend, act, dx):
-    if _is16(dy):
-        _lib.call("radet_relu_bwd_h", _ptr(dy), _ptr(addend), _ptr(act), _ptr(dx), C.c_size_t(dx.numel()), _stream())
-        return
-    _lib.call("radet_relu_bwd_a", _ptr(dy), _ptr(addend), _ptr(act), _ptr(dx), C.c_size_t(dx.numel()), _ptr(amax_slot(dx)),
-              _stream())
+    flags, sl = _layer(dx)
+    _lib.call("radet_relu_bwd", _ptr(dy), _ptr(addend), _ptr(act), _ptr(dx), C.c_size_t(dx.numel()), flags, sl, _stream())
 
 
 def nchw_to_nhwc(x, y, B, ch, H, W):

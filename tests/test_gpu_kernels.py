@@ -443,7 +443,7 @@ def test_plane_pair_operand_conv(K, case):
 
 
 def test_plane_pair_outputs_of_groupnorm_and_fold(K):
-    """GroupNorm + ReLU forward / backward with plane-PAIR outputs (radet_gn_relu_fwd_q / _bwd_q): the pairs reproduce the fp32
+    """GroupNorm + ReLU forward / backward with plane-PAIR outputs (RADET_LAYER_PAIRS): the pairs reproduce the fp32
     outputs to 2^-22 of every element (2^-24 of the bound for the smallest ones), the bound written to the amax slot really
     bounds the tensor, the tracked slots (fp32 output, |zhat|) hold the exact maxima, and the statistics / parameter
     gradients are those of the fp32 kernels bit for bit."""
@@ -456,7 +456,7 @@ def test_plane_pair_outputs_of_groupnorm_and_fold(K):
     stats, stats2 = torch.empty(len(lv) * lv.B * 64, device=dev), torch.empty(len(lv) * lv.B * 64, device=dev)
     ws = torch.empty(K.gn_ws_floats(lv), device=dev)
     y = torch.empty_like(z)
-    K.gn_relu_fwd(lv, z, gam, bet, y, stats, ws)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, y=y))
 
     def close(planes, ref):
         got = planes.to_float()
@@ -468,7 +468,7 @@ def test_plane_pair_outputs_of_groupnorm_and_fold(K):
     yq, y2 = K.Planes(R, 256, device=dev, kind="h2"), torch.empty_like(z)
     ya, zh = K.new_amax(dev), K.new_amax(dev).fill_(77)
     key = K.register_amax(y2, ya)
-    K.gn_relu_fwd_q(lv, z, gam, bet, y2, yq, stats2, ws, zhat_amax=zh)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats2, ws, y=y2, planes=yq, zhat_amax=zh))
     K.unregister_amax([key])
     assert torch.equal(y2, y) and torch.equal(stats2, stats)
     close(yq, y)
@@ -481,18 +481,18 @@ def test_plane_pair_outputs_of_groupnorm_and_fold(K):
     zb = torch.randn(R, 256, generator=g).to(dev)
     yb, yqb = torch.empty_like(z), K.Planes(R, 256, device=dev, kind="h2")
     stats_b, ws_b = torch.empty_like(stats), torch.empty_like(ws)
-    K.gn_relu_fwd_pair_q(lv, (z, gam, bet, None, yq, stats, ws, zh), (zb, gam, bet, yb, yqb, stats_b, ws_b, None))
-    K.gn_relu_fwd(lv, zb, gam, bet, y2, stats_b, ws_b)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, planes=yq, zhat_amax=zh), K.GnFwd(zb, gam, bet, stats_b, ws_b, y=yb, planes=yqb))
+    K.gn_relu_fwd(lv, K.GnFwd(zb, gam, bet, stats_b, ws_b, y=y2))
     close(yq, y)
     close(yqb, y2)
     assert torch.equal(yb, y2)
     # backward
     dy = (torch.randn(R, 256, generator=g) * 1e-4).to(dev)
     dz, dg, db = torch.empty_like(z), torch.empty(256, device=dev), torch.empty(256, device=dev)
-    K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dz, dg, db, ws)
+    K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dg, db, ws, dz=dz)
     for zslot in (zh, None):                                   # tracked |zhat| bound, and the hard sqrt(n - 1) one
         dzq, dg2, db2 = K.Planes(R, 256, device=dev, kind="h2"), torch.empty(256, device=dev), torch.empty(256, device=dev)
-        K.gn_relu_bwd_q(lv, dy, z, stats, gam, bet, None, dzq, dg2, db2, ws, zhat_amax=zslot)
+        K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dg2, db2, ws, planes=dzq, zhat_amax=zslot)
         close(dzq, dz)
         assert torch.equal(dg2, dg) and torch.equal(db2, db)
     # folded weights as plane pairs (RadetConvDesc.w16 = 3) against the fp32 fold, through the engine's descriptor table
@@ -764,27 +764,27 @@ def test_groupnorm_fwd_bwd(K):
     stats = torch.empty(len(hw) * B * 64, device=dev)
     ws = torch.empty(K.gn_ws_floats(lv), device=dev)
     gm, bt = gamma.detach().float().to(dev), beta.detach().float().to(dev)
-    K.gn_relu_fwd(lv, z, gm, bt, y, stats, ws)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gm, bt, stats, ws, y=y))
     for i in range(len(hw)):
         r0, r1 = lv.level_rows(i)
         assert rel_err(from_rows(y[r0:r1], B, *hw[i]), ys[i].detach()) < 1e-5
     # the paired launch (cls / reg tower of one layer): bit-identical to two single launches, in fp32 and bf16 storage
     z2, gm2, bt2 = z * 0.7 - 0.2, gm * 1.3, bt - 0.1
     y2, stats2, ws2 = torch.empty_like(z), torch.empty_like(stats), torch.empty_like(ws)
-    K.gn_relu_fwd(lv, z2, gm2, bt2, y2, stats2, ws2)
+    K.gn_relu_fwd(lv, K.GnFwd(z2, gm2, bt2, stats2, ws2, y=y2))
     ya, yb, sa, sb = torch.empty_like(z), torch.empty_like(z), torch.empty_like(stats), torch.empty_like(stats)
-    K.gn_relu_fwd_pair(lv, (z, gm, bt, ya, sa, ws), (z2, gm2, bt2, yb, sb, ws2))
+    K.gn_relu_fwd(lv, K.GnFwd(z, gm, bt, sa, ws, y=ya), K.GnFwd(z2, gm2, bt2, sb, ws2, y=yb))
     assert torch.equal(ya, y) and torch.equal(yb, y2) and torch.equal(sa, stats) and torch.equal(sb, stats2)
     zh, zh2 = z.bfloat16(), z2.bfloat16()
     yh, yh2, yha, yhb = (torch.empty_like(zh) for _ in range(4))
-    K.gn_relu_fwd(lv, zh, gm, bt, yh, sa, ws)
-    K.gn_relu_fwd(lv, zh2, gm2, bt2, yh2, sb, ws2)
-    K.gn_relu_fwd_pair(lv, (zh, gm, bt, yha, sa, ws), (zh2, gm2, bt2, yhb, sb, ws2))
+    K.gn_relu_fwd(lv, K.GnFwd(zh, gm, bt, sa, ws, y=yh))
+    K.gn_relu_fwd(lv, K.GnFwd(zh2, gm2, bt2, sb, ws2, y=yh2))
+    K.gn_relu_fwd(lv, K.GnFwd(zh, gm, bt, sa, ws, y=yha), K.GnFwd(zh2, gm2, bt2, sb, ws2, y=yhb))
     assert torch.equal(yha, yh) and torch.equal(yhb, yh2)
     dy = torch.cat([to_rows(d) for d in dys]).to(dev)
     dz = torch.empty_like(z)
     dg, db = torch.empty(Cch, device=dev), torch.empty(Cch, device=dev)
-    K.gn_relu_bwd(lv, dy, z, stats, gm, bt, dz, dg, db, ws)
+    K.gn_relu_bwd(lv, dy, z, stats, gm, bt, dg, db, ws, dz=dz)
     for i in range(len(hw)):
         r0, r1 = lv.level_rows(i)
         assert rel_err(from_rows(dz[r0:r1], B, *hw[i]), grads[i]) < 2e-5
@@ -1230,21 +1230,21 @@ def test_plane_outputs_of_groupnorm_and_fold(K):
     stats = torch.empty(len(lv) * lv.B * 64, device=dev)
     ws = torch.empty(K.gn_ws_floats(lv), device=dev)
     y = torch.empty_like(z)
-    K.gn_relu_fwd(lv, z, gam, bet, y, stats, ws)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, y=y))
     yp, y2 = K.Planes(R, 256, device=dev), torch.empty_like(z)
-    K.gn_relu_fwd_p(lv, z, gam, bet, y2, yp, stats, ws)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, y=y2, planes=yp))
     assert torch.equal(y2, y) and torch.equal(yp.to_float(), y)
     yq, zb = K.Planes(R, 256, device=dev), torch.randn(R, 256, generator=g).to(dev)
     yb = torch.empty_like(z)
     stats_b, ws_b = torch.empty_like(stats), torch.empty_like(ws)
-    K.gn_relu_fwd_pair_p(lv, (z, gam, bet, None, yp, stats, ws), (zb, gam, bet, yb, yq, stats_b, ws_b))
-    K.gn_relu_fwd(lv, zb, gam, bet, y2, stats_b, ws_b)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, planes=yp), K.GnFwd(zb, gam, bet, stats_b, ws_b, y=yb, planes=yq))
+    K.gn_relu_fwd(lv, K.GnFwd(zb, gam, bet, stats_b, ws_b, y=y2))
     assert torch.equal(yp.to_float(), y) and torch.equal(yq.to_float(), y2) and torch.equal(yb, y2)
     dy = torch.randn(R, 256, generator=g).to(dev)
     dz, dg, db = torch.empty_like(z), torch.empty(256, device=dev), torch.empty(256, device=dev)
-    K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dz, dg, db, ws)
+    K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dg, db, ws, dz=dz)
     dzp, dg2, db2 = K.Planes(R, 256, device=dev), torch.empty(256, device=dev), torch.empty(256, device=dev)
-    K.gn_relu_bwd_p(lv, dy, z, stats, gam, bet, None, dzp, dg2, db2, ws)
+    K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dg2, db2, ws, planes=dzp)
     assert torch.equal(dzp.to_float(), dz) and torch.equal(dg2, dg) and torch.equal(db2, db)
     # special values survive the split: zeros, tiny and huge magnitudes, a full 24-bit significand (inputs in fp32's own
     # denormal range are outside the contract: their low planes are bf16 denormals)

@@ -3,23 +3,24 @@ radet_amd/kernels.py and compared with a CPU reference (tests/_layers_ref.py, ch
 tests/test_layers_ref_cpu.py) computed in fp64 from exactly the values the kernel reads (bf16 cases: inputs rounded first).
 
 kernel                               reference                                      bound
-maxpool fp32 / bf16 (_h)             F.max_pool2d(x, 3, 2, 1)                       bit equal (a max has no rounding)
-maxpool _a                           |y| of the same                                slot == max |y| exactly; never lowered
-maxpool _q (yq=)                     the fp32 output y                              |err| <= 2^-22 |ref| + 2^-36 bound; yq.amax = x's slot
+maxpool fp32 / bf16                  F.max_pool2d(x, 3, 2, 1)                       bit equal (a max has no rounding)
+maxpool, y's amax slot               |y| of the same                                slot == max |y| exactly; never lowered
+maxpool yq= (plane pairs)            the fp32 output y                              |err| <= 2^-22 |ref| + 2^-36 bound; yq.amax = x's slot
 maxpool_bwd_relu                     [s > 0] * torch CPU fp64 autograd of the pool  bit equal (sums of <= 4 exact terms)
 stem_wgrad                           nn.grad.conv2d_weight fp64, column sums of ds  rel_err < 1e-5; two runs bit identical
 fold_weights w16 = 0                 s w, beta - mean s in fp64                     |err| <= 2^-21 |ref| per element
 fold_weights w16 = 1 (bf16)          same                                           |err| <= 2^-8 |ref| per element
 unfold_grads                         fp64 autograd of <wf, G> + <bias_f, db>        dw, db rel_err < 1e-6; dgamma 1e-6 of the summed magnitude
-relu_bwd fp32 (_a) / bf16 (_h)       (dy + addend) * (act > 0) in fp32 (rounded)    bit equal (zeros +0.0); slot == max |dx| exactly
+relu_bwd fp32 / bf16                 (dy + addend) * (act > 0) in fp32 (rounded)    bit equal (zeros +0.0); slot == max |dx| exactly
 upsample_add fp32 / bf16             dst + F.interpolate(nearest), torch CPU        equal (bf16: one rounding of the fp32 sum)
 upsample_add_bwd fp32 / bf16         base + fp64 autograd of the same               rel_err < 1e-6 / equal to the bf16 rounding (exact sums)
-upsample_add(_bwd) _a                |output|                                       slot == max exactly; never lowered
+upsample_add(_bwd), amax slot        |output|                                       slot == max exactly; never lowered
 gn_relu_fwd fp32 / bf16              F.group_norm fp64 + ReLU                       rel_err < 1e-5 per level / 2^-8 |ref| + 1e-5 max |ref|; stats 1e-5
-gn_relu_bwd fp32 / bf16 (_h)         fp64 autograd, ReLU mask of the kernel's y     rel_err < 2e-5 per level / 2^-8 |ref| + 1e-5 max |ref|; dgamma, dbeta 2e-5
+gn_relu_bwd fp32 / bf16              fp64 autograd, ReLU mask of the kernel's y     rel_err < 2e-5 per level / 2^-8 |ref| + 1e-5 max |ref|; dgamma, dbeta 2e-5
 nchw_to_nhwc / nhwc_to_nchw          torch permute                                  bit equal (bf16: one rounding); slot == max |x|
 absmax (behind nchw_to_nhwc)         max |x|                                        slot == max exactly for any element count; never lowered
-stem _a                              |y| of its own output                          slot == max |y| exactly
+stem, y's amax slot                  |y| of its own output                          slot == max |y| exactly
+gn_relu_fwd / _bwd output forms      two single launches / the fp32-only call       bit equal; planes vs fp32: equal (triples), pair rule
 """
 import ctypes as C
 
@@ -400,10 +401,10 @@ def _gn_run(K, levels, bf16, relu, seed):
     y = torch.empty_like(zd)
     stats = torch.full((len(hw) * B * 64,), float("nan"), device=DEV)
     ws = torch.empty(K.gn_ws_floats(lv), device=DEV)
-    K.gn_relu_fwd(lv, zd, gm, bt, y, stats, ws, relu=relu)
+    K.gn_relu_fwd(lv, K.GnFwd(zd, gm, bt, stats, ws, y=y), relu=relu)
     dz = torch.empty_like(zd)
     dg, db = torch.full((256,), float("nan"), device=DEV), torch.full((256,), float("nan"), device=DEV)
-    K.gn_relu_bwd(lv, dyd, zd, stats, gm, bt, dz, dg, db, ws, relu=relu)
+    K.gn_relu_bwd(lv, dyd, zd, stats, gm, bt, dg, db, ws, dz=dz, relu=relu)
     assert y.dtype == dz.dtype == (torch.bfloat16 if bf16 else torch.float32)
     return z, gamma, beta, dy, y.cpu(), stats.cpu().view(-1, 32, 2), dz.cpu(), dg.cpu(), db.cpu()
 
@@ -511,3 +512,119 @@ def test_stem_amax_slot(K, size):
         K.stem(img.to(DEV), w.permute(0, 2, 3, 1).contiguous().to(DEV), bias.to(DEV), y, B, H, W)
         assert rel_err(from_rows(y, B, Ho, Wo), ref) < 1e-5
         assert s.value == float(y.abs().max())
+
+
+# ---------------------------------------------------------------------- 8. GroupNorm: every output form through the one entry point
+GN_FORMS = dict(y=(True, None), b3=(False, "b3"), y_b3=(True, "b3"), h2=(False, "h2"), y_h2=(True, "h2"), bf16=(True, None))
+NAN = float("nan")
+
+
+def _same_bits(a, b):
+    """bit for bit (NaN equals NaN, -0.0 differs from 0.0): tensors, or Planes by their plane tensors and bound slots"""
+    if a is None or b is None:
+        return a is None and b is None
+    if hasattr(a, "kind"):
+        return _same_bits(a.t, b.t) and _same_bits(a.amax, b.amax)
+    w = {2: torch.int16, 4: torch.int32}[a.element_size()]
+    return a.dtype == b.dtype and torch.equal(a.view(w), b.view(w))
+
+
+class _GnFwdOut:
+    """fresh, NaN-filled outputs of one tensor of a forward launch in the given form, and the slots the launch may raise"""
+
+    def __init__(self, K, lv, src, form):
+        with_y, kind = GN_FORMS[form]
+        self.z, self.gamma, self.beta = src
+        fp32 = form != "bf16"
+        if not fp32:
+            self.z = self.z.bfloat16()
+        self.stats = torch.full((len(lv) * lv.B * 64,), NAN, device=DEV)
+        self.ws = torch.empty(K.gn_ws_floats(lv), device=DEV)
+        self.y = torch.full_like(self.z, NAN) if with_y else None
+        self.planes = K.Planes(lv.rows, 256, device=DEV, kind=kind) if kind else None
+        if kind:
+            self.planes.t.fill_(NAN)
+        self.y_slot = K.new_amax(DEV) if with_y and fp32 else None
+        self.zhat = K.new_amax(DEV) if fp32 else None
+
+    def arg(self, K):
+        return K.GnFwd(self.z, self.gamma, self.beta, self.stats, self.ws, y=self.y, planes=self.planes, zhat_amax=self.zhat)
+
+    def same(self, o):
+        return all(_same_bits(getattr(self, n), getattr(o, n)) for n in ("stats", "y", "planes", "y_slot", "zhat"))
+
+
+def _gn_fwd_launch(K, lv, *outs):
+    keys = [K.register_amax(o.y, o.y_slot) for o in outs if o.y_slot is not None]
+    try:
+        K.gn_relu_fwd(lv, *[o.arg(K) for o in outs])
+    finally:
+        K.unregister_amax(keys)
+
+
+@pytest.fixture(scope="module")
+def gn_forms_case(K):
+    """R.GN_SET1 (crosses the chunk and the level boundaries), two tensors with different z / gamma / beta, and each one's fp32
+    output from a single launch: the reference of every other form"""
+    hw, B = R.GN_SET1
+    lv = K.Levels(hw, B)
+    z, gamma, beta, dy = (t.to(DEV) for t in R.gn_inputs(hw, B, 101))
+    srcs = [(z, gamma, beta), (z * 0.7 - 0.2, gamma * 1.3, beta - 0.1)]
+    refs = [_GnFwdOut(K, lv, s, "y") for s in srcs]
+    for o in refs:
+        _gn_fwd_launch(K, lv, o)
+        assert bool(torch.isfinite(o.y).all()) and bool(torch.isfinite(o.stats).all())
+    return lv, srcs, refs, dy
+
+
+@pytest.mark.parametrize("form", list(GN_FORMS))
+def test_groupnorm_fwd_output_forms_single_and_paired_launch(K, gn_forms_case, form):
+    """Two single launches and one paired launch write the same bits: y, the planes, the statistics and every amax slot (the
+    raised slot of y, the bound of the pairs, the zhat slot).  The planes against the fp32 y: equal for bf16 triples (the split is
+    exact), the rule of test_plane_pair_outputs_of_groupnorm_and_fold for fp16 pairs."""
+    lv, srcs, refs, _ = gn_forms_case
+    single = [_GnFwdOut(K, lv, s, form) for s in srcs]
+    for o in single:
+        _gn_fwd_launch(K, lv, o)
+    paired = [_GnFwdOut(K, lv, s, form) for s in srcs]
+    _gn_fwd_launch(K, lv, *paired)
+    for s, q, ref in zip(single, paired, refs):
+        assert q.same(s)
+        assert bool(torch.isfinite(q.stats).all()) and (q.y is None or bool(torch.isfinite(q.y.float()).all()))
+        if form == "bf16":
+            continue
+        assert _same_bits(q.stats, ref.stats) and _same_bits(q.zhat, ref.zhat)
+        if q.y is not None:
+            assert _same_bits(q.y, ref.y) and K.amax_value(q.y_slot) == float(ref.y.abs().max())
+        if q.planes is not None and q.planes.kind == "b3":
+            assert torch.equal(q.planes.to_float(), ref.y)
+        elif q.planes is not None:
+            _pairs_close(K, q.planes, ref.y)
+
+
+def test_groupnorm_bwd_output_forms(K, gn_forms_case):
+    """dz as fp32, as bf16 triples and as fp16 pairs: dz, dgamma and dbeta of the fp32 + planes call are those of the fp32-only
+    call bit for bit, the planes-only call writes the same planes, and the planes hold dz (triples: exactly; pairs: the pair rule)"""
+    lv, srcs, refs, dy = gn_forms_case
+    (z, gamma, beta), fwd = srcs[0], refs[0]
+
+    def run(with_dz, kind):
+        dz = torch.full_like(z, NAN) if with_dz else None
+        planes = K.Planes(lv.rows, 256, device=DEV, kind=kind) if kind else None
+        if kind:
+            planes.t.fill_(NAN)
+        dg, db = torch.full((256,), NAN, device=DEV), torch.full((256,), NAN, device=DEV)
+        K.gn_relu_bwd(lv, dy, z, fwd.stats, gamma, beta, dg, db, fwd.ws, dz=dz, planes=planes, zhat_amax=fwd.zhat)
+        return dz, planes, dg, db
+
+    dz, _, dg, db = run(True, None)
+    assert all(bool(torch.isfinite(t).all()) for t in (dz, dg, db))
+    for kind in ("b3", "h2"):
+        dz2, both, dg2, db2 = run(True, kind)
+        assert _same_bits(dz2, dz) and _same_bits(dg2, dg) and _same_bits(db2, db)
+        _, only, dg3, db3 = run(False, kind)
+        assert _same_bits(only, both) and _same_bits(dg3, dg) and _same_bits(db3, db)
+        if kind == "b3":
+            assert torch.equal(both.to_float(), dz)
+        else:
+            _pairs_close(K, both, dz)

@@ -245,6 +245,75 @@ def test_host_only_entry_points():
     assert lib.radet_assign_ws_bytes(4, 6400) >= 4 * 6400 * 32
 
 
+def test_layer_entry_points_refuse_bad_arguments_before_any_launch():
+    """The seven layer entry points (stem, max-pool, GroupNorm forward / backward, upsample-add forward / backward, ReLU
+    backward) check their arguments before the first HIP call: with dummy device pointers and no device, a refused call returns
+    -1 (a launch attempt would return -2 here, or fault on the pointers).  RADET_LAYER_<N> of the header is kernels.LAYER_<N>."""
+    from radet_amd import _lib, kernels as K
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    hdr = open(os.path.join(REPO, "include", "radet_hip.h")).read()
+    defs = {n: int(v, 0) for n, v in re.findall(r"^\s*RADET_LAYER_([A-Z0-9_]+)\s*=\s*(0x[0-9A-Fa-f]+)", hdr, re.M)}
+    assert defs == dict(BF16=K.LAYER_BF16, PAIRS=K.LAYER_PAIRS) == dict(BF16=1, PAIRS=2)
+    lib = _lib.load()
+    BF16, PAIRS, UNKNOWN = K.LAYER_BF16, K.LAYER_PAIRS, 0x4
+    P = 0x10000                                                        # a non-null "device pointer" that is never dereferenced
+    seg = (ctypes.c_int * 6)(4, 4, 4, 4, 0, 0)
+    refused = []
+
+    def stem(flags=0, y_amax=None):
+        refused.append(lib.radet_stem_conv_bn_relu(P, P, P, P, 1, 8, 8, flags, y_amax, None))
+
+    def pool(flags=0, C=64, y_amax=None, yq=None, yq_amax=None, x_amax=None):
+        refused.append(lib.radet_maxpool3x3s2(P, P, 1, 8, 8, C, flags, y_amax, yq, yq_amax, x_amax, None))
+
+    def gn_fwd(flags=0, a=None, b=None, C=256, groups=32, nseg=1):
+        sets = []
+        for s, z in ((a, P), (b, P if b is not None else None)):      # (a second set with z == NULL: one tensor)
+            d = dict(dict(y=P, planes=None, y_amax=None, planes_amax=None, zhat_amax=None), **(s or {}))
+            sets += [z, P, P, d["y"], d["planes"], P, P, d["y_amax"], d["planes_amax"], d["zhat_amax"]]
+        refused.append(lib.radet_gn_relu_fwd(*sets, 2, C, groups, 1e-5, 1, flags, seg, nseg, None))
+
+    def gn_bwd(flags=0, dz=P, planes=None, dy_amax=None, zhat_amax=None, planes_amax=None, C=256, groups=32, nseg=1):
+        refused.append(lib.radet_gn_relu_bwd(P, P, P, P, P, dz, planes, P, P, P, 2, C, groups, 1, flags, seg, nseg, None, dy_amax,
+                                             zhat_amax, planes_amax))
+
+    def up(fn, flags=0, C=256, amax=None):
+        refused.append(fn(P, P, 1, 8, 8, 4, 4, C, flags, amax, None))
+
+    def relu(flags=0, n=8, amax=None):
+        refused.append(lib.radet_relu_bwd(P, None, P, P, n, flags, amax, None))
+
+    # an unknown flag bit; a bit the operation has no use for
+    stem(UNKNOWN), pool(UNKNOWN), gn_fwd(UNKNOWN), gn_bwd(UNKNOWN), relu(UNKNOWN), stem(PAIRS), relu(PAIRS)
+    up(lib.radet_upsample_add, UNKNOWN), up(lib.radet_upsample_add_bwd, UNKNOWN), up(lib.radet_upsample_add, PAIRS)
+    # bf16 storage with a plane pointer, with an amax pointer, with pairs
+    pool(BF16 | PAIRS, yq=P, yq_amax=P, x_amax=P), pool(BF16, yq=P), gn_fwd(BF16, dict(planes=P)), gn_bwd(BF16, planes=P)
+    gn_fwd(BF16, dict(), dict(planes=P)), gn_fwd(BF16 | PAIRS), gn_bwd(BF16 | PAIRS)
+    stem(BF16, P), pool(BF16, y_amax=P), pool(BF16, x_amax=P), relu(BF16, amax=P)
+    up(lib.radet_upsample_add, BF16, amax=P), up(lib.radet_upsample_add_bwd, BF16, amax=P)
+    gn_fwd(BF16, dict(y_amax=P)), gn_fwd(BF16, dict(zhat_amax=P)), gn_fwd(BF16, dict(planes_amax=P)), gn_fwd(BF16, dict(), dict(y_amax=P))
+    gn_bwd(BF16, dy_amax=P), gn_bwd(BF16, zhat_amax=P), gn_bwd(BF16, planes_amax=P)
+    # pairs without the amax pointers they are scaled with; a pair copy of the max-pool without the flag
+    pool(PAIRS, yq=P, x_amax=P), pool(PAIRS, yq=P, yq_amax=P), pool(0, yq=P, yq_amax=P, x_amax=P)
+    gn_fwd(PAIRS, dict(planes=P)), gn_fwd(PAIRS, dict(planes=P, planes_amax=P), dict(planes=P))
+    gn_bwd(PAIRS, planes=P, dy_amax=P), gn_bwd(PAIRS, planes=P, planes_amax=P)
+    # GroupNorm with neither y nor planes (either tensor of a paired launch), C = 255, groups != 32, nseg out of range
+    gn_fwd(0, dict(y=None)), gn_fwd(0, dict(), dict(y=None)), gn_bwd(0, dz=None)
+    gn_fwd(C=255), gn_bwd(C=255), gn_fwd(groups=16), gn_bwd(groups=16)
+    gn_fwd(nseg=0), gn_bwd(nseg=0), gn_fwd(nseg=9), gn_bwd(nseg=9)
+    # channel counts and lengths the float4 kernels cannot take
+    pool(C=6), pool(PAIRS, C=48, yq=P, yq_amax=P, x_amax=P), up(lib.radet_upsample_add, C=6), up(lib.radet_upsample_add_bwd, C=6)
+    relu(n=6), relu(BF16, n=6)
+    assert len(refused) == 54 and set(refused) == {-1}, refused
+    # the wrappers' earlier positional forms do not bind (the backward's had dz where dgamma is now)
+    with pytest.raises(TypeError):
+        K.gn_relu_bwd(*[None] * 11)
+    with pytest.raises(TypeError):
+        K.gn_relu_fwd(*[None] * 7)
+
+
 def test_config_and_registry_dropin():
     from radet_amd import models
     from radet_amd.utils import Config

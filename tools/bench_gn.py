@@ -32,6 +32,6 @@ for dt in (torch.float32, torch.bfloat16):
         return s.elapsed_time(e) / n * 1e3
 
     es = z.element_size()
-    tf = timeit(lambda: K.gn_relu_fwd(lv, z, gamma, beta, y, stats, ws))
-    tb = timeit(lambda: K.gn_relu_bwd(lv, dy, z, stats, gamma, beta, dz, dg, db, ws))
+    tf = timeit(lambda: K.gn_relu_fwd(lv, K.GnFwd(z, gamma, beta, stats, ws, y=y)))
+    tb = timeit(lambda: K.gn_relu_bwd(lv, dy, z, stats, gamma, beta, dg, db, ws, dz=dz))
     print(f"{dt}: R={R} fwd {tf:.1f} us = {3 * R * 256 * es / tf / 1e3:.0f} GB/s | bwd {tb:.1f} us = {5 * R * 256 * es / tb / 1e3:.0f} GB/s")

@@ -106,22 +106,22 @@ def run_gn(lv):
     y, yp = torch.empty_like(z), Planes(R, 256, device=dev)
     stats = torch.empty(len(lv) * lv.B * 64, device=dev)
     ws = torch.empty(K.gn_ws_floats(lv), device=dev)
-    K.gn_relu_fwd(lv, z, gam, bet, y, stats, ws)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, y=y))
     y2 = torch.empty_like(z)
-    K.gn_relu_fwd_p(lv, z, gam, bet, y2, yp, stats, ws)
+    K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, y=y2, planes=yp))
     torch.cuda.synchronize()
     print("== GN fwd planes exact:", torch.equal(yp.to_float(), y), torch.equal(y2, y),
-          f"fp32 {timeit(lambda: K.gn_relu_fwd(lv, z, gam, bet, y, stats, ws)):.1f} us, planes only "
-          f"{timeit(lambda: K.gn_relu_fwd_p(lv, z, gam, bet, None, yp, stats, ws)):.1f} us")
+          f"fp32 {timeit(lambda: K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, y=y))):.1f} us, planes only "
+          f"{timeit(lambda: K.gn_relu_fwd(lv, K.GnFwd(z, gam, bet, stats, ws, planes=yp))):.1f} us")
     dy = torch.randn(R, 256, device=dev)
     dz, dzp = torch.empty_like(z), Planes(R, 256, device=dev)
     dg, db = torch.empty(256, device=dev), torch.empty(256, device=dev)
-    K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dz, dg, db, ws)
-    K.gn_relu_bwd_p(lv, dy, z, stats, gam, bet, None, dzp, dg, db, ws)
+    K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dg, db, ws, dz=dz)
+    K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dg, db, ws, planes=dzp)
     torch.cuda.synchronize()
     print("== GN bwd planes exact:", torch.equal(dzp.to_float(), dz),
-          f"fp32 {timeit(lambda: K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dz, dg, db, ws)):.1f} us, planes "
-          f"{timeit(lambda: K.gn_relu_bwd_p(lv, dy, z, stats, gam, bet, None, dzp, dg, db, ws)):.1f} us")
+          f"fp32 {timeit(lambda: K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dg, db, ws, dz=dz)):.1f} us, planes "
+          f"{timeit(lambda: K.gn_relu_bwd(lv, dy, z, stats, gam, bet, dg, db, ws, planes=dzp)):.1f} us")
     x = torch.randn(R, 256, device=dev)
     xp = Planes(R, 256, device=dev)
     print(f"== split_planes R={R}: {timeit(lambda: K.split_planes(x, xp)):.1f} us")
