@@ -664,6 +664,54 @@ int radet_cutout_u8(uint8_t* img, size_t img_px, const int* desc, int nimg, cons
 int radet_cutout_f32(float* out, int nbatch, int Hp, int Wp, const int* desc, int nimg, const int* holes, int nholes, int max_holes,
                      int max_area, float m0, float m1, float m2, float s0, float s1, float s2, void* stream);
 
+/* ---- AutoAugment's colour stages (csrc/color.hip; radet/datasets/pipelines/auto_augment.py:709-890: ColorTransform,
+ *      EqualizeTransform, BrightnessTransform, ContrastTransform) on nimg packed u8 HWC BGR images, in place, two launches.
+ *      desc (device) = nimg rows of COLOR_DESC_INTS ints: [COLOR_DESC_OFF] pixel offset of the image in the packed buffer
+ *      (byte 3 * offset: any alignment), [COLOR_DESC_H], [COLOR_DESC_W], [COLOR_DESC_KIND] (COLOR_BRIGHTNESS, COLOR_CONTRAST,
+ *      COLOR_COLOR, COLOR_EQUALIZE; any other value: the row is not run), [COLOR_DESC_ALPHA] / [COLOR_DESC_BETA] the fp32
+ *      bits of alpha = fl32(factor) and beta = fl32(1 - factor) (1 - factor formed in double; fl32 = one rounding to
+ *      nearest even), [COLOR_DESC_FLAGS] (COLOR_SKIP: the image is left alone), one spare word.
+ *      The pixel rules are this project's restatement of mmcv 1.3.18 (adjust_brightness / adjust_contrast / adjust_color /
+ *      imequalize) on OpenCV 4; neither is installed where this is developed, so parity with their PIXELS is unpinned (as
+ *      for radet_warp_affine_u8), the stages' planning is pinned to the reference.  x = a channel byte, N = h * w,
+ *          gray(b, g, r) = (3735 b + 19235 g + 9798 r + 16384) >> 15                 (OpenCV 4's u8 BGR2GRAY)
+ *          hist[c][v] = the number of pixels with value v in channel c (B, G, R), ghist[v] the same of the gray image
+ *      Brightness: t = fl32(x * alpha), clipped to [0, 255], truncated: one 256-entry map for the three channels.
+ *      Contrast:   mean = sum(v * ghist[v]) / N rounded half to even, in integers (= Python's round(float64(S) / N) for
+ *                  every image up to 8192 x 8192); m = fl32(mean * beta), rounded on its own; t = fma(x, alpha, m), clipped,
+ *                  truncated: one 256-entry map.
+ *      Color:      per pixel g = gray(pixel); per channel t = fma(x, alpha, fl32(g * beta)), rounded half to even,
+ *                  saturated to [0, 255].
+ *      Equalize:   per channel c: last = the highest v with hist[c][v] > 0, step = (N - hist[c][last]) / 255 (integer);
+ *                  step == 0: the channel is unchanged; else lut[v] = min(255, (sum_{u < v} hist[c][u] + step / 2) / step).
+ *      The fused multiply-add (one rounding of x * alpha + m) is this project's choice where OpenCV's scalar and SIMD paths
+ *      of addWeighted may differ; the product g * beta / mean * beta is never contracted into it.
+ *      radet_color_stats_u8: hist u32 [nimg, 4, 256] = hist of B, G, R and ghist of every row whose kind is COLOR_EQUALIZE or
+ *      COLOR_CONTRAST, ADDED to what hist holds (integer atomics: bit-reproducible): the caller zeroes it.  Other rows are
+ *      not read.  radet_color_apply_u8: every row's image mapped in place; hist is read for COLOR_EQUALIZE / COLOR_CONTRAST
+ *      rows (NULL: those rows are not run).  A workgroup takes COLOR_CHUNK_PX pixels of one image; no byte outside the rows'
+ *      images is read or written.  A row with h, w <= 0 or whose image does not lie inside the buffer (img_px pixels,
+ *      < 2^31) is not run.  max_px = the largest image's pixel count; channels must be 3; nimg <= 65535; images up to 8192 a
+ *      side (counts fit 32 bits). */
+#define COLOR_DESC_INTS 8
+#define COLOR_DESC_OFF 0
+#define COLOR_DESC_H 1
+#define COLOR_DESC_W 2
+#define COLOR_DESC_KIND 3
+#define COLOR_DESC_ALPHA 4
+#define COLOR_DESC_BETA 5
+#define COLOR_DESC_FLAGS 6
+#define COLOR_SKIP 1
+#define COLOR_BRIGHTNESS 1
+#define COLOR_CONTRAST 2
+#define COLOR_COLOR 3
+#define COLOR_EQUALIZE 4
+#define COLOR_CHUNK_PX 4096
+int radet_color_stats_u8(const uint8_t* img, size_t img_px, const int* desc, int nimg, int max_px, unsigned* hist, int channels,
+                         void* stream);
+int radet_color_apply_u8(uint8_t* img, size_t img_px, const int* desc, int nimg, int max_px, const unsigned* hist, int channels,
+                         void* stream);
+
 /* ---- in-memory frames through the test pipeline in one launch (csrc/preprocess.hip): LoadImageFromWebcam -> Resize ->
  *      Normalize -> Pad (radet/datasets/pipelines/loading.py:88 as radet/apis/inference.py:97-102 uses it).  nimg u8 HWC BGR
  *      frames of any, mixed sizes -> out f32 [nimg,3,Hp,Wp]: what radet_resize_linear_u8 followed by radet_augment_finish

@@ -97,6 +97,8 @@ SIGNATURES = {
     "radet_warp_affine_u8": (_i, [_p, _sz, _p, _sz, _p, _i, _i, _i, _p]),
     "radet_cutout_u8": (_i, [_p, _sz, _p, _i, _p, _i, _i, _i, _i, _p]),
     "radet_cutout_f32": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p]),
+    "radet_color_stats_u8": (_i, [_p, _sz, _p, _i, _i, _p, _i, _p]),
+    "radet_color_apply_u8": (_i, [_p, _sz, _p, _i, _i, _p, _i, _p]),
     "radet_gaussian_blur9_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "radet_sobel_edge": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "radet_convert_rows": (_i, [_p, _p, _sz, _i, _i, _i, _i, _i, _i, _p]),

@@ -29,6 +29,9 @@ entry (radet_warp_affine_u8: cv2.warpAffine's classic fixed-point bilinear path)
 CutOut (in that block, bare or in AutoAugment policies, or behind the photometric stages in front of RandomFlip): the stage
 plans its holes; run() fills them per entry rank on the packed u8 frames (radet_cutout_u8, next to the warp launch of that
 rank) or, for the late position, in the finished f32 batch (radet_cutout_f32 after radet_augment_finish).
+Colour stages (ColorTransform, EqualizeTransform, BrightnessTransform, ContrastTransform, in that block, bare or in the
+policies of an AutoAugment(color_stages=True)): the stage plans its gate and factor; run() maps the packed u8 frames at the entry's rank
+(radet_color_stats_u8 for the histograms Equalize and Contrast need, radet_color_apply_u8 in place).
 Options the RADet configs do not use raise NotImplementedError."""
 import collections
 import glob
@@ -56,7 +59,8 @@ _ORDER = ("LoadImageFromFile", "LoadAnnotations", "MultiScaleFlipAug", "Expand",
           "DefaultFormatBundle", "ImageToTensor", "Collect")
 _ZOOM = ("Expand", "MinIoURandomCrop")                       # the source-window stages
 _AFFINE = ("Rotate", "Shear", "Translate", "AutoAugment")    # the warp stages: one block in the "Affine" slot of _ORDER
-_BLOCK = _AFFINE + ("CutOut",)                               # what may stand in that block (a CutOut elsewhere is a late one)
+# what may stand in that block (a CutOut elsewhere is a late one; a colour stage elsewhere is refused)
+_BLOCK = _AFFINE + ("CutOut", "ColorTransform", "EqualizeTransform", "BrightnessTransform", "ContrastTransform")
 _MIX = ("RandomHSV", "RandomNoise", "RandomSmooth")          # the mixpbr stages: aug_hsv_noise + aug_box
 _COSY_ORDER = ("PillowBlur", "PillowSharpness", "PillowContrast", "PillowBrightness", "PillowColor")
 # flags of a params row (include/radet_hip.h)
@@ -557,11 +561,17 @@ def _block_entries(s):
     return len(s["block_ops"]) if "block_ops" in s else len(s.get("affine", ()))
 
 
+# one fired colour stage: a key of K.COLOR_KINDS and the factor (float64; 1.0 for "equalize", which has none)
+ColorOp = collections.namedtuple("ColorOp", "kind factor")
+_BLOCK_KEYS = dict(warp="affine", cutout="cutout", color="color")
+
+
 def _block_list(s):
-    """the entries of the sample's block in the order they ran: (matrix, fill) of s["affine"] and CutHoles of s["cutout"]"""
+    """the entries of the sample's block in the order they ran: (matrix, fill) of s["affine"], CutHoles of s["cutout"] and
+    ColorOp of s["color"]"""
     if "block_ops" not in s:
         return list(s.get("affine", ()))
-    return [s["affine" if kind == "warp" else "cutout"][j] for kind, j in s["block_ops"]]
+    return [s[_BLOCK_KEYS[kind]][j] for kind, j in s["block_ops"]]
 
 
 def rotation_matrix(center, angle, scale):
@@ -784,7 +794,8 @@ class Translate(_AffineStage):
 
 
 _AFFINE_STAGES = ("Rotate", "Shear", "Translate")
-_POLICY_STAGES = _AFFINE_STAGES + ("CutOut",)
+_COLOR_STAGES = ("ColorTransform", "EqualizeTransform", "BrightnessTransform", "ContrastTransform")
+_POLICY_STAGES = _AFFINE_STAGES + ("CutOut",)       # (+ _COLOR_STAGES in an AutoAugment(color_stages=True))
 
 
 def _fill_in_arg(fill_in):
@@ -866,23 +877,103 @@ class CutOut:
         holes.append(CutHoles(rects, self.fill))
 
 
+def enhance_level_to_value(level, a=1.8, b=0.1):
+    """auto_augment.py:18-20: the factor of a colour stage, in Python floats"""
+    return (level / _MAX_LEVEL) * a + b
+
+
+class _ColorStage:
+    """What ColorTransform, EqualizeTransform, BrightnessTransform and ContrastTransform (auto_augment.py:709-890) share,
+    planned: one nprnd.rand() per call, the stage is skipped when it is > prob, no other draw; factor =
+    enhance_level_to_value(level).  A stage that fires is one entry of the block after Resize: it appends ColorOp(kind,
+    factor as float64) to s["color"] and ("color", its index there) to s["block_ops"] (created as CutOut.plan creates it).
+    No pixel is touched here and boxes, labels and masks never are; ImagePipeline.run maps the packed u8 frame at the
+    entry's rank (radet_color_stats_u8 / radet_color_apply_u8), so a stage behind a warp sees the warp's fill pixels."""
+    kind = None
+
+    def _common(self, level, prob):
+        name = type(self).__name__
+        if self.kind != "equalize" and (isinstance(level, bool) or not isinstance(level, (int, float)) or not 0 <= level <= _MAX_LEVEL):
+            raise ValueError(f"{name}: level is a number in [0, {_MAX_LEVEL}], got {level!r}")
+        if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0 <= prob <= 1.0:
+            raise ValueError(f"{name}: prob is in [0, 1], got {prob!r}")
+        self.level, self.prob = level, prob
+        self.factor = 1.0 if self.kind == "equalize" else enhance_level_to_value(level)
+
+    def plan(self, s, rnd, nprnd):
+        if s.get("seg_fields"):
+            _refuse(f"{type(self).__name__} on a sample with seg_fields (semantic segmentation maps; drop the stage or the "
+                    f"seg fields)")
+        if nprnd.rand() > self.prob:
+            return
+        if _block_entries(s) >= _AFFINE_MAX_ENTRIES:
+            _refuse(f"more than {_AFFINE_MAX_ENTRIES} affine stages firing on one sample")
+        ops = s.setdefault("block_ops", [("warp", k) for k in range(len(s.get("affine", ())))])
+        fired = s.setdefault("color", [])
+        ops.append(("color", len(fired)))
+        fired.append(ColorOp(self.kind, float(self.factor)))
+
+
+@PIPELINES.register_module()
+class ColorTransform(_ColorStage):
+    """mmcv.adjust_color(img, factor): every pixel blended with its gray value"""
+    kind = "color"
+
+    def __init__(self, level, prob=0.5):
+        self._common(level, prob)
+
+
+@PIPELINES.register_module()
+class EqualizeTransform(_ColorStage):
+    """mmcv.imequalize(img): every channel mapped through its own histogram"""
+    kind = "equalize"
+
+    def __init__(self, prob=0.5):
+        self._common(None, prob)
+
+
+@PIPELINES.register_module()
+class BrightnessTransform(_ColorStage):
+    """mmcv.adjust_brightness(img, factor): the image blended with black"""
+    kind = "brightness"
+
+    def __init__(self, level, prob=0.5):
+        self._common(level, prob)
+
+
+@PIPELINES.register_module()
+class ContrastTransform(_ColorStage):
+    """mmcv.adjust_contrast(img, factor): the image blended with the mean of its gray image"""
+    kind = "contrast"
+
+    def __init__(self, level, prob=0.5):
+        self._common(level, prob)
+
+
 @PIPELINES.register_module()
 class AutoAugment:
     """The reference's AutoAugment (auto_augment.py:45-108) over the affine stages and CutOut: np.random.choice over the
-    policies on the sample's NumPy generator, then the stages of the chosen policy in order.  s["policy"] = the index drawn."""
+    policies on the sample's NumPy generator, then the stages of the chosen policy in order.  s["policy"] = the index drawn.
+    color_stages=True (this project's argument, the reference has none) lets policies hold ColorTransform, EqualizeTransform,
+    BrightnessTransform and ContrastTransform too; without it a policy that names one is refused, as it was before these
+    stages were built (the existing tests hold that refusal), and the message names the argument."""
 
-    def __init__(self, policies):
+    def __init__(self, policies, color_stages=False):
+        if not isinstance(color_stages, bool):
+            raise ValueError(f"AutoAugment: color_stages is a bool, got {color_stages!r}")
+        allowed = _POLICY_STAGES + (_COLOR_STAGES if color_stages else ())
         if not isinstance(policies, list) or not policies or not all(isinstance(p, list) and p for p in policies):
             raise ValueError("AutoAugment: policies is a non-empty list of non-empty lists")
         for policy in policies:
             for t in policy:
                 if not isinstance(t, dict) or "type" not in t:
                     raise ValueError("AutoAugment: each augmentation is a dict with the key 'type'")
-                if t["type"] not in _POLICY_STAGES:
-                    _refuse(f"AutoAugment policy stage {t['type']} (policies hold {_POLICY_STAGES} only)")
+                if t["type"] not in allowed:
+                    hint = "; pass color_stages=True to AutoAugment for the colour stages" if t["type"] in _COLOR_STAGES else ""
+                    _refuse(f"AutoAugment policy stage {t['type']} (policies hold {allowed} only{hint})")
             if len(policy) > _AFFINE_MAX_ENTRIES:
                 _refuse(f"an AutoAugment policy of {len(policy)} stages (at most {_AFFINE_MAX_ENTRIES} affine entries per sample)")
-        self.policies = [[dict(t) for t in policy] for policy in policies]
+        self.policies, self.color_stages = [[dict(t) for t in policy] for policy in policies], color_stages
         self.transforms = [[build_from_cfg(t, PIPELINES) for t in policy] for policy in self.policies]
 
     def plan(self, s, rnd, nprnd):
@@ -1335,10 +1426,19 @@ class ImagePipeline:
         stop = start
         while stop < len(names) and names[stop] in _BLOCK:
             stop += 1
-        block = [k for k, n in enumerate(names) if n in _AFFINE or (n == "CutOut" and start <= k < stop)]
+        block = [k for k, n in enumerate(names) if n in _AFFINE or (n in ("CutOut",) + _COLOR_STAGES and start <= k < stop)]
         late = [k for k, n in enumerate(names) if n == "CutOut" and k not in block]
         if "CutOut" in names and any(isinstance(t, MultiScaleFlipAug) for t in flat):
             _refuse("CutOut in a MultiScaleFlipAug (test) pipeline")
+        # the colour stages work on the packed u8 frames of that block and nowhere else
+        for k, n in enumerate(names):
+            if n in _COLOR_STAGES and any(isinstance(t, MultiScaleFlipAug) for t in flat):
+                _refuse(f"{n} in a MultiScaleFlipAug (test) pipeline (the colour stages are training augmentation: take it out "
+                        f"of the test pipeline)")
+            if n in _COLOR_STAGES and k not in block:
+                _refuse(f"{n} at position {k} of {names} (the colour stages stand in the block directly after Resize -- or after "
+                        f"the RandomCrop behind it --, bare next to Rotate / Shear / Translate / CutOut or inside one AutoAugment(color_stages=True): "
+                        f"move it there)")
         for k in late:
             flat[k].late = True
         if block:
@@ -1579,39 +1679,63 @@ class ImagePipeline:
         entry is not a warp is copied (WARP_SKIP) --, then one radet_cutout_u8 launch, in place, if any image's k-th entry
         is a CutOut (the other images are skip rows).  So a hole cut at a lower rank is warped with the image and one cut at
         a higher rank is axis-aligned.  One descriptor upload for all ranks: the warp rows, then (only when some entry is a
-        CutOut) the CutOut rows and the hole table.  Returns the buffer that holds the result."""
+        CutOut) the CutOut rows and the hole table, then (only when some entry is a colour stage) the colour rows.  A ColorOp
+        at rank k: after the warp and CutOut launches of that rank, one radet_color_stats_u8 launch if any image's k-th entry
+        is 'equalize' or 'contrast' (into its own slice of one histogram buffer, zeroed once per batch by radet_fill_zero),
+        then one radet_color_apply_u8 launch, in place (the other images are skip rows).  Returns the buffer that holds
+        the result."""
         ranks, n = max(len(e) for e in entries), len(entries)
         if not ranks:
             return img
         cut = any(isinstance(x, CutHoles) for e in entries for x in e)
+        col = any(isinstance(x, ColorOp) for e in entries for x in e)
         W = np.zeros((ranks, n, K.WARP_DESC_INTS), np.int32)
         D = np.zeros((ranks, n, K.CUTOUT_DESC_INTS), np.int32) if cut else None
+        CD = np.zeros((ranks, n, K.COLOR_DESC_INTS), np.int32) if col else None
         holes, first, dims = [], 0, []
         for k in range(ranks):
             kth = [(e[k] if k < len(e) else None) for e in entries]
             for i, (x, o, (h, w)) in enumerate(zip(kth, offs, hw)):
-                K.warp_desc_row(W[k, i], o, o, h, w, channels, *((None,) if x is None or isinstance(x, CutHoles) else x))
+                K.warp_desc_row(W[k, i], o, o, h, w, channels, *((None,) if x is None or isinstance(x, (CutHoles, ColorOp)) else x))
                 if isinstance(x, CutHoles):
                     K.cutout_desc_row(D[k, i], o, h, w, x.fill, first, len(x.rects))
                     holes.append(np.asarray(x.rects, np.int32).reshape(-1, 4))
                     first += len(x.rects)
                 elif cut:
                     K.cutout_desc_row(D[k, i], o, h, w, skip=True)
-            dims.append((any(x is not None and not isinstance(x, CutHoles) for x in kth),
-                         *K.cutout_launch_dims([x.rects if isinstance(x, CutHoles) else None for x in kth], hw)))
-        parts = [W] + ([D, np.concatenate(holes)] if cut else [])
+                if isinstance(x, ColorOp):
+                    K.color_desc_row(CD[k, i], o, h, w, x.kind, x.factor)
+                elif col:
+                    K.color_desc_row(CD[k, i], o, h, w, skip=True)
+            dims.append((any(x is not None and not isinstance(x, (CutHoles, ColorOp)) for x in kth),
+                         *K.cutout_launch_dims([x.rects if isinstance(x, CutHoles) else None for x in kth], hw),
+                         any(isinstance(x, ColorOp) for x in kth),
+                         any(isinstance(x, ColorOp) and x.kind in K.COLOR_STATS_KINDS for x in kth)))
+        parts = [W] + ([D, np.concatenate(holes)] if cut else []) + ([CD] if col else [])
         up = torch.from_numpy(np.concatenate([a.reshape(-1) for a in parts])).to(dev)
         wdesc = up[:W.size].view(ranks, n, K.WARP_DESC_INTS)
         if cut:
-            cdesc, table = up[W.size:W.size + D.size].view(ranks, n, K.CUTOUT_DESC_INTS), up[W.size + D.size:].view(-1, 4)
+            cdesc = up[W.size:W.size + D.size].view(ranks, n, K.CUTOUT_DESC_INTS)
+            table = up[W.size + D.size:up.numel() - (CD.size if col else 0)].view(-1, 4)
+        hist = None
+        if col:
+            coldesc = up[up.numel() - CD.size:].view(ranks, n, K.COLOR_DESC_INTS)
+            if any(d[4] for d in dims):
+                hist = torch.empty((ranks, n, 4, 256), dtype=torch.int32, device=dev)
+                K.fill_zero(hist)
+        max_px = max(h * w for h, w in hw)
         cur, other = img, None
-        for k, (warp, most, area) in enumerate(dims):
+        for k, (warp, most, area, colour, stats) in enumerate(dims):
             if warp:
                 other = torch.empty_like(img) if other is None else other
-                K.warp_affine_u8(cur, other, wdesc[k], n, max(h * w for h, w in hw), channels)
+                K.warp_affine_u8(cur, other, wdesc[k], n, max_px, channels)
                 cur, other = other, cur
             if most and area:
                 K.cutout_u8(cur, cdesc[k], table, n, most, area)
+            if stats:
+                K.color_stats_u8(cur, coldesc[k], hist[k], n, max_px)
+            if colour:
+                K.color_apply_u8(cur, coldesc[k], hist[k] if stats else None, n, max_px)
         return cur
 
     @staticmethod

@@ -1763,6 +1763,46 @@ def cutout_f32(out, desc, holes, n, max_holes, max_area, mean, stdinv):
               *[float(v) for v in stdinv], _stream())
 
 
+# ---------------------------------------------------------------------- AutoAugment's colour stages (csrc/color.hip)
+COLOR_DESC_INTS, COLOR_CHUNK_PX = 8, 4096                   # include/radet_hip.h
+COLOR_SKIP = 1
+COLOR_KINDS = dict(brightness=1, contrast=2, color=3, equalize=4)
+COLOR_STATS_KINDS = ("contrast", "equalize")                # the kinds whose map is built from the image's histogram
+
+
+def color_factors(factor):
+    """(fp32 bits of alpha = fl32(factor), fp32 bits of beta = fl32(1 - factor)), 1 - factor formed in double"""
+    import numpy as np
+    return tuple(int(np.array([v], np.float64).astype(np.float32).view(np.int32)[0]) for v in (factor, 1.0 - float(factor)))
+
+
+def color_desc_row(row, off, h, w, kind=None, factor=1.0, skip=False):
+    """fills one int32 [COLOR_DESC_INTS] row.  off: the image's pixel offset in the packed u8 buffer; kind: a key of
+    COLOR_KINDS (None: the row is not run); factor: the stage's factor as a Python float (unused by 'equalize')"""
+    alpha, beta = color_factors(factor)
+    row[:] = [off, h, w, COLOR_KINDS[kind] if kind is not None else 0, alpha, beta, COLOR_SKIP if skip else 0, 0]
+
+
+def color_stats_u8(img, desc, hist, n, max_px, channels=3):
+    """img: the packed u8 BGR device buffer; desc i32 [n, COLOR_DESC_INTS]; hist u32-as-i32 [n, 4, 256], zeroed by the
+    caller: the histograms of B, G, R and gray of every 'equalize' / 'contrast' row's image are added to it, one launch"""
+    assert img.dtype == torch.uint8 and img.is_contiguous()
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.numel() >= n * COLOR_DESC_INTS
+    assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.numel() >= n * 4 * 256
+    _lib.call("radet_color_stats_u8", _ptr(img), C.c_size_t(img.numel() // 3), _ptr(desc), int(n), int(max_px), _ptr(hist),
+              int(channels), _stream())
+
+
+def color_apply_u8(img, desc, hist, n, max_px, channels=3):
+    """img: the packed u8 BGR device buffer, changed in place: every row's image under the row's colour stage, one launch;
+    hist: what color_stats_u8 filled for the same rows (None when no row is 'equalize' / 'contrast')"""
+    assert img.dtype == torch.uint8 and img.is_contiguous()
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.numel() >= n * COLOR_DESC_INTS
+    assert hist is None or (hist.dtype == torch.int32 and hist.is_contiguous() and hist.numel() >= n * 4 * 256)
+    _lib.call("radet_color_apply_u8", _ptr(img), C.c_size_t(img.numel() // 3), _ptr(desc), int(n), int(max_px), _ptr(hist),
+              int(channels), _stream())
+
+
 def resize_linear_f(src, sdesc, dst, ddesc, n, max_dst_px):
     _lib.call("radet_resize_linear_f", _ptr(src), _ptr(sdesc), _ptr(dst), _ptr(ddesc), n, max_dst_px,
               1 if src.dtype == torch.float64 else 0, _stream())
