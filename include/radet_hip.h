@@ -426,6 +426,52 @@ int radet_soft_nms(const float* boxes, const float* scores, const int64_t* label
                    float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_keep, int* out_count,
                    void* ws, void* stream);
 
+/* ---- detections tracked across frames (csrc/track.hip), one launch per batch of consecutive frames.  The reference has no
+ *      tracker: these are this project's OWN rules (parity: UNPINNED), pinned bit for bit to the NumPy restatement
+ *      tests/_track_ref.py.  The default parameters (Python: ops/track.py) are starting points nobody has evaluated.
+ *   A SEQUENCE (one camera) holds TRACK_MAX_TRACKS = 256 slots; a zero-filled state is the empty tracker.  Ids start at 1;
+ *   id 0 means "no track".  State of sequence s: TRACK_STATE_BYTES bytes at state + s * TRACK_STATE_BYTES (16-byte aligned):
+ *        box f32 [256,4] (the current estimate) | vel f32 [256,4] (per-frame displacement of the four coordinates) |
+ *        label i32 [256] | id i32 [256] (0: the slot is free) | misses i32 [256] | hits i32 [256] | score f32 [256] |
+ *        next_id i32 (the last id handed out), frames i32, refused i32, one i32 of padding
+ *   Inputs as radet_nms emits them: boxes [nseq,B,cap,4], scores [nseq,B,cap], labels i64, counts [nseq,B] (clamped to
+ *   [0, cap]); the B frames of a sequence are consecutive in time and run one after the other.  Per frame, in this order --
+ *   all arithmetic fp32, every operation rounded once, min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b,
+ *   area = (x2 - x1) * (y2 - y1):
+ *   1. predict: for every slot pred = box + vel, one add per coordinate (motion TRACK_MOTION_NONE: pred = box; vel is then
+ *      neither read nor written, except that a new track's is zeroed).
+ *   2. the detections are visited in the order given (rank order).  ELIGIBLE: four finite coordinates, a finite score,
+ *      score >= track_thr, 0 <= label < 2^31.  An ineligible detection gets id 0 and touches nothing.
+ *   3. match: candidate slots are live (id != 0), not yet matched in this frame, of index < max_tracks and -- with class_aware
+ *      -- of the detection's label.  IoU of pred (a) against the detection (b): iw = max(min(x2a, x2b) - max(x1a, x1b), 0), ih
+ *      likewise, inter = iw * ih, union = (area_a + area_b) - inter, iou = inter / union.  A slot qualifies with iou >=
+ *      iou_thr (a NaN IoU -- two zero-area boxes -- never does); the highest IoU wins, equal IoUs go to the lower slot.  On a
+ *      match: vel = det - box (one subtraction per coordinate against the estimate of one frame ago, observed or coasted; no
+ *      division), box = det, score = the detection's, misses = 0, hits += 1; the detection's id is the slot's.
+ *   4. start: an unmatched eligible detection with score >= new_thr takes the lowest slot below max_tracks that is free AT
+ *      THIS MOMENT (slots that expire in step 5 of this frame are free from the next frame on): id = ++next_id, box = det,
+ *      vel = 0, label, score, hits = 1, misses = 0, and the slot counts as matched for the rest of the frame.  No free slot:
+ *      id 0 and refused += 1.  Below new_thr: id 0.
+ *   5. age: every live slot not matched in this frame gets misses += 1; with misses > max_age it is freed (id = 0, its other
+ *      fields stay as they are), otherwise box = pred (the track coasts, vel unchanged).
+ *   6. frames += 1.
+ *   Outputs [nseq,B,cap]: ids i32 (0: none), hits i32 (the track's hits after the update, 0 where the id is 0); slots at or
+ *   beyond a frame's count are written as 0.  One wave per sequence: the 256 slots live in registers, four per lane (slot =
+ *   4 * lane + j), detections are read 64 at a time and broadcast from registers; no LDS, no barriers, no atomics, no host
+ *   synchronisation, no allocation.
+ *   RADET_ERR_ARG before any launch: nseq, B or cap < 1, cap > TRACK_MAX_DETS, max_tracks outside [1, TRACK_MAX_TRACKS],
+ *   iou_thr outside (0, 1], max_age < 0, a non-finite threshold, an unknown motion, class_aware not 0 / 1, a NULL or
+ *   misaligned (boxes, state: 16 bytes) pointer. */
+#define TRACK_MAX_TRACKS 256
+#define TRACK_MAX_DETS 4096
+#define TRACK_STATE_BYTES 13328          /* 256 * (16 + 16 + 5 * 4) + 16 */
+#define TRACK_MOTION_NONE 0
+#define TRACK_MOTION_CONSTANT 1
+size_t radet_track_state_bytes(int nseq);
+int radet_track_update(const float* boxes, const float* scores, const int64_t* labels, const int* counts, int nseq, int B,
+                       int cap, void* state, float iou_thr, float track_thr, float new_thr, int max_age, int max_tracks,
+                       int motion, int class_aware, int* ids, int* hits, void* stream);
+
 /* ---- visibility-guided positive-sample assigner (radet/datasets/pipelines/label_assignment.py:57-201).
  *      One image per workgroup.  masks u8 [sumG, H, W]; rng_words u32 [B, U] = the next U raw 32-bit outputs of the image's
  *      RandomState (MT19937; a random_sample() is two words); out p2g i64 [B,N], pw f32 [B,N], used i32 [B] (words

@@ -89,6 +89,8 @@ SIGNATURES = {
     "radet_nms": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "radet_soft_nms_ws_bytes": (_sz, [_i, _i]),
     "radet_soft_nms": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "radet_track_state_bytes": (_sz, [_i]),
+    "radet_track_update": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _f, _f, _f, _i, _i, _i, _i, _p, _p, _p]),
     "radet_assign_ws_bytes": (_sz, [_i, _i]),
     "radet_assign_points": (_i, [_p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
     "radet_assign_points_f": (_i, [_p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),

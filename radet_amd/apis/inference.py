@@ -474,6 +474,76 @@ def draw_frames(model, frames, batch_size=8, on_device=False, inplace=False, **s
         stream.close()
 
 
+_TRACK_KEYS = ("iou_thr", "track_thr", "new_thr", "max_age", "max_tracks", "motion", "class_aware")
+
+
+def track_frames(model, frames, batch_size=8, on_device=False, tracker=None, crops=None, **params):
+    """Generator over an iterable of frames of ONE camera, as detect_frames: yields (result, ids) per frame, in order -- ids[i]
+    is the track of the frame's i-th detection (0: none), the same number for the same object instance from frame to frame.
+    When a batch's detections are handed out its frames go through `ops.Tracker.update` in ONE HIP launch on the caller's
+    stream (include/radet_hip.h, radet_track_update: greedy IoU association in rank order against a constant-velocity
+    prediction; this project's own rules, parity unpinned, the defaults not evaluated on any data).
+    on_device=True: result is the (dets f32 [k,5], labels i64 [k]) device tensors and ids an i32 device view of length k;
+    nothing is read back.  on_device=False: result is the per-class list of ndarray [k,5] and ids a list of one i32 ndarray
+    per class, regrouped exactly as bbox2result regroups the boxes; the ids of a whole batch come back in one copy.
+    tracker: an ops.Tracker of one sequence to continue (its numbering goes on across calls; tracker.tracks() reads the live
+    tracks, coasting ones included); otherwise one is made from **params (ops.track.track_params: iou_thr, track_thr, new_thr,
+    max_age, max_tracks, motion, class_aware).  crops=dict(size=..., ...) as for detect_frames: yields (result, ids, Crops of
+    that frame); the track of crop j is ids[crops.index[:, 1]][j].  set_tta / set_tiling work unchanged underneath.
+    Refused: a tracker of several sequences (one generator is one camera), a tracker together with **params, unknown
+    keyword arguments (TypeError)."""
+    from collections import deque
+    from ..ops.draw import pad_detections
+    from ..ops.track import Tracker
+    if batch_size < 1:
+        raise ValueError(f"batch_size={batch_size}")
+    unknown = set(params) - set(_TRACK_KEYS)
+    if unknown:
+        raise TypeError(f"track_frames: unknown tracker arguments {sorted(unknown)}")
+    if tracker is None:
+        tracker = Tracker(**params)
+    elif params:
+        raise TypeError(f"track_frames: a tracker was passed in together with {sorted(params)}; its parameters are its own")
+    elif not isinstance(tracker, Tracker) or tracker.sequences != 1:
+        raise ValueError("track_frames: tracker= takes an ops.Tracker of one sequence (one generator is one camera)")
+    num_classes = model.bbox_head.num_classes
+    sizes = deque()
+
+    def counted():
+        n = 0
+        for f in frames:
+            n += 1
+            if n == batch_size:                                      # (noted before the frame that completes its group is taken)
+                sizes.append(n)
+                n = 0
+            yield f
+        if n:
+            sizes.append(n)
+
+    stream = detect_frames(model, counted(), batch_size=batch_size, on_device=True, crops=crops)
+    try:
+        got = []
+        for res in stream:
+            got.append(res)
+            if len(got) < sizes[0]:
+                continue
+            sizes.popleft()
+            dets = got if crops is None else [r[0] for r in got]
+            ids, _ = tracker.update(pad_detections(dets, tracker.dev))
+            host = None if on_device else ids.cpu().numpy()          # (the batch's ids: one copy)
+            for i, (b, l) in enumerate(dets):
+                k = int(b.shape[0])
+                if on_device:
+                    out = ((b, l), ids[i, :k])
+                else:
+                    b, l = b.detach().cpu().numpy(), l.detach().cpu().numpy()
+                    out = (bbox2result(b, l, num_classes), [host[i, :k][l == c] for c in range(num_classes)])
+                yield out if crops is None else out + (got[i][1],)
+            got = []
+    finally:
+        stream.close()
+
+
 def show_result_pyplot(model, img, result, score_thr=0.3, fig_size=(15, 10), title="result", block=True, wait_time=0):
     """radet/apis/inference.py:163: the result drawn over img (model.show_result) and shown with matplotlib; `block` is
     ignored as in the reference"""

@@ -2032,6 +2032,32 @@ def draw_detections(src_desc, dst_desc, B, max_h, max_w, boxes, scores, labels, 
               None if atlas is None else _ptr(atlas), None if atlas is None else _ptr(widths), S, Hc, Wa, _stream())
 
 
+# ---------------------------------------------------------------------- detections tracked across frames (csrc/track.hip)
+TRACK_MAX_TRACKS = 256             # include/radet_hip.h
+TRACK_MAX_DETS = 4096
+TRACK_STATE_BYTES = 13328
+TRACK_MOTIONS = dict(none=0, constant=1)
+
+
+def track_state_bytes(nseq):
+    return int(_lib.load().radet_track_state_bytes(nseq))
+
+
+def track_update(boxes, scores, labels, counts, nseq, B, cap, state, iou_thr, track_thr, new_thr, max_age, max_tracks, motion,
+                 class_aware, ids, hits):
+    """one launch: the B consecutive frames of each of nseq sequences -- boxes f32 [nseq,B,cap,4], scores f32 [nseq,B,cap],
+    labels i64, counts i32 [nseq,B] -- through the trackers of state (u8 [nseq, TRACK_STATE_BYTES]); ids / hits i32
+    [nseq,B,cap] are written (include/radet_hip.h)"""
+    assert boxes.dtype == torch.float32 and tuple(boxes.shape) == (nseq, B, cap, 4) and scores.dtype == torch.float32
+    assert tuple(scores.shape) == (nseq, B, cap) and labels.dtype == torch.int64 and tuple(labels.shape) == (nseq, B, cap)
+    assert counts.dtype == torch.int32 and counts.numel() == nseq * B
+    assert state.numel() * state.element_size() == nseq * TRACK_STATE_BYTES
+    assert all(t.dtype == torch.int32 and tuple(t.shape) == (nseq, B, cap) for t in (ids, hits))
+    _lib.call("radet_track_update", _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(counts), int(nseq), int(B), int(cap),
+              _ptr(state), float(iou_thr), float(track_thr), float(new_thr), int(max_age), int(max_tracks), int(motion),
+              int(class_aware), _ptr(ids), _ptr(hits), _stream())
+
+
 # ---------------------------------------------------------------------- COCO-protocol evaluation (csrc/cocoeval.hip)
 COCO_MAX_GT = 512                  # RADET_COCO_MAX_GT of include/radet_hip.h: ground truths per (category, image) segment
 COCO_ERR_OVERSIZE = -3             # RADET_ERR_COCO_OVERSIZE

@@ -11,7 +11,7 @@ from .. import kernels as K
 __all__ = ["vote_nms", "global_vote_nms", "cluster_nms", "batched_nms", "soft_nms", "MBD_box2distance", "GDT_box2distance", "MBD", "GDT",
            "mbd_batch", "gdt_batch", "border_seeds", "resize_batch", "gaussian_blur9_batch", "sobel_edge_batch", "crop_detections",
            "Crops", "merge_view_candidates", "plan_tiles", "merge_tile_candidates", "draw_detections", "build_atlas",
-           "adjust_brightness", "adjust_contrast", "adjust_color", "imequalize"]
+           "adjust_brightness", "adjust_contrast", "adjust_color", "imequalize", "Tracker", "track_detections"]
 
 _MAX = 65536      # 16-bit positions in the kernel's sort keys (above 8192 the sorts run in global memory)
 
@@ -467,4 +467,5 @@ from .crops import Crops, crop_detections  # noqa: E402  (RoI crops of detection
 from .tta import merge_view_candidates  # noqa: E402  (test-time augmentation: the views' candidates merged per image)
 from .tiles import merge_tile_candidates, plan_tiles  # noqa: E402  (tiled inference: the tile plan, the rows' candidates merged per image)
 from .draw import build_atlas, draw_detections  # noqa: E402  (detections drawn on frames: one overlay launch)
+from .track import Tracker, track_detections  # noqa: E402  (detections tracked across frames: one update launch per batch)
 from .color import adjust_brightness, adjust_color, adjust_contrast, imequalize  # noqa: E402  (mmcv's photometric functions)
